@@ -9,6 +9,12 @@ A step = one pass of get_reconstruction_error over one batch already resident in
   video (--workload video; configs[2]): 64 clips of 10 frames per GPU.
 With N > 1 the frame stream is block-partitioned over ranks (weak scaling, no data-path collective) and each
 step ends with the one all_gather of the score vector (RCCL).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the steps and prints the line.  --full adds everything else the line can carry:
+per-layer events and the roofline of the timed steps, the split / Winograd modes, configs[2] / configs[3] beside the
+headline, the training step, the reference's call sizes, the CPU baseline and the multi-GPU evidence.
+--dump-outputs DIR writes the scores of the last timed step to DIR/scores.npy (float32; inputs are seeded, so two builds
+can be compared output for output).
 """
 from __future__ import annotations
 
@@ -64,8 +70,13 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", choices=["image", "video", "dense"], default="image")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement and check (the --no-* and --stream-frames options below select among them); "
+                         "without it only the headline steps run, with per-layer events off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (the score vector) to DIR/scores.npy as float32")
     ap.add_argument("--stream-frames", type=int, default=-1,
-                    help="configs[3]: also time scoring.score_stream over this many frames (image workload, reported as `stream`); "
+                    help="configs[3] (--full): also time scoring.score_stream over this many frames (image workload, reported as `stream`); "
                          "-1 = 100000 in the default line (image, fp32, default batch / size), 0 = skip")
     ap.add_argument("--no-video", action="store_true", help="skip the secondary configs[2] measurement of the default line")
     ap.add_argument("--stride", type=int, default=1, help="dense workload: window stride")
@@ -78,7 +89,7 @@ def main():
     ap.add_argument("--chunk", type=int, default=0, help="frames/clips per launch group (0 = model default)")
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--clip-len", type=int, default=10)
-    ap.add_argument("--no-layer-events", action="store_true", help="do not bracket layers with hipEvents")
+    ap.add_argument("--no-layer-events", action="store_true", help="--full: do not bracket layers with hipEvents")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-split", action="store_true", help="skip the secondary split-precision measurement")
     ap.add_argument("--no-small", action="store_true", help="skip the secondary measurement of the reference's own call sizes")
@@ -91,6 +102,8 @@ def main():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse N > 1 on one GPU)")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal: all ranks use GPU 0")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -214,7 +227,7 @@ def main():
 
     for _ in range(args.warmup):
         scores = step()
-    events = not args.no_layer_events
+    events = args.full and not args.no_layer_events
     fence()
     if events:
         lib.vad_prof_reset()
@@ -232,6 +245,10 @@ def main():
         elapsed = float(tt.item())
     total_frames = frames_per_step * world * args.steps
     fps = total_frames / elapsed
+    if args.dump_outputs and rank == 0:
+        # the gathered score vector of the last timed step: [items] (image) or [items, T] frame scores (video / dense)
+        Path(args.dump_outputs).mkdir(parents=True, exist_ok=True)
+        np.save(Path(args.dump_outputs) / "scores.npy", scores.detach().to(torch.float32).cpu().numpy())
 
     layers, roofline = None, None
     if events:
@@ -263,7 +280,7 @@ def main():
     # Secondary measurements, same workload and step count: the opt-in arithmetic modes - split-fp16 (3 x fp16 MFMA, fp32
     # accumulate) and Winograd F(2x2,3x3) on the exact-fp32 MFMA (all-fp32, 16 instead of 36 products
     # per 2x2 outputs).  `value` above is always the exact-fp32 direct path.
-    if args.precision == "fp32" and not args.no_split:
+    if args.full and args.precision == "fp32" and not args.no_split:
         exact_scores = scores.clone()
         for mode in ("split", "winograd"):
             if mode == "winograd" and args.workload == "dense":
@@ -299,10 +316,10 @@ def main():
         model.precision = "fp32"
         scores = exact_scores
     # configs[3]: the frame stream generated on the device in chunks of 512, block-partitioned over the ranks, ONE all_gather
-    # at the end; generation is inside the timed region.  Part of the default line (image, fp32, default batch and size: the
-    # driver's `bench.py --gpus N` run); 100,000 frames in total whatever the rank count (strong scaling, its own object).
+    # at the end; generation is inside the timed region.  Part of the default --full line (image, fp32, default batch and
+    # size); 100,000 frames in total whatever the rank count (strong scaling, its own object).
     default_line = args.workload == "image" and args.precision == "fp32" and not args.batch and hw == 256 and args.ingest == "f32" and not args.graph
-    stream_frames = args.stream_frames if args.stream_frames >= 0 else (100000 if default_line else 0)
+    stream_frames = (args.stream_frames if args.stream_frames >= 0 else (100000 if default_line else 0)) if args.full else 0
     if stream_frames > 0 and args.workload == "image" and args.precision == "fp32":
         fence()
         t1 = time.perf_counter()
@@ -334,23 +351,23 @@ def main():
             if not rel < 1e-4:
                 raise SystemExit(f"stream parity check failed: scores differ from the CPU oracle by {rel:.3e} on frames {picks}")
     # configs[2] beside it (1 GPU: the driver's N = 1 line then carries every single-GPU configuration)
-    if rank == 0 and world == 1 and default_line and not args.no_video:
+    if args.full and rank == 0 and world == 1 and default_line and not args.no_video:
         out["video"] = video_config2(vad, hip, lib, dev, hw, args.steps, args.warmup, not args.no_cpu_baseline)
     # The reference's own call sizes (main.py:274 one image, evaluate.py:240 16 images, evaluate_video.py:416 4 clips x 16 frames,
     # :344 one 16-frame window), eager launches, per-layer events off.  Never part of `value`.
-    if rank == 0 and world == 1 and default_line and not args.no_small:
+    if args.full and rank == 0 and world == 1 and default_line and not args.no_small:
         out["reference_call_sizes"] = reference_call_sizes(vad, lib, model, dev, hw, seed)
         if "winograd_precision" in out:       # the same calls in the opt-in Winograd mode (never part of `value`)
             out["winograd_precision"]["reference_call_sizes"] = reference_call_sizes(vad, lib, model, dev, hw, seed, precision="winograd")
     # Secondary measurement (row f-1): the native training step of the ConvLSTM video autoencoder (train_video.py:44-65),
     # exact fp32, 32 clips x 10 frames at the bench resolution.  Never part of `value` / `roofline`.
-    if rank == 0 and world == 1 and not args.no_train and args.workload == "image" and args.precision == "fp32":
+    if args.full and rank == 0 and world == 1 and not args.no_train and args.workload == "image" and args.precision == "fp32":
         out["training_step"] = training_step(vad, dev, hw)
     if args.workload == "dense":
         out["unique_frames_per_sec"] = round(((per_gpu - 1) * args.stride + t) * world * args.steps / elapsed, 1)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload != "dense":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload != "dense":
         out["cpu_baseline"] = cpu_baseline(vad, state, args.workload, args.clip_len, scores, seed, hw)
-    if world > 1:
+    if args.full and world > 1:
         out["multi_gpu"] = multi_gpu_evidence(vad, dist, args, state, scores, seed, hw, per_gpu, width, rank, world, dev, local_rank)
     if rank == 0:
         print(json.dumps(out))

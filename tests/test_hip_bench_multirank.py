@@ -32,7 +32,7 @@ def _free_port():
 def test_multi_rank_bench_line_verifies_itself(world, workload, extra):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), str(REPO / "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1",
-           "--backend", "gloo", "--share-gpu", "--workload", workload, "--no-train", *extra]
+           "--backend", "gloo", "--share-gpu", "--workload", workload, "--full", "--no-train", *extra]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -60,10 +60,10 @@ def test_multi_rank_bench_line_verifies_itself(world, workload, extra):
 
 
 def test_default_bench_line_carries_every_single_gpu_object():
-    """`python bench.py --gpus 1 --steps K --warmup W` as the driver runs it: ONE JSON line with the contract's fields, the
+    """`python bench.py --gpus 1 --steps K --warmup W --full`: ONE JSON line with the contract's fields, the
     roofline and cpu_baseline objects of configs[1], and - as secondary objects that never enter `value` - configs[2] with its
     own roofline / cpu_baseline, the configs[3] stream on one rank, the training step and the reference's own call sizes."""
-    cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1"]
+    cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full"]
     out = subprocess.run(cmd, cwd=REPO, env=dict(os.environ), capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -98,7 +98,7 @@ def test_bench_line_with_an_opt_in_mode_as_the_timed_path_says_so(workload, extr
     """`bench.py --precision winograd`: the opt-in arithmetic as the timed path must be visible in the line itself - `dtype` names
     it, no secondary-mode objects ride along, and the CPU baseline's parity figure is that of the mode (still inside 1e-5)."""
     cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--precision", "winograd",
-           "--workload", workload, "--no-train", "--no-small", *extra]
+           "--workload", workload, "--full", "--no-train", "--no-small", *extra]
     out = subprocess.run(cmd, cwd=REPO, env=dict(os.environ), capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -108,3 +108,49 @@ def test_bench_line_with_an_opt_in_mode_as_the_timed_path_says_so(workload, extr
     assert 0 < d["roofline"]["frac"] < 1 and "executed" in d["roofline"]["flops"]       # executed matrix FLOPs, not algorithmic ones
     assert "split_precision" not in d and "winograd_precision" not in d
     assert d["cpu_baseline"]["gpu_vs_cpu_max_rel_score_err"] < 1e-5
+
+
+# A plain line (no --full): the headline steps only.  `--dump-outputs` must hand back what the timed path returned in its last
+# step, on inputs fixed by the arguments alone: the dumped scores are checked against the CPU oracle on a few items of the same
+# seeded frames and weights bench.py builds (image: state seed 7, frame seed 0xC0FFEE + 1; video: state seed 8, seed 0xC0FFEE + 2).
+@pytest.mark.parametrize("workload,extra,shape", [("image", [], (512,)),
+                                                  ("video", ["--batch", "3", "--clip-len", "4", "--size", "64"], (3, 4))])
+def test_plain_bench_line_is_lean_and_dumps_the_timed_scores(vad, tmp_path, workload, extra, shape):
+    import numpy as np
+    import torch
+    from conftest import synthetic_state_for
+    from oracle import torch_oracle
+    cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", workload,
+           "--dump-outputs", str(tmp_path / "out"), *extra]
+    out = subprocess.run(cmd, cwd=REPO, env=dict(os.environ), capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f32" and d["higher_is_better"] is True
+    fps = d["config"]["frames_per_gpu_per_step"] / (d["ms_per_step"] * 1e-3)
+    assert abs(d["value"] - fps) <= 0.01 * fps
+    for k in ("layers", "cpu_baseline", "split_precision", "winograd_precision", "stream", "video", "training_step",
+              "reference_call_sizes", "multi_gpu"):
+        assert k not in d, k
+    assert d["roofline"] is None
+    got = np.load(tmp_path / "out" / "scores.npy")
+    assert got.dtype == np.float32 and got.shape == shape and np.all(np.isfinite(got))
+    hw = 64 if "--size" in extra else 256
+    items = [0, shape[0] // 2, shape[0] - 1]
+    if workload == "image":
+        m = vad.ConvAutoencoder(in_channels=3, latent_dim=256)
+        st = {k: torch.from_numpy(np.asarray(v)) for k, v in synthetic_state_for(vad, m, 7).items()}
+        xs = torch.from_numpy(np.concatenate([vad.synth.frames(0xC0FFEE + 1, i, 1, 3, hw, hw) for i in items]))
+        with torch.no_grad():
+            ref = torch_oracle.img_scores(st, xs)["scores"].numpy()
+    else:
+        m = vad.VideoAutoencoder(in_channels=3, latent_dim=128, lstm_hidden_dim=128, lstm_num_layers=2)
+        st = {k: torch.from_numpy(np.asarray(v)) for k, v in synthetic_state_for(vad, m, 8).items()}
+        xs = torch.from_numpy(np.concatenate([vad.synth.clips(0xC0FFEE + 2, i, 1, shape[1], 3, hw, hw) for i in items]))
+        with torch.no_grad():
+            ref = torch_oracle.vid_scores(st, xs, 128, 2)["frame"].numpy()
+    rel = float(np.max(np.abs(got[items] - ref) / np.abs(ref)))
+    assert rel < 1e-5, rel

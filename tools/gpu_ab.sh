@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out; T=${1:-ab}
 python -m pytest tests/test_hip_layers.py tests/test_hip_models.py tests/test_hip_fuzz.py -m gpu -x -q > $O/${T}_tests.log 2>&1 || { tail -40 $O/${T}_tests.log; exit 1; }
 tail -2 $O/${T}_tests.log
-for i in 1 2; do python bench.py --no-split --no-train --no-cpu-baseline > $O/${T}_bench_image_$i.json 2> $O/${T}_bi.err || { tail $O/${T}_bi.err; exit 1; }; done
+for i in 1 2; do python bench.py --full --no-split --no-train --no-cpu-baseline > $O/${T}_bench_image_$i.json 2> $O/${T}_bi.err || { tail $O/${T}_bi.err; exit 1; }; done
 python - <<PY
 import json
 for i in (1,2):

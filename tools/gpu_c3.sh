@@ -6,7 +6,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out; T=${1:-c3}
 timeout -k 10 900 python -m pytest tests/test_hip_layers.py tests/test_hip_models.py tests/test_hip_fuzz.py tests/test_hip_train_ops.py tests/test_hip_train_bf16.py tests/test_hip_train_step.py -m gpu -x -q > $O/${T}_tests.log 2>&1 || { tail -40 $O/${T}_tests.log; exit 1; }
 tail -2 $O/${T}_tests.log
-timeout -k 10 600 python bench.py --no-cpu-baseline --no-small --stream-frames 0 > $O/${T}_bench.json 2> $O/${T}_bench.err || { tail -20 $O/${T}_bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full --no-cpu-baseline --no-small --stream-frames 0 > $O/${T}_bench.json 2> $O/${T}_bench.err || { tail -20 $O/${T}_bench.err; exit 1; }
 python - <<PY
 import json
 d = json.load(open("$O/${T}_bench.json"))

@@ -8,7 +8,7 @@ R=$GRAFT_REPO_ROOT
 O=gpurun_out; T=${1:-r04final}
 timeout -k 10 1100 python -m pytest tests -m gpu -q > $O/${T}_tests.log 2>&1 || { tail -40 $O/${T}_tests.log; exit 1; }
 tail -2 $O/${T}_tests.log
-timeout -k 10 600 python bench.py > $O/${T}_bench_default.json 2> $O/${T}_bench_default.err || { tail -20 $O/${T}_bench_default.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/${T}_bench_default.json 2> $O/${T}_bench_default.err || { tail -20 $O/${T}_bench_default.err; exit 1; }
 python - <<PY
 import json
 d = json.load(open("$O/${T}_bench_default.json"))

@@ -7,7 +7,7 @@ O=gpurun_out; T=${1:-r04}; shift
 ARGS=${@:-tests}
 python -m pytest $ARGS -m gpu -x -q > $O/${T}_tests.log 2>&1 || { tail -60 $O/${T}_tests.log; exit 1; }
 tail -3 $O/${T}_tests.log
-python bench.py > $O/${T}_bench_default.json 2> $O/${T}_bench_default.err || { tail -20 $O/${T}_bench_default.err; exit 1; }
+python bench.py --full > $O/${T}_bench_default.json 2> $O/${T}_bench_default.err || { tail -20 $O/${T}_bench_default.err; exit 1; }
 python - <<PY
 import json
 d = json.load(open("$O/${T}_bench_default.json"))

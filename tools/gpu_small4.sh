@@ -3,10 +3,10 @@
 set -o pipefail
 cd $GRAFT_REPO_ROOT
 O=gpurun_out; T=${1:-small4}
-python bench.py --batch 16 --steps 300 --warmup 20 --no-split --no-train --no-cpu-baseline --no-video --no-small --stream-frames 0 > $O/${T}_img16.json 2>/dev/null
-python bench.py --batch 16 --steps 300 --warmup 20 --no-split --no-train --no-cpu-baseline --no-video --no-small --stream-frames 0 --no-layer-events > $O/${T}_img16_noev.json 2>/dev/null
-python bench.py --workload video --batch 1 --clip-len 16 --steps 300 --warmup 20 --no-split --no-train --no-cpu-baseline --no-small > $O/${T}_vid1.json 2>/dev/null
-python bench.py --workload video --batch 1 --clip-len 16 --steps 300 --warmup 20 --no-split --no-train --no-cpu-baseline --no-small --no-layer-events > $O/${T}_vid1_noev.json 2>/dev/null
+python bench.py --full --batch 16 --steps 300 --warmup 20 --no-split --no-train --no-cpu-baseline --no-video --no-small --stream-frames 0 > $O/${T}_img16.json 2>/dev/null
+python bench.py --full --batch 16 --steps 300 --warmup 20 --no-split --no-train --no-cpu-baseline --no-video --no-small --stream-frames 0 --no-layer-events > $O/${T}_img16_noev.json 2>/dev/null
+python bench.py --full --workload video --batch 1 --clip-len 16 --steps 300 --warmup 20 --no-split --no-train --no-cpu-baseline --no-small > $O/${T}_vid1.json 2>/dev/null
+python bench.py --full --workload video --batch 1 --clip-len 16 --steps 300 --warmup 20 --no-split --no-train --no-cpu-baseline --no-small --no-layer-events > $O/${T}_vid1_noev.json 2>/dev/null
 python - <<PY
 import json
 for n in ("img16", "vid1"):

@@ -4,7 +4,7 @@
 set -o pipefail
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; T=${1:-r03s}
 cd $R
-python bench.py --precision split --no-train --no-cpu-baseline --no-split > $O/${T}_bench_split.json 2> $O/${T}_bench_split.err || { tail -20 $O/${T}_bench_split.err; exit 1; }
+python bench.py --full --precision split --no-train --no-cpu-baseline --no-split > $O/${T}_bench_split.json 2> $O/${T}_bench_split.err || { tail -20 $O/${T}_bench_split.err; exit 1; }
 python - <<PY
 import json
 d = json.load(open("$O/${T}_bench_split.json"))

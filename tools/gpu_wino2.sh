@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out; T=${1:-wino2}
 timeout -k 10 600 python -m pytest tests/test_hip_layers.py tests/test_hip_models.py -m gpu -x -q -k "winograd or split_precision or blob or c_abi" > $O/${T}_tests.log 2>&1 || { tail -40 $O/${T}_tests.log; exit 1; }
 tail -2 $O/${T}_tests.log
-timeout -k 10 600 python bench.py --no-train --no-cpu-baseline --no-small --stream-frames 0 > $O/${T}_bench.json 2> $O/${T}_bench.err || { tail -20 $O/${T}_bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full --no-train --no-cpu-baseline --no-small --stream-frames 0 > $O/${T}_bench.json 2> $O/${T}_bench.err || { tail -20 $O/${T}_bench.err; exit 1; }
 python - <<PY
 import json
 d = json.load(open("$O/${T}_bench.json"))
