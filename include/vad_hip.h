@@ -529,6 +529,57 @@ int vad_vid_score_windows_c(const void* frames, int x_format, int precision, int
                             size_t workspace_bytes, int chunk_windows, float* seq_scores, float* frame_scores, float* errmap,
                             float* recon, void* stream);
 
+/* ------------------------------------------------------------------ recurrent state carried across calls
+ * ConvLSTM.forward(x, hidden_state) takes an initial state and returns the final one (models/video_autoencoder.py:127-166);
+ * a live stream is scored a frame (or a few) per call, for O(1) work per frame, by carrying that state.
+ *
+ * State blob (caller-owned device memory, 16-B aligned, fp32, the kernels' own layout):
+ *     for l in 0..layers-1:  h_l [B][GH][GW][hid_p]  then  c_l [B][GH][GW][hid_p]        (NHWC, dense)
+ * GH x GW is the ConvLSTM's grid (H/16 x W/16 of the video model), hid_p the hidden width zero-padded to a multiple of 64
+ * (the padded channels hold exact zeros and stay zero).  vad_vid_state_floats / vad_convlstm_state_floats give its size, 0 for
+ * unsupported shapes.  A blob is valid ONLY for the (B, H, W, hid, layers) it was sized for: row i belongs to stream i of a
+ * B-stream call, and a launch group [c0, c0+nc) of a chunked call reads and writes rows c0..c0+nc-1 of every plane.  Zero-filled
+ * memory is the zero state.  The library keeps no state of its own: two streams or threads share nothing.
+ *
+ * In-place rule: state_in == state_out is allowed.  Step 0 of every layer reads state_in; state_out is written once per
+ * launch group after all of that group's steps have run, so an aliased blob is updated only after its last reader.
+ * state_in == NULL is the zero state and takes exactly the launches of the stateless call; state_out == NULL discards. */
+size_t vad_vid_state_floats(int b, int h, int w, int hid, int layers);
+size_t vad_convlstm_state_floats(int b, int gh, int gw, int hid_p, int layers);
+/* vad_vid_score_c plus the state: x [B,T,in_ch,H,W] (or uint8 [B,T,H,W,3]) continues B streams by T frames each.  Every
+ * arithmetic mode, ingest format, in_ch, proj / layer count and chunking of vad_vid_score_c; T >= 1; the workspace is sized by
+ * vad_vid_workspace_bytes_c for THIS call's T.  Scoring a clip in one call or in pieces with the state carried gives the same
+ * bits.  vad_vid_score_c(...) is vad_vid_score_s(..., NULL, NULL, stream). */
+int vad_vid_score_s(const void* x, int x_format, int precision, int in_ch, long long b, int t, int h, int w, int latent, int hid,
+                    int layers, const float* packed_dev, void* workspace, size_t workspace_bytes, int chunk_clips,
+                    float* seq_scores, float* frame_scores, float* errmap, float* recon,
+                    const float* state_in, float* state_out, void* stream);
+/* Blob <-> the reference's tensors for one layer: h, c NCHW [B, hid, GH, GW] with the REAL width hid <= hid_p.  Import writes
+ * exact zeros into the padded channels, export drops them (csrc/state_io.hip: LDS-staged, both sides coalesced). */
+int vad_state_import(const float* h_nchw, const float* c_nchw, float* state, int layer, int b, int gh, int gw, int hid, int hid_p,
+                     int layers, void* stream);
+int vad_state_export(const float* state, float* h_nchw, float* c_nchw, int layer, int b, int gh, int gw, int hid, int hid_p,
+                     int layers, void* stream);
+/* The same converters on plain frame batches: NCHW [n, c, h, w] <-> NHWC [n, h, w, cpad], cpad >= c a multiple of 4. */
+int vad_nchw_to_nhwc_padded(const float* in, float* out, long long n, int h, int w, int c, int cpad, void* stream);
+int vad_nhwc_padded_to_nchw(const float* in, float* out, long long n, int h, int w, int c, int cpad, void* stream);
+
+/* Layer-level roll-out: ConvLSTM(input_dim, hidden_dims).forward(x, hidden_state) (models/video_autoencoder.py:94-179) - the
+ * ConvLSTM block of vad_vid_score_s as an entry point of its own (one launch sequence serves both).  The reference takes one
+ * hidden width per layer; every layer runs at ONE padded width hid_p (that of the widest, vad_convlstm_padded_dims), cin_p is
+ * the padded input width.  vad_convlstm_pack: params = (weight (4*hid_l, in_l + hid_l, 3, 3), bias) per cell, host pointers.
+ * x [B][T][GH][GW][cin_p] NHWC (padded channels zero).  hseq_out: the h sequence [B][T][GH][GW][hid_p] of the last layer, or
+ * with all_layers != 0 of every layer ([layers][B][T]...).  state_in / state_out: blobs of vad_convlstm_state_floats(b, gh, gw,
+ * hid_p, layers), NULL = zero state / discard, may alias.  precision: VAD_PREC_FP32; VAD_PREC_SPLIT / _WINO need cin_p == hid_p. */
+int vad_convlstm_padded_dims(int cin, const int* hids, int layers, int* cin_p, int* hid_p);
+size_t vad_convlstm_packed_floats(int cin_p, int hid_p, int layers);
+int vad_convlstm_pack(const float* const* params, int nparams, int cin, const int* hids, int layers, int precision,
+                      float* packed_host);
+size_t vad_convlstm_seq_workspace_bytes(int b, int t, int gh, int gw, int cin_p, int hid_p, int layers, int all_layers);
+int vad_convlstm_seq(const float* x, int precision, long long b, int t, int gh, int gw, int cin_p, int hid_p, int layers,
+                     const float* packed_dev, void* workspace, size_t workspace_bytes, float* hseq_out, int all_layers,
+                     const float* state_in, float* state_out, void* stream);
+
 /* ------------------------------------------------------------------ hipGraph capture / replay of a scoring call
  * vad_graph_begin(stream); <one vad_img_score* / vad_vid_score* call on `stream`>; vad_graph_end(stream, &exec) captures
  * the call's launch sequence (kernels, and the fork / join with the library's helper streams) into an instantiated

@@ -4,3 +4,4 @@ import importlib
 _impl = importlib.import_module("video-anomaly-detection_amd.video_autoencoder")
 ConvLSTMCell, ConvLSTM = _impl.ConvLSTMCell, _impl.ConvLSTM
 VideoEncoder, VideoDecoder, VideoAutoencoder = _impl.VideoEncoder, _impl.VideoDecoder, _impl.VideoAutoencoder
+VideoState = _impl.VideoState

@@ -7,7 +7,7 @@ packages at the repository root, which re-export the reference's import surface.
 from . import hip, synth                                              # noqa: F401
 from .autoencoder import Autoencoder, ConvAutoencoder, Decoder, Encoder   # noqa: F401
 from .video_autoencoder import (ConvLSTM, ConvLSTMCell, VideoAutoencoder,    # noqa: F401
-                                VideoDecoder, VideoEncoder)
+                                VideoDecoder, VideoEncoder, VideoState)
 from . import losses                                                   # noqa: F401
 from .losses import CombinedLoss, SSIMLoss                           # noqa: F401
 from . import training                                                 # noqa: F401

@@ -366,6 +366,19 @@ extern "C" int vad_img_pack(const float* const* P, int nparams, int in_ch, int l
     return rc;
 }
 
+// One ConvLSTM cell, weight (4*hr, xr + hr, 3, 3): the gate blocks i,f,g,o and the x / h input halves are zero-padded
+// separately to (4*hp, xp + hp).  Shared by the model blob (vad_vid_pack_c) and the layer-level set (vad_convlstm_pack).
+static int pack_lstm_cell(const float* w, const float* b, int xr, int xp, int hr, int hp, int precision, float* wo, float* bo) {
+    // VAD_PREC_WINO: the gate convolution in Winograd form when both sources have one width (vad_convlstm_step_wino's
+    // requirement; the launch sequence makes the same test), else the direct form
+    const int lprec = (precision == VAD_PREC_WINO && xp == hp) ? VAD_PREC_WINO : base_prec(precision);
+    if (xr == xp && hr == hp) return pack_conv3x3_any(w, b, nullptr, 4 * hp, xp + hp, lprec, wo, bo);
+    PaddedLayer Q;
+    pad_layer(w, b, nullptr, 4 * hr, xr + hr, 9, false, 4 * hp, xp + hp,
+              [=](int co) { return (co / hr) * hp + co % hr; }, [=](int ci) { return ci < xr ? ci : xp + (ci - xr); }, Q);
+    return pack_conv3x3_any(Q.w.data(), Q.bias.data(), nullptr, 4 * hp, xp + hp, lprec, wo, bo);
+}
+
 // --------------------------------------------------------------------------- video autoencoder
 VidLayout vid_layout(int in_ch, int latent_real, int hid_real, int layers) {
     VidLayout L{};
@@ -449,16 +462,9 @@ extern "C" int vad_vid_pack_c(const float* const* P, int nparams, int in_ch, int
             }
             for (int i = 0; i < 4; ++i) bn[i] = P[pi + 2 + i];    // decoder.0 is the one whose cin is latent_dim
             rc = pack_convt2x2_slot(w, b, bn, li == first_convt ? latent : s.cin, s.cout, s, precision, out); pi += 6; break;
-        case LK_LSTM: {   // weight (4*hid, x + hid, 3, 3): gate blocks i,f,g,o and the x / h input halves are padded separately
-            const int xr = (li == 4) ? latent : hid, xp = (li == 4) ? L.latent_p : L.hid_p, hp = L.hid_p;
-            // VAD_PREC_WINO: the gate convolution in Winograd form when both sources have one width (vad_convlstm_step_wino's
-            // requirement; vid_run makes the same test), else the direct form
-            const int lprec = (precision == VAD_PREC_WINO && xp == hp) ? VAD_PREC_WINO : base_prec(precision);
-            if (xr == xp && hid == hp) { rc = pack_conv3x3_any(w, b, nullptr, s.cout, s.cin, lprec, out + s.w, out + s.b); pi += 2; break; }
-            PaddedLayer Q;
-            pad_layer(w, b, nullptr, 4 * hid, xr + hid, 9, false, s.cout, s.cin,
-                      [=](int co) { return (co / hid) * hp + co % hid; }, [=](int ci) { return ci < xr ? ci : xp + (ci - xr); }, Q);
-            rc = pack_conv3x3_any(Q.w.data(), Q.bias.data(), nullptr, s.cout, s.cin, lprec, out + s.w, out + s.b); pi += 2; break; }
+        case LK_LSTM:     // weight (4*hid, x + hid, 3, 3)
+            rc = pack_lstm_cell(w, b, (li == 4) ? latent : hid, (li == 4) ? L.latent_p : L.hid_p, hid, L.hid_p, precision, out + s.w, out + s.b);
+            pi += 2; break;
         case LK_PROJ: {
             if (latent == s.cout && hid == s.cin) { rc = vad_pack_conv1x1(w, b, s.cout, s.cin, out + s.w, out + s.b); pi += 2; break; }
             PaddedLayer Q;
@@ -472,5 +478,44 @@ extern "C" int vad_vid_pack_c(const float* const* P, int nparams, int in_ch, int
         }
     }
     if (rc == VAD_OK && pi != nparams) return vad_fail(VAD_ERR_ARG, "vid_pack: consumed %d of %d parameters", pi, nparams);
+    return rc;
+}
+
+// --------------------------------------------------------------------------- stand-alone ConvLSTM (vad_convlstm_seq)
+// ConvLSTM(input_dim, hidden_dims) takes one hidden width PER layer (models/video_autoencoder.py:108-125); the roll-out runs every
+// layer at ONE padded width, that of the widest layer (a padded channel carries exactly 0 through the cell, vad_layout.h).
+extern "C" int vad_convlstm_padded_dims(int cin, const int* hids, int layers, int* cin_p, int* hid_p) {
+    REQ(hids && cin_p && hid_p, "convlstm_padded_dims: null pointer");
+    REQ(layers >= 1 && layers <= 8, "convlstm: num_layers=%d out of range [1,8]", layers);
+    REQ(cin > 0 && cin <= VAD_MAX_WIDTH, "convlstm: input_dim=%d out of range [1,%d]", cin, VAD_MAX_WIDTH);
+    int hmax = 0;
+    for (int l = 0; l < layers; ++l) {
+        REQ(hids[l] > 0 && hids[l] <= VAD_MAX_WIDTH, "convlstm: hidden_dims[%d]=%d out of range [1,%d]", l, hids[l], VAD_MAX_WIDTH);
+        if (hids[l] > hmax) hmax = hids[l];
+    }
+    *hid_p = vad_pad_up(hmax, 64);
+    *cin_p = vad_pad_up(cin, 64) == *hid_p ? *hid_p : vad_pad_up(cin, 32);       // one width for both sources where the padding allows it
+    return VAD_OK;
+}
+
+extern "C" size_t vad_convlstm_packed_floats(int cin_p, int hid_p, int layers) {
+    if (cin_p <= 0 || cin_p % 32 || hid_p <= 0 || hid_p % 64 || layers < 1 || layers > 8) return 0;
+    return vad_seq_slot(cin_p, hid_p, layers).w;
+}
+
+extern "C" int vad_convlstm_pack(const float* const* P, int nparams, int cin, const int* hids, int layers, int precision, float* out) {
+    REQ(P && out && hids, "convlstm_pack: null pointer");
+    REQ_PREC("convlstm_pack");
+    int cin_p = 0, hid_p = 0;
+    int rc = vad_convlstm_padded_dims(cin, hids, layers, &cin_p, &hid_p);
+    if (rc != VAD_OK) return rc;
+    REQ(nparams == 2 * layers, "convlstm_pack: expected %d parameter tensors (weight, bias per cell), got %d", 2 * layers, nparams);
+    for (int i = 0; i < nparams; ++i) REQ(P[i], "convlstm_pack: parameter %d is NULL", i);
+    memset(out, 0, vad_convlstm_packed_floats(cin_p, hid_p, layers) * sizeof(float));
+    for (int l = 0; l < layers && rc == VAD_OK; ++l) {
+        const VadSeqSlot s = vad_seq_slot(cin_p, hid_p, l);
+        // the x half of a layer above 0 is the layer below's h: its real width may differ from this layer's
+        rc = pack_lstm_cell(P[2 * l], P[2 * l + 1], l ? hids[l - 1] : cin, l ? hid_p : cin_p, hids[l], hid_p, precision, out + s.w, out + s.b);
+    }
     return rc;
 }

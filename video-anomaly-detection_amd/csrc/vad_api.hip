@@ -366,65 +366,32 @@ static std::atomic<int> g_vad_lstm_wavefront{1};   // debug: 0 = always the sequ
 extern "C" int vad_debug_set_lstm_wavefront(int on) { g_vad_lstm_wavefront = on; return VAD_OK; }
 extern "C" int vad_lstm_wavefront_mode(void) { return g_vad_lstm_wavefront.load(std::memory_order_relaxed); }   // the training step shares the switch
 
-// clips [c0, c0+nc) of a stream whose clip c starts at source frame c*cs; x points at source frame 0 of the stream
-int vid_run(const void* xv, int x_format, int precision, int in_ch, long long nclips, int t, int cs, int h, int w, int latent_real, int hid_real, int layers,
-            const float* packed, void* ws, size_t ws_bytes, int chunk, float* seq_scores, float* frame_scores,
-            float* errmap, float* recon, hipStream_t s, const char* who) {
-    VAD_REQUIRE(x_format == VAD_X_F32_NCHW || x_format == VAD_X_U8_NHWC, "%s: unknown input format %d", who, x_format);
-    VAD_REQUIRE(precision == VAD_PREC_FP32 || precision == VAD_PREC_SPLIT || precision == VAD_PREC_WINO, "%s: precision=%d must be VAD_PREC_FP32 (0), VAD_PREC_SPLIT (1) or VAD_PREC_WINO (4)", who, precision);
-    const int mprec = precision;                                                  // the blob's mode (device-side tag check)
-    const bool wino = precision == VAD_PREC_WINO;
-    if (wino) precision = VAD_PREC_FP32;                                          // everything but the encoder's 3x3 convolutions
-    const size_t xelem = x_format == VAD_X_U8_NHWC ? 1 : 4;
-    const char* x = (const char*)xv;
-    VAD_REQUIRE(in_ch >= 3 && in_ch <= VAD_MAX_IN_CH, "%s: in_channels=%d out of range [3,%d]", who, in_ch, VAD_MAX_IN_CH);
-    VAD_REQUIRE(in_ch == 3 || x_format == VAD_X_F32_NCHW, "%s: uint8 frames are 3-channel images (in_channels=%d)", who, in_ch);
-    const VidWs Z = vid_ws(chunk, t, cs, h, w, latent_real, hid_real, layers, in_ch);
-    if (ws_bytes < Z.total) return vad_fail(VAD_ERR_WS, "%s: workspace %zu B < required %zu B", who, ws_bytes, Z.total);
-    VAD_REQUIRE(((uintptr_t)ws & 255) == 0 && ((uintptr_t)packed & 15) == 0, "%s: workspace must be 256-B and weights 16-B aligned", who);
-    const VidLayout L = vid_layout(in_ch, latent_real, hid_real, layers);
-    const int latent = L.latent_p, hid = L.hid_p;   // the widths the kernels see (zero-padded, vad_layout.h)
-    const int wide = L.wide;                        // in_channels > 3: generic first / last layers over planes padded to `wide` channels
-    char* base = (char*)ws;
-    float* A = (float*)base; base += Z.act;
-    float* Bf = (float*)base; base += Z.act;
-    float* E = (float*)base; base += Z.enc;
-    float* HS[8];
-    float* CS[8];
-    for (int l = 0; l < layers; ++l) { HS[l] = (float*)base; base += Z.hseq; }
-    for (int l = 0; l < layers; ++l) { CS[l] = (float*)base; base += Z.cst; }
-    float* P = nullptr;
-    if (L.has_proj) { P = (float*)base; base += Z.proj; }
-    float* parts = (float*)base; base += Z.parts;
-    float* ZX[8] = {};
-    if (Z.zx0) {
-        ZX[0] = (float*)base; base += Z.zx0;
-        for (int l = 1; l < layers; ++l) { ZX[l] = (float*)base; base += Z.zxl; }
-    }
-    float* ZW[8];                                   // per layer: the layers of a small launch group run concurrently (wavefront)
-    for (int l = 0; l < layers; ++l) { ZW[l] = (float*)base; base += Z.zw; }
-    const int nparts = wide ? vad_wide_score_partials(h, w) : vad_score_partials(1, h, w);
-    const int h16 = h / 16, w16 = w / 16;
-    const long long fs_lat = (long long)h16 * w16 * latent, fs_hid = (long long)h16 * w16 * hid;
-#define W_(i) (packed + L.layer[i].w)
-#define B_(i) (packed + L.layer[i].b)
+// One ConvLSTM roll-out: `layers` stacked cells over t steps for nc clips.  Shared by the video model (vid_run) and the
+// layer-level entry point (vad_convlstm_seq).  h0 / c0 (per layer, or all NULL): the initial state, [nc][h16][w16][hid] dense -
+// step 0 of layer l then reads h_prev from h0[l] with clip stride fs_hid and c_prev from c0[l]; every step writes CS[l].
+struct LstmRun {
+    const float* x;            // layer 0's input, [..][h16][w16][cin]; clip c, step ti at x + c*clip_x + ti*fs_x
+    long long fs_x, clip_x;
+    int nf_x, cs;              // distinct source frames behind x (hoisted x halves of layer 0) and the clip stride in frames
+    const float* W[8]; const float* B[8];
+    float* HS[8]; float* CS[8]; float* ZX[8]; float* ZW[8];
+    const float* h0[8]; const float* c0[8];
+    int nc, t, h16, w16, cin, hid, layers;
+    int precision;             // VAD_PREC_FP32 / VAD_PREC_SPLIT: the arithmetic of the direct steps
+    bool wino;                 // the blob holds Winograd-form gate weights where both sources have one width
+};
 
-    for (long long c0 = 0; c0 < nclips; c0 += chunk) {
-        const int nc = (int)((nclips - c0 < chunk) ? (nclips - c0) : chunk);
-        const int n = nc * t;                       // (clip, t) frames that are decoded and scored
-        const int nf = (nc - 1) * cs + t;           // distinct source frames that are encoded
-        const char* xin = x + (size_t)c0 * cs * in_ch * h * w * xelem;
-        // VideoEncoder: 4 x conv-BN-LeakyReLU-MaxPool on the flattened frames
-        // (models/video_autoencoder.py:191-215, :222-228)
-        if (wide) {
-            VadProfScope ps(0, s);
-            TRY(vad_nchw_to_nhwc_pad((const float*)xin, Bf, nf, h, w, in_ch, wide, s));
-            TRY(conv3x3_mode(Bf, W_(0), B_(0), A, nf, h, w, wide, 32, VAD_ACT_LEAKY, 1, mprec, s));
-        } else { VadProfScope ps(0, s); TRY(vad_conv3x3_c3_fmt(xin, x_format, W_(0), B_(0), A, nf, h, w, 32, VAD_ACT_LEAKY, 1, s)); }
-        { VadProfScope ps(1, s); TRY(conv3x3_mode(A, W_(1), B_(1), Bf, nf, h / 2, w / 2, 32, 64, VAD_ACT_LEAKY, 1, mprec, s)); }
-        { VadProfScope ps(2, s); TRY(conv3x3_mode(Bf, W_(2), B_(2), A, nf, h / 4, w / 4, 64, 128, VAD_ACT_LEAKY, 1, mprec, s)); }
-        { VadProfScope ps(3, s); TRY(conv3x3_mode(A, W_(3), B_(3), E, nf, h / 8, w / 8, 128, latent, VAD_ACT_LEAKY, 1, mprec, s)); }
-        // ConvLSTM, zero initial state (models/video_autoencoder.py:144-166).  Step (l, t) needs (l, t-1) and (l-1, t) only.
+int lstm_rollout(const LstmRun& R, hipStream_t s) {
+    const float* E = R.x;
+    float* const* HS = R.HS; float* const* CS = R.CS; float* const* ZX = R.ZX; float* const* ZW = R.ZW;
+    const int nc = R.nc, t = R.t, cs = R.cs, nf = R.nf_x, h16 = R.h16, w16 = R.w16, latent = R.cin, hid = R.hid, layers = R.layers;
+    const int precision = R.precision;
+    const bool wino = R.wino;
+    const long long fs_lat = R.fs_x, fs_hid = (long long)h16 * w16 * hid;
+#define W_(i) (R.W[(i) - 4])
+#define B_(i) (R.B[(i) - 4])
+    {
+        // Step (l, t) needs (l, t-1) and (l-1, t) only.
         const long long fs_zx = (long long)h16 * w16 * 4 * hid;
         // x halves ahead of the recurrence (small launch groups, exact fp32): a step's accumulator chain runs over the x chunks
         // first and the h chunks second, so bias + x half can be computed for ALL steps of layer 0 in one batched convolution
@@ -440,16 +407,20 @@ int vid_run(const void* xv, int x_format, int precision, int in_ch, long long nc
         auto lstm_step = [&](int l, int ti, hipStream_t st) -> int {
             const float* xin_l = (l == 0) ? E : HS[l - 1];
             const long long fs_in = (l == 0) ? fs_lat : fs_hid;
-            const long long clip_in = (l == 0) ? (long long)cs * fs_lat : (long long)t * fs_hid;   // layer 0 reads the shared features
+            const long long clip_in = (l == 0) ? R.clip_x : (long long)t * fs_hid;   // layer 0 reads the shared features
+            // h(t-1), c(t-1): the previous step's, or at step 0 the caller's initial state (NULL = zero)
+            const float* hp = ti ? HS[l] + (size_t)(ti - 1) * fs_hid : R.h0[l];
+            const long long hp_fs = ti ? (long long)t * fs_hid : fs_hid;
+            const float* cp = ti ? CS[l] : R.c0[l];
             const long long clip_zx = (l == 0) ? (long long)cs * fs_zx : (long long)t * fs_zx;
             VadProfScope ps(4, st);
             if (wino_layer(l))
-                return vad_convlstm_step_wino(xin_l + (size_t)ti * fs_in, clip_in, ti ? HS[l] + (size_t)(ti - 1) * fs_hid : nullptr, (long long)t * fs_hid,
-                                              ti ? CS[l] : nullptr, W_(4 + l), B_(4 + l), HS[l] + (size_t)ti * fs_hid, (long long)t * fs_hid, CS[l], ZW[l],
+                return vad_convlstm_step_wino(xin_l + (size_t)ti * fs_in, clip_in, hp, hp_fs,
+                                              cp, W_(4 + l), B_(4 + l), HS[l] + (size_t)ti * fs_hid, (long long)t * fs_hid, CS[l], ZW[l],
                                               nc, h16, w16, hid, hid, st);
             return vad_convlstm_step_zx(xin_l + (size_t)ti * fs_in, clip_in, (hoist && (l == 0 || hoist_upper)) ? ZX[l] + (size_t)ti * fs_zx : nullptr, clip_zx,
-                                        ti ? HS[l] + (size_t)(ti - 1) * fs_hid : nullptr, (long long)t * fs_hid,
-                                        ti ? CS[l] : nullptr, W_(4 + l), B_(4 + l),
+                                        hp, hp_fs,
+                                        cp, W_(4 + l), B_(4 + l),
                                         HS[l] + (size_t)ti * fs_hid, (long long)t * fs_hid, CS[l],
                                         nc, h16, w16, (l == 0) ? latent : hid, hid, precision, st);
         };
@@ -504,6 +475,92 @@ int vid_run(const void* xv, int x_format, int precision, int in_ch, long long nc
                                           VAD_PREC_FP32, nullptr, nullptr, s));
                 }
                 for (int ti = 0; ti < t; ++ti) TRY(lstm_step(l, ti, s));
+            }
+        }
+    }
+#undef W_
+#undef B_
+    return VAD_OK;
+}
+
+// clips [c0, c0+nc) of a stream whose clip c starts at source frame c*cs; x points at source frame 0 of the stream
+int vid_run(const void* xv, int x_format, int precision, int in_ch, long long nclips, int t, int cs, int h, int w, int latent_real, int hid_real, int layers,
+            const float* packed, void* ws, size_t ws_bytes, int chunk, float* seq_scores, float* frame_scores,
+            float* errmap, float* recon, const float* state_in, float* state_out, hipStream_t s, const char* who) {
+    VAD_REQUIRE(x_format == VAD_X_F32_NCHW || x_format == VAD_X_U8_NHWC, "%s: unknown input format %d", who, x_format);
+    VAD_REQUIRE(precision == VAD_PREC_FP32 || precision == VAD_PREC_SPLIT || precision == VAD_PREC_WINO, "%s: precision=%d must be VAD_PREC_FP32 (0), VAD_PREC_SPLIT (1) or VAD_PREC_WINO (4)", who, precision);
+    const int mprec = precision;                                                  // the blob's mode (device-side tag check)
+    const bool wino = precision == VAD_PREC_WINO;
+    if (wino) precision = VAD_PREC_FP32;                                          // everything but the encoder's 3x3 convolutions
+    const size_t xelem = x_format == VAD_X_U8_NHWC ? 1 : 4;
+    const char* x = (const char*)xv;
+    VAD_REQUIRE(in_ch >= 3 && in_ch <= VAD_MAX_IN_CH, "%s: in_channels=%d out of range [3,%d]", who, in_ch, VAD_MAX_IN_CH);
+    VAD_REQUIRE(in_ch == 3 || x_format == VAD_X_F32_NCHW, "%s: uint8 frames are 3-channel images (in_channels=%d)", who, in_ch);
+    const VidWs Z = vid_ws(chunk, t, cs, h, w, latent_real, hid_real, layers, in_ch);
+    if (ws_bytes < Z.total) return vad_fail(VAD_ERR_WS, "%s: workspace %zu B < required %zu B", who, ws_bytes, Z.total);
+    VAD_REQUIRE(((uintptr_t)ws & 255) == 0 && ((uintptr_t)packed & 15) == 0, "%s: workspace must be 256-B and weights 16-B aligned", who);
+    const VidLayout L = vid_layout(in_ch, latent_real, hid_real, layers);
+    const int latent = L.latent_p, hid = L.hid_p;   // the widths the kernels see (zero-padded, vad_layout.h)
+    const int wide = L.wide;                        // in_channels > 3: generic first / last layers over planes padded to `wide` channels
+    char* base = (char*)ws;
+    float* A = (float*)base; base += Z.act;
+    float* Bf = (float*)base; base += Z.act;
+    float* E = (float*)base; base += Z.enc;
+    float* HS[8];
+    float* CS[8];
+    for (int l = 0; l < layers; ++l) { HS[l] = (float*)base; base += Z.hseq; }
+    for (int l = 0; l < layers; ++l) { CS[l] = (float*)base; base += Z.cst; }
+    float* P = nullptr;
+    if (L.has_proj) { P = (float*)base; base += Z.proj; }
+    float* parts = (float*)base; base += Z.parts;
+    float* ZX[8] = {};
+    if (Z.zx0) {
+        ZX[0] = (float*)base; base += Z.zx0;
+        for (int l = 1; l < layers; ++l) { ZX[l] = (float*)base; base += Z.zxl; }
+    }
+    float* ZW[8];                                   // per layer: the layers of a small launch group run concurrently (wavefront)
+    for (int l = 0; l < layers; ++l) { ZW[l] = (float*)base; base += Z.zw; }
+    const int nparts = wide ? vad_wide_score_partials(h, w) : vad_score_partials(1, h, w);
+    const int h16 = h / 16, w16 = w / 16;
+    const long long fs_lat = (long long)h16 * w16 * latent, fs_hid = (long long)h16 * w16 * hid;
+#define W_(i) (packed + L.layer[i].w)
+#define B_(i) (packed + L.layer[i].b)
+
+    for (long long c0 = 0; c0 < nclips; c0 += chunk) {
+        const int nc = (int)((nclips - c0 < chunk) ? (nclips - c0) : chunk);
+        const int n = nc * t;                       // (clip, t) frames that are decoded and scored
+        const int nf = (nc - 1) * cs + t;           // distinct source frames that are encoded
+        const char* xin = x + (size_t)c0 * cs * in_ch * h * w * xelem;
+        // VideoEncoder: 4 x conv-BN-LeakyReLU-MaxPool on the flattened frames
+        // (models/video_autoencoder.py:191-215, :222-228)
+        if (wide) {
+            VadProfScope ps(0, s);
+            TRY(vad_nchw_to_nhwc_pad((const float*)xin, Bf, nf, h, w, in_ch, wide, s));
+            TRY(conv3x3_mode(Bf, W_(0), B_(0), A, nf, h, w, wide, 32, VAD_ACT_LEAKY, 1, mprec, s));
+        } else { VadProfScope ps(0, s); TRY(vad_conv3x3_c3_fmt(xin, x_format, W_(0), B_(0), A, nf, h, w, 32, VAD_ACT_LEAKY, 1, s)); }
+        { VadProfScope ps(1, s); TRY(conv3x3_mode(A, W_(1), B_(1), Bf, nf, h / 2, w / 2, 32, 64, VAD_ACT_LEAKY, 1, mprec, s)); }
+        { VadProfScope ps(2, s); TRY(conv3x3_mode(Bf, W_(2), B_(2), A, nf, h / 4, w / 4, 64, 128, VAD_ACT_LEAKY, 1, mprec, s)); }
+        { VadProfScope ps(3, s); TRY(conv3x3_mode(A, W_(3), B_(3), E, nf, h / 8, w / 8, 128, latent, VAD_ACT_LEAKY, 1, mprec, s)); }
+        // ConvLSTM (models/video_autoencoder.py:144-166): zero initial state, or rows [c0, c0+nc) of the caller's state blob
+        {
+            LstmRun R{};
+            R.x = E; R.fs_x = fs_lat; R.clip_x = (long long)cs * fs_lat; R.nf_x = nf; R.cs = cs;
+            for (int l = 0; l < layers; ++l) {
+                R.W[l] = W_(4 + l); R.B[l] = B_(4 + l); R.HS[l] = HS[l]; R.CS[l] = CS[l]; R.ZX[l] = ZX[l]; R.ZW[l] = ZW[l];
+                if (state_in) {
+                    R.h0[l] = state_in + ((size_t)2 * l * nclips + (size_t)c0) * fs_hid;
+                    R.c0[l] = R.h0[l] + (size_t)nclips * fs_hid;
+                }
+            }
+            R.nc = nc; R.t = t; R.h16 = h16; R.w16 = w16; R.cin = latent; R.hid = hid; R.layers = layers;
+            R.precision = precision; R.wino = wino;
+            TRY(lstm_rollout(R, s));
+            // the final (h, c) of every layer into rows [c0, c0+nc) of state_out: after every step of this launch group has
+            // read its inputs (the join above), so state_out may be state_in
+            if (state_out) {
+                VadProfScope ps(4, s);
+                TRY(vad_state_store(HS[0], (long long)(Z.hseq / sizeof(float)), CS[0], (long long)(Z.cst / sizeof(float)), state_out, nclips, c0, nc, t,
+                                    fs_hid, layers, s));
             }
         }
         const float* dec_in = HS[layers - 1];
@@ -566,14 +623,102 @@ extern "C" int vad_vid_score_x(const void* x, int x_format, int precision, long 
 extern "C" int vad_vid_score_c(const void* x, int x_format, int precision, int in_ch, long long b, int t, int h, int w, int latent, int hid, int layers,
                                const float* packed, void* ws, size_t ws_bytes, int chunk,
                                float* seq_scores, float* frame_scores, float* errmap, float* recon, void* stream) {
+    return vad_vid_score_s(x, x_format, precision, in_ch, b, t, h, w, latent, hid, layers, packed, ws, ws_bytes, chunk, seq_scores, frame_scores, errmap,
+                           recon, nullptr, nullptr, stream);
+}
+
+// Stateful form: the ConvLSTM starts from state_in (NULL = zero) and leaves its final (h, c) in state_out (NULL = discard).
+extern "C" int vad_vid_score_s(const void* x, int x_format, int precision, int in_ch, long long b, int t, int h, int w, int latent, int hid, int layers,
+                               const float* packed, void* ws, size_t ws_bytes, int chunk,
+                               float* seq_scores, float* frame_scores, float* errmap, float* recon,
+                               const float* state_in, float* state_out, void* stream) {
     VAD_REQUIRE(x && packed && ws, "vid_score: null pointer");
     VAD_REQUIRE(b > 0 && t > 0 && chunk > 0, "vid_score: clips=%lld T=%d chunk=%d must be positive", b, t, chunk);
     VAD_REQUIRE(h > 0 && w > 0 && h % 16 == 0 && w % 16 == 0,
                 "vid_score: H=%d W=%d must be positive multiples of 16 (4 MaxPool2d(2) stages)", h, w);
     if (vad_vid_packed_floats(latent, hid, layers) == 0) return VAD_ERR_ARG;   // message already set
-    VAD_REQUIRE(seq_scores || frame_scores || errmap || recon, "vid_score: no output requested");
+    VAD_REQUIRE(seq_scores || frame_scores || errmap || recon || state_out, "vid_score: no output requested");
+    if (state_in || state_out) {
+        VAD_REQUIRE(b < (1ll << 31) && vad_vid_state_floats((int)b, h, w, hid, layers) != 0, "vid_score: no state blob exists for %lld streams of %dx%d", b, h, w);
+        VAD_REQUIRE(((uintptr_t)state_in & 15) == 0 && ((uintptr_t)state_out & 15) == 0, "vid_score: state blobs must be 16-B aligned");
+    }
     return vid_run(x, x_format, precision, in_ch, b, t, t, h, w, latent, hid, layers, packed, ws, ws_bytes, chunk, seq_scores, frame_scores, errmap,
-                   recon, (hipStream_t)stream, "vid_score");
+                   recon, state_in, state_out, (hipStream_t)stream, "vid_score");
+}
+
+// ------------------------------------------------------------------------------ layer-level ConvLSTM roll-out
+namespace {
+struct SeqWs { size_t hseq, cst, zx0, zxl, zw, total; };
+SeqWs seq_ws(int b, int t, int gh, int gw, int hid_p, int layers, int all_layers) {
+    SeqWs z{};
+    const size_t n = (size_t)b * t, p = (size_t)gh * gw;
+    z.hseq = up256(sizeof(float) * n * p * hid_p);
+    z.cst = up256(sizeof(float) * (size_t)b * p * hid_p);
+    const bool small = vid_lstm_groups(b, gh, gw, hid_p) < 256;       // as in vid_ws: x halves ahead of the recurrence
+    z.zx0 = small ? up256(sizeof(float) * n * p * 4 * hid_p) : 0;
+    z.zxl = z.zx0;
+    z.zw = up256(sizeof(float) * (size_t)b * p * 4 * hid_p);
+    z.total = (size_t)(all_layers ? 0 : layers - 1) * z.hseq + (size_t)layers * (z.cst + z.zw) + z.zx0 + (size_t)(layers - 1) * z.zxl;
+    return z;
+}
+int seq_dims_ok(const char* who, long long b, int t, int gh, int gw, int cin_p, int hid_p, int layers) {
+    VAD_REQUIRE(b > 0 && b < (1ll << 24) && t > 0 && gh > 0 && gw > 0, "%s: bad shape b=%lld T=%d grid=%dx%d", who, b, t, gh, gw);
+    VAD_REQUIRE(vad_convlstm_packed_floats(cin_p, hid_p, layers) != 0,
+                "%s: cin_p=%d must be a positive multiple of 32, hid_p=%d of 64, layers=%d in [1,8]", who, cin_p, hid_p, layers);
+    return VAD_OK;
+}
+}  // namespace
+
+extern "C" size_t vad_convlstm_seq_workspace_bytes(int b, int t, int gh, int gw, int cin_p, int hid_p, int layers, int all_layers) {
+    if (b <= 0 || t <= 0 || gh <= 0 || gw <= 0 || vad_convlstm_packed_floats(cin_p, hid_p, layers) == 0) return 0;
+    const size_t n = seq_ws(b, t, gh, gw, hid_p, layers, all_layers).total;
+    return n ? n : 256;
+}
+
+extern "C" int vad_convlstm_seq(const float* x, int precision, long long b, int t, int gh, int gw, int cin_p, int hid_p, int layers,
+                                const float* packed, void* ws, size_t ws_bytes, float* hseq_out, int all_layers,
+                                const float* state_in, float* state_out, void* stream) {
+    VAD_REQUIRE(x && packed && ws && hseq_out, "convlstm_seq: null pointer");
+    REQ_PREC("convlstm_seq");
+    TRY(seq_dims_ok("convlstm_seq", b, t, gh, gw, cin_p, hid_p, layers));
+    VAD_REQUIRE(precision == VAD_PREC_FP32 || cin_p == hid_p, "convlstm_seq: split / Winograd steps need cin_p == hid_p (got %d, %d)", cin_p, hid_p);
+    const SeqWs Z = seq_ws((int)b, t, gh, gw, hid_p, layers, all_layers);
+    if (ws_bytes < Z.total) return vad_fail(VAD_ERR_WS, "convlstm_seq: workspace %zu B < required %zu B", ws_bytes, Z.total);
+    VAD_REQUIRE(((uintptr_t)ws & 255) == 0 && ((uintptr_t)packed & 15) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)hseq_out & 15) == 0,
+                "convlstm_seq: workspace must be 256-B, weights / x / hseq_out 16-B aligned");
+    VAD_REQUIRE(((uintptr_t)state_in & 15) == 0 && ((uintptr_t)state_out & 15) == 0, "convlstm_seq: state blobs must be 16-B aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const long long fs_hid = (long long)gh * gw * hid_p, fs_x = (long long)gh * gw * cin_p;
+    const size_t seq_floats = (size_t)b * t * fs_hid;
+    LstmRun R{};
+    char* base = (char*)ws;
+    for (int l = 0; l < layers; ++l) {
+        if (all_layers) R.HS[l] = hseq_out + (size_t)l * seq_floats;
+        else if (l == layers - 1) R.HS[l] = hseq_out;
+        else { R.HS[l] = (float*)base; base += Z.hseq; }
+    }
+    for (int l = 0; l < layers; ++l) { R.CS[l] = (float*)base; base += Z.cst; }
+    if (Z.zx0) {
+        R.ZX[0] = (float*)base; base += Z.zx0;
+        for (int l = 1; l < layers; ++l) { R.ZX[l] = (float*)base; base += Z.zxl; }
+    }
+    for (int l = 0; l < layers; ++l) { R.ZW[l] = (float*)base; base += Z.zw; }
+    for (int l = 0; l < layers; ++l) {
+        const VadSeqSlot sl = vad_seq_slot(cin_p, hid_p, l);
+        R.W[l] = packed + sl.w; R.B[l] = packed + sl.b;
+        if (state_in) { R.h0[l] = state_in + (size_t)2 * l * b * fs_hid; R.c0[l] = R.h0[l] + (size_t)b * fs_hid; }
+    }
+    R.x = x; R.fs_x = fs_x; R.clip_x = (long long)t * fs_x; R.nf_x = (int)b * t; R.cs = t;
+    R.nc = (int)b; R.t = t; R.h16 = gh; R.w16 = gw; R.cin = cin_p; R.hid = hid_p; R.layers = layers;
+    R.wino = precision == VAD_PREC_WINO;
+    R.precision = R.wino ? VAD_PREC_FP32 : precision;
+    TRY(lstm_rollout(R, s));
+    if (state_out) {
+        // (one launch per layer: the sequences may live in the caller's buffer, not at one stride)
+        for (int l = 0; l < layers; ++l)
+            TRY(vad_state_store(R.HS[l], 0, R.CS[l], 0, state_out + (size_t)2 * l * b * fs_hid, b, 0, (int)b, t, fs_hid, 1, s));
+    }
+    return VAD_OK;
 }
 
 extern "C" long long vad_vid_num_windows(long long frames, int t, int stride) {
@@ -617,5 +762,5 @@ extern "C" int vad_vid_score_windows_c(const void* frames, int x_format, int pre
     if (vad_vid_packed_floats(latent, hid, layers) == 0) return VAD_ERR_ARG;
     VAD_REQUIRE(seq_scores || frame_scores || errmap || recon, "vid_score_windows: no output requested");
     return vid_run(frames, x_format, precision, in_ch, vad_vid_num_windows(nframes, t, stride), t, stride, h, w, latent, hid, layers, packed, ws,
-                   ws_bytes, chunk, seq_scores, frame_scores, errmap, recon, (hipStream_t)stream, "vid_score_windows");
+                   ws_bytes, chunk, seq_scores, frame_scores, errmap, recon, nullptr, nullptr, (hipStream_t)stream, "vid_score_windows");
 }

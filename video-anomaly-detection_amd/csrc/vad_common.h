@@ -179,6 +179,10 @@ int vad_conv3x3_c3_stats_t(const void* x, int fmt, const float* w, const float* 
 // vad_score_finalize + the device-side blob check: when hdr != NULL and hdr[1] != want_tag every score becomes NaN
 // csrc/wide_io.hip (models with in_channels > 3)
 int vad_nchw_to_nhwc_pad(const float* x, float* out, long long n, int h, int w, int c, int cpad, void* stream);
+// csrc/state_io.hip: rows [row0, row0+nc) of every layer of a state blob sized for b streams <- last h of hs + l*hs_layer_stride
+// ([nc][t][fs]) and cs + l*cs_layer_stride ([nc][fs])
+int vad_state_store(const float* hs, long long hs_layer_stride, const float* cs, long long cs_layer_stride, float* state, long long b, long long row0,
+                    int nc, int t, long long fs, int layers, void* stream);
 int vad_wide_score_partials(int h, int w);
 int vad_tanh_score_nhwc(const float* pre, int cpad, const float* x, int c, float* partials, float* recon, float* errmap,
                         int n, int h, int w, int t, int clip_stride, void* stream);

@@ -52,3 +52,19 @@ constexpr int VAD_MAX_IN_CH = VAD_MAX_IN_CHANNELS;
 inline int vad_wide_p(int in_ch) { return vad_pad_up(in_ch, 32); }
 ImgLayout img_layout(int in_ch, int latent);            // real dimensions in, padded slots out
 VidLayout vid_layout(int in_ch, int latent, int hid, int layers);
+
+// Layer-level ConvLSTM weight set (vad_convlstm_pack / vad_convlstm_seq): per layer a 3x3 slot of (4*hid_p, x + hid_p) in either
+// form (direct or Winograd, as in the model blobs) and 4*hid_p biases, each aligned to 4 floats.  vad_seq_slot(.., layers).w is
+// the total.
+struct VadSeqSlot { size_t w, b; };
+inline VadSeqSlot vad_seq_slot(int cin_p, int hid_p, int layer) {
+    size_t off = 0;
+    VadSeqSlot s{0, 0};
+    for (int l = 0; l <= layer; ++l) {
+        s.w = off;
+        off = (off + vad_pack_conv3x3_wino_floats(4 * hid_p, (l == 0 ? cin_p : hid_p) + hid_p) + 3) & ~(size_t)3;
+        s.b = off;
+        off = (off + (size_t)4 * hid_p + 3) & ~(size_t)3;
+    }
+    return s;
+}

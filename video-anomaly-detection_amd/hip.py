@@ -16,7 +16,7 @@ PKG_DIR = Path(__file__).resolve().parent
 REPO_DIR = PKG_DIR.parent
 CSRC = PKG_DIR / "csrc"
 LIB_PATH = Path(os.environ.get("VAD_LIB", PKG_DIR / "libvad_hip.so"))
-SOURCES = ["conv_mfma.hip", "conv_wino.hip", "dec4_fused.hip", "tail.hip", "wide_io.hip", "ssim.hip", "train_ops.hip", "train_step.hip", "train_step_img.hip", "vad_api.hip", "pack.cpp"]
+SOURCES = ["conv_mfma.hip", "conv_wino.hip", "dec4_fused.hip", "tail.hip", "wide_io.hip", "state_io.hip", "ssim.hip", "train_ops.hip", "train_step.hip", "train_step_img.hip", "vad_api.hip", "pack.cpp"]
 
 VAD_OK = 0
 ABI_VERSION = 3
@@ -49,7 +49,7 @@ MAX_WIDTH = 4096          # VAD_MAX_WIDTH: largest latent_dim / lstm_hidden_dim
 
 _lock = threading.Lock()
 _lib = None
-calls = {"img_score": 0, "vid_score": 0}   # tests assert the native path really ran
+calls = {"img_score": 0, "vid_score": 0, "vid_score_stateful": 0, "convlstm_seq": 0}   # tests assert the native path really ran
 
 
 class VadError(RuntimeError):
@@ -233,6 +233,19 @@ SIGNATURES = {
     "vad_vid_windows_workspace_bytes_c": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i, _i]),
     "vad_vid_score_windows_c": (_i, [_vp, _i, _i, _i, _ll, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _i, _vp, _vp, _vp, _vp, _vp]),
     "vad_vid_score_windows": (_i, [_vp, _ll, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _i, _vp, _vp, _vp, _vp, _vp]),
+    # recurrent state carried across calls (stateful scoring, layer-level ConvLSTM roll-out)
+    "vad_vid_state_floats": (_sz, [_i, _i, _i, _i, _i]),
+    "vad_convlstm_state_floats": (_sz, [_i, _i, _i, _i, _i]),
+    "vad_vid_score_s": (_i, [_vp, _i, _i, _i, _ll, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vad_state_import": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "vad_state_export": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "vad_nchw_to_nhwc_padded": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _vp]),
+    "vad_nhwc_padded_to_nchw": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _vp]),
+    "vad_convlstm_padded_dims": (_i, [_i, _vp, _i, _vp, _vp]),
+    "vad_convlstm_packed_floats": (_sz, [_i, _i, _i]),
+    "vad_convlstm_pack": (_i, [_vp, _i, _i, _vp, _i, _i, _vp]),
+    "vad_convlstm_seq_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i]),
+    "vad_convlstm_seq": (_i, [_vp, _i, _ll, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _i, _vp, _vp, _vp]),
     "vad_graph_begin": (_i, [_vp]),
     "vad_graph_end": (_i, [_vp, C.POINTER(_vp)]),
     "vad_graph_launch": (_i, [_vp, _vp]),

@@ -84,6 +84,30 @@ def score_clips(model, loader: Iterable[dict], device, per_frame: bool = False):
     return np.array(seq), np.array(labels)
 
 
+def score_frames_stateful(model, frame_iter: Iterable, batch: int = 1, state=None, device=None):
+    """Drive live streams through `VideoAutoencoder.score_stateful`: `frame_iter` yields the newest frames, one item per
+    time step - `[B,C,H,W]` float (`[B,H,W,3]` uint8) for `batch` = B parallel streams, or `[B,T,...]` to hand over a few
+    frames per stream at once.  Every frame goes through the encoder, ONE ConvLSTM step and the decoder once; the
+    recurrent state is carried between calls (the reference's video-file mode re-scores a 16-frame window per new frame,
+    evaluate_video.py:322-352).  Returns (float32[B, frames] scores, final VideoState); `state` continues earlier streams."""
+    scores = []
+    with torch.no_grad():
+        for frames in frame_iter:
+            frames = torch.as_tensor(frames)
+            if device is not None:
+                frames = frames.to(device)
+            if frames.dim() == 4:
+                frames = frames.unsqueeze(1)
+            if frames.shape[0] != batch:
+                raise hip.VadError(f"expected {batch} streams per step, got {tuple(frames.shape)}")
+            out = model.score_stateful(frames, state)
+            state = out["state"]
+            scores.append(out["frame"])
+    if not scores:
+        return np.zeros((batch, 0), np.float32), state
+    return torch.cat(scores, dim=1).cpu().numpy(), state
+
+
 # ------------------------------------------------------------------------------ device synth
 def synth_frames_device(seed: int, first_frame: int, n: int, h: int = 256, w: int = 256, c: int = 3,
                         device="cuda", anomalies: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:

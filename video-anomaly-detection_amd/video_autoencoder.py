@@ -51,10 +51,116 @@ class ConvLSTM(nn.Module):
         self.return_all_layers = return_all_layers
         dims = [input_dim] + self.hidden_dims
         self.cells = nn.ModuleList(ConvLSTMCell(dims[i], dims[i + 1], kernel_size) for i in range(self.num_layers))
+        self.kernel_size = kernel_size
+        self._hip = _HipScorer()
+
+    #: arithmetic of the HIP roll-out: the stand-alone module runs the exact-fp32 steps
+    precision = "fp32"
+
+    # ------------------------------------------------------------------ HIP path
+    def _use_hip(self, x) -> bool:
+        """GPU tensors under eval() + no_grad() run vad_convlstm_seq; train mode, autograd and CPU tensors keep the torch
+        composition below (the model's own training path differentiates through it)."""
+        return (not self.training and not torch.is_grad_enabled() and x.is_cuda and self.kernel_size == 3
+                and x.dim() == 5 and x.shape[0] > 0 and x.shape[1] > 0)
+
+    def train(self, mode: bool = True):
+        if mode != self.training:
+            self._hip.key = None
+        return super().train(mode)
+
+    def invalidate_packed(self) -> None:
+        """Drop the packed-weight cache (see ConvAutoencoder.invalidate_packed)."""
+        self._hip.key = None
+
+    def _dims(self):
+        """(cin_p, hid_p): the padded widths the roll-out runs at (vad_convlstm_padded_dims)."""
+        hids = (hip.C.c_int * self.num_layers)(*self.hidden_dims)
+        cin_p, hid_p = hip.C.c_int(0), hip.C.c_int(0)
+        hip.check(hip.lib().vad_convlstm_padded_dims(self.input_dim, hids, self.num_layers, hip.C.byref(cin_p), hip.C.byref(hid_p)),
+                  "vad_convlstm_padded_dims")
+        return cin_p.value, hid_p.value
+
+    def _packed(self, device) -> torch.Tensor:
+        l = hip.lib()
+        mode = hip.precision_mode(self.precision)
+        key = (mode,) + _HipScorer.state_key(self)
+        if self._hip.key != key or self._hip.packed is None or self._hip.packed.device != device:
+            cin_p, hid_p = self._dims()
+            params = _HipScorer.float_params(self)
+            blob = np.empty(l.vad_convlstm_packed_floats(cin_p, hid_p, self.num_layers), dtype=np.float32)
+            hids = (hip.C.c_int * self.num_layers)(*self.hidden_dims)
+            hip.check(l.vad_convlstm_pack(hip.pointer_array(params), len(params), self.input_dim, hids, self.num_layers, mode,
+                                          blob.ctypes.data), "vad_convlstm_pack")
+            self._hip.packed = torch.from_numpy(blob).to(device)
+            self._hip.key = key
+            self._hip.mode = mode
+        return self._hip.packed
+
+    def _hip_forward(self, x, hidden_state):
+        """x [B,T,C,H,W] on the GPU -> (per-layer h sequences, per-layer (h, c)) through vad_convlstm_seq."""
+        l = hip.lib()
+        b, t, c, h, w = x.shape
+        if c != self.input_dim:
+            raise hip.VadError(f"ConvLSTM expects {self.input_dim} input channels, got {tuple(x.shape)}")
+        dev = x.device
+        layers = self.num_layers
+        packed = self._packed(dev)
+        cin_p, hid_p = self._dims()
+        nstate = l.vad_convlstm_state_floats(b, h, w, hid_p, layers)
+        nws = l.vad_convlstm_seq_workspace_bytes(b, t, h, w, cin_p, hid_p, layers, int(self.return_all_layers))
+        if nstate == 0 or nws == 0:
+            raise hip.VadError(f"ConvLSTM roll-out of {tuple(x.shape)} is not supported by the HIP path")
+        if hidden_state is not None:
+            if len(hidden_state) != layers:
+                raise hip.VadError(f"hidden_state must hold one (h, c) per layer ({layers}), got {len(hidden_state)}")
+            for li, (hs, cs) in enumerate(hidden_state):
+                want = (b, self.hidden_dims[li], h, w)
+                if tuple(hs.shape) != want or tuple(cs.shape) != want or not hs.is_cuda or not cs.is_cuda:
+                    raise hip.VadError(f"hidden_state[{li}] must be two cuda tensors of shape {want}, got "
+                                       f"{tuple(hs.shape)} / {tuple(cs.shape)} on {hs.device} / {cs.device}")
+        with torch.cuda.device(dev):
+            st = hip.current_stream()
+            xs = x.contiguous().float()
+            xn = torch.empty(b * t * h * w * cin_p, dtype=torch.float32, device=dev)
+            hip.check(l.vad_nchw_to_nhwc_padded(xs.data_ptr(), xn.data_ptr(), b * t, h, w, c, cin_p, st), "vad_nchw_to_nhwc_padded")
+            state_in = None
+            if hidden_state is not None:
+                state_in = torch.empty(nstate, dtype=torch.float32, device=dev)
+                for li, (hs, cs) in enumerate(hidden_state):
+                    hs, cs = hs.contiguous().float(), cs.contiguous().float()
+                    hip.check(l.vad_state_import(hs.data_ptr(), cs.data_ptr(), state_in.data_ptr(), li, b, h, w, self.hidden_dims[li],
+                                                 hid_p, layers, st), "vad_state_import")
+            state_out = torch.empty(nstate, dtype=torch.float32, device=dev)
+            nseq = layers if self.return_all_layers else 1
+            hseq = torch.empty(nseq, b * t * h * w * hid_p, dtype=torch.float32, device=dev)
+            ws = self._hip.workspace(nws, dev)
+            hip.check(l.vad_convlstm_seq(xn.data_ptr(), self._hip.mode, b, t, h, w, cin_p, hid_p, layers, packed.data_ptr(), ws.data_ptr(),
+                                         ws.numel(), hseq.data_ptr(), int(self.return_all_layers), hip.ptr(state_in),
+                                         state_out.data_ptr(), st), "vad_convlstm_seq")
+            hip.calls["convlstm_seq"] += 1
+            outputs, finals = [], []
+            for li in (range(layers) if self.return_all_layers else [layers - 1]):
+                hid = self.hidden_dims[li]
+                o = torch.empty(b, t, hid, h, w, dtype=torch.float32, device=dev)
+                hip.check(l.vad_nhwc_padded_to_nchw(hseq[li if self.return_all_layers else 0].data_ptr(), o.data_ptr(), b * t, h, w, hid,
+                                                    hid_p, st), "vad_nhwc_padded_to_nchw")
+                hl = torch.empty(b, hid, h, w, dtype=torch.float32, device=dev)
+                cl = torch.empty_like(hl)
+                hip.check(l.vad_state_export(state_out.data_ptr(), hl.data_ptr(), cl.data_ptr(), li, b, h, w, hid, hid_p, layers, st),
+                          "vad_state_export")
+                outputs.append(o)
+                finals.append((hl, cl))
+        return outputs, finals
 
     def forward(self, x, hidden_state=None):
         if not self.batch_first:
             x = x.permute(1, 0, 2, 3, 4)
+        if self._use_hip(x):
+            outputs, finals = self._hip_forward(x, hidden_state)
+            if self.return_all_layers:
+                return outputs, finals
+            return outputs[-1], finals[-1]
         b, t, _, h, w = x.size()
         if hidden_state is None:
             hidden_state = self._init_hidden(b, h, w, x.device)
@@ -117,6 +223,82 @@ class VideoDecoder(nn.Module):
 
     def forward(self, x):
         return _per_frame(self.decoder, x)
+
+
+class VideoState:
+    """The ConvLSTM state of `b` streams between two `VideoAutoencoder.score_stateful` calls: one caller-owned device
+    tensor in the kernels' own layout (include/vad_hip.h: per layer h then c, [B][H/16][W/16][hid_p] fp32 NHWC).  Valid only
+    for the (B, H, W, hid, layers, device) it was made for; row i is stream i."""
+
+    def __init__(self, blob: torch.Tensor, b: int, h: int, w: int, hid: int, layers: int):
+        self.blob, self.b, self.h, self.w, self.hid, self.layers = blob, int(b), int(h), int(w), int(hid), int(layers)
+        self.hid_p = (self.hid + 63) // 64 * 64
+        self.device = blob.device
+        n = hip.lib().vad_vid_state_floats(self.b, self.h, self.w, self.hid, self.layers)
+        if n == 0 or blob.numel() != n or blob.dtype != torch.float32 or not blob.is_contiguous():
+            raise hip.VadError(f"not a state blob for {self.b} streams of {self.h}x{self.w}, hidden {self.hid} x {self.layers} layers: "
+                               f"{blob.dtype} tensor of {blob.numel()} elements, {n} floats expected")
+
+    @property
+    def key(self):
+        return (self.b, self.h, self.w, self.hid, self.layers, self.device)
+
+    @classmethod
+    def zeros(cls, model: "VideoAutoencoder", b: int, h: int, w: int, device) -> "VideoState":
+        """The state of `b` fresh streams of h x w frames."""
+        n = hip.lib().vad_vid_state_floats(b, h, w, model.lstm_hidden_dim, model.lstm_num_layers)
+        if n == 0:
+            raise hip.VadError(f"no state exists for {b} streams of {h}x{w} (H and W must be multiples of 16)")
+        return cls(torch.zeros(n, dtype=torch.float32, device=device), b, h, w, model.lstm_hidden_dim, model.lstm_num_layers)
+
+    @classmethod
+    def from_reference(cls, model: "VideoAutoencoder", states) -> "VideoState":
+        """From the reference's structure: a list of (h, c) per layer, NCHW [B, hid, H/16, W/16] on the GPU (what
+        `ConvLSTM.forward` returns with return_all_layers=True).  The padded channels of the blob are exact zeros."""
+        layers, hid = model.lstm_num_layers, model.lstm_hidden_dim
+        if len(states) != layers:
+            raise hip.VadError(f"expected one (h, c) per layer ({layers}), got {len(states)}")
+        b, _, gh, gw = states[0][0].shape
+        for hs, cs in states:
+            if tuple(hs.shape) != (b, hid, gh, gw) or tuple(cs.shape) != (b, hid, gh, gw) or not hs.is_cuda or not cs.is_cuda:
+                raise hip.VadError(f"every h and c must be a cuda tensor of shape {(b, hid, gh, gw)}")
+        dev = states[0][0].device
+        l = hip.lib()
+        st = cls(torch.empty(l.vad_vid_state_floats(b, gh * 16, gw * 16, hid, layers), dtype=torch.float32, device=dev),
+                 b, gh * 16, gw * 16, hid, layers)
+        with torch.cuda.device(dev):
+            for li, (hs, cs) in enumerate(states):
+                hs, cs = hs.contiguous().float(), cs.contiguous().float()
+                hip.check(l.vad_state_import(hs.data_ptr(), cs.data_ptr(), st.blob.data_ptr(), li, b, gh, gw, hid, st.hid_p, layers,
+                                             hip.current_stream()), "vad_state_import")
+        return st
+
+    def to_reference(self):
+        """[(h, c)] per layer, NCHW [B, hid, H/16, W/16], exactly what the reference's ConvLSTM.forward returns as its
+        final states (models/video_autoencoder.py:163-166)."""
+        l = hip.lib()
+        gh, gw = self.h // 16, self.w // 16
+        out = []
+        with torch.cuda.device(self.device):
+            for li in range(self.layers):
+                hs = torch.empty(self.b, self.hid, gh, gw, dtype=torch.float32, device=self.device)
+                cs = torch.empty_like(hs)
+                hip.check(l.vad_state_export(self.blob.data_ptr(), hs.data_ptr(), cs.data_ptr(), li, self.b, gh, gw, self.hid, self.hid_p,
+                                             self.layers, hip.current_stream()), "vad_state_export")
+                out.append((hs, cs))
+        return out
+
+    def clone(self) -> "VideoState":
+        return VideoState(self.blob.clone(), self.b, self.h, self.w, self.hid, self.layers)
+
+    def reset(self, rows=None) -> "VideoState":
+        """Zero the state of some streams (all by default), e.g. at a scene cut: they continue as fresh streams."""
+        planes = self.blob.view(2 * self.layers, self.b, -1)
+        if rows is None:
+            planes.zero_()
+        else:
+            planes[:, torch.as_tensor(list(rows), dtype=torch.long, device=self.device)] = 0.0
+        return self
 
 
 class VideoAutoencoder(nn.Module):
@@ -185,13 +367,15 @@ class VideoAutoencoder(nn.Module):
             self._hip.key = None
         return super().train(mode)
 
-    def capture(self, x: torch.Tensor, seq=True, frame=True, errmap=False, recon=False) -> "hip.CapturedCall":
+    def capture(self, x: torch.Tensor, seq=True, frame=True, errmap=False, recon=False, state=None) -> "hip.CapturedCall":
         """Capture ONE scoring call on clips shaped like `x` into a hipGraph and return the replayable call (see
         ConvAutoencoder.capture).  At the reference's sizes (4 clips x 16 frames, evaluate_video.py:416; one window,
         evaluate_video.py:344) a call is ~45 short launches on two streams (the ConvLSTM layer wavefront is captured with
         its fork / join); replaying them as one graph removes the per-launch host cost."""
         if not self._use_hip():
             raise hip.VadError("capture is an inference entry point: call under eval() and torch.no_grad()")
+        if state is not None:
+            raise hip.VadError("capture does not take a recurrent state: a stateful call (score_stateful) is not captured into a hipGraph")
         want = dict(seq=seq, frame=frame, errmap=errmap, recon=recon)
         _HipScorer.check_input(x, 5, self.in_channels)
         # 1- / 2-channel models: widened once outside the capture, outputs at kernel shape (see ConvAutoencoder.capture)
@@ -204,8 +388,10 @@ class VideoAutoencoder(nn.Module):
                                 keep=(self._hip.packed, self._hip.ws, xs3),
                                 post=None if self.in_channels >= 3 else self._narrow_outputs)
 
-    def _run_hip(self, x: torch.Tensor, seq=False, frame=False, errmap=False, recon=False, out=None, prewidened=False):
-        """`prewidened` (captured calls): `x` already has the kernels' 3 planes and the outputs stay at kernel shape."""
+    def _run_hip(self, x: torch.Tensor, seq=False, frame=False, errmap=False, recon=False, out=None, prewidened=False,
+                 state_in=None, state_out=None):
+        """`prewidened` (captured calls): `x` already has the kernels' 3 planes and the outputs stay at kernel shape.
+        `state_in` / `state_out` (VideoState or None, may be one object): the stateful entry point, vad_vid_score_s."""
         u8 = x.dtype == torch.uint8       # raw decoded frames [B,T,H,W,3]: normalised inside the kernels (row f-3)
         kc = _HipScorer.kernel_channels(self.in_channels)
         cin = kc if prewidened else self.in_channels
@@ -238,13 +424,26 @@ class VideoAutoencoder(nn.Module):
                 out["recon"] = torch.empty(b, t, kc, h, w, dtype=torch.float32, device=dev)
         if b == 0:                                        # an empty batch gives empty outputs, as the reference's modules do
             return out
+        stateful = state_in is not None or state_out is not None
+        for st in (state_in, state_out):
+            if st is not None and st.key != (b, h, w, self.lstm_hidden_dim, self.lstm_num_layers, dev):
+                raise hip.VadError(f"the state was made for (streams, H, W, hidden, layers, device) = {st.key}; this call has "
+                                   f"{(b, h, w, self.lstm_hidden_dim, self.lstm_num_layers, dev)}")
         with torch.cuda.device(dev):
-            hip.check(l.vad_vid_score_c(x.data_ptr(), hip.X_U8_NHWC if u8 else hip.X_F32_NCHW, self._hip.mode, kc, b, t, h, w, *dims,
-                                        packed.data_ptr(), ws.data_ptr(), ws.numel(),
-                                      chunk, hip.ptr(out.get("seq")), hip.ptr(out.get("frame")),
-                                      hip.ptr(out.get("errmap")), hip.ptr(out.get("recon")), hip.current_stream()),
-                      "vad_vid_score")
-        hip.calls["vid_score"] += 1
+            if stateful:
+                hip.check(l.vad_vid_score_s(x.data_ptr(), hip.X_U8_NHWC if u8 else hip.X_F32_NCHW, self._hip.mode, kc, b, t, h, w, *dims,
+                                            packed.data_ptr(), ws.data_ptr(), ws.numel(), chunk, hip.ptr(out.get("seq")),
+                                            hip.ptr(out.get("frame")), hip.ptr(out.get("errmap")), hip.ptr(out.get("recon")),
+                                            hip.ptr(state_in.blob if state_in is not None else None),
+                                            hip.ptr(state_out.blob if state_out is not None else None), hip.current_stream()),
+                          "vad_vid_score_s")
+            else:
+                hip.check(l.vad_vid_score_c(x.data_ptr(), hip.X_U8_NHWC if u8 else hip.X_F32_NCHW, self._hip.mode, kc, b, t, h, w, *dims,
+                                            packed.data_ptr(), ws.data_ptr(), ws.numel(),
+                                            chunk, hip.ptr(out.get("seq")), hip.ptr(out.get("frame")),
+                                            hip.ptr(out.get("errmap")), hip.ptr(out.get("recon")), hip.current_stream()),
+                          "vad_vid_score")
+        hip.calls["vid_score_stateful" if stateful else "vid_score"] += 1
         return out if prewidened else self._narrow_outputs(out)
 
     def _narrow_outputs(self, out: dict) -> dict:
@@ -340,6 +539,37 @@ class VideoAutoencoder(nn.Module):
                                               hip.ptr(out.get("recon")), hip.current_stream()), "vad_vid_score_windows")
         hip.calls["vid_score"] += 1
         return self._narrow_outputs(out)
+
+    def score_stateful(self, frames: torch.Tensor, state: "VideoState | None" = None, errmap: bool = False, recon: bool = False,
+                       inplace: bool = True):
+        """Continue B streams by T >= 1 frames each: `frames` [B,T,C,H,W] float (or uint8 [B,T,H,W,3]) are the NEXT frames of
+        the streams whose ConvLSTM state `state` holds (None = fresh streams).  Returns {'frame': [B,T], 'state': VideoState}
+        (+ 'errmap' [B,T,1,H,W], 'recon' [B,T,C,H,W] on request).  A given state is updated in place and returned
+        (`inplace=False`: left untouched, a new one is returned).  Scoring a clip in one call or in pieces with the state
+        carried gives the same bits; with state=None the scores are those of `get_reconstruction_error(per_frame=True)`.
+        The reference re-scores a 16-frame window per new frame (evaluate_video.py:322-352); this is O(1) work per frame.
+        The workspace is sized for this call's own T."""
+        if not self._use_hip():
+            raise hip.VadError("score_stateful is an inference entry point: call under eval() and torch.no_grad()")
+        if state is not None and not isinstance(state, VideoState):
+            raise hip.VadError(f"state must be a VideoState or None, got {type(state).__name__}")
+        _HipScorer.check_input(frames, 5, self.in_channels)
+        u8 = frames.dtype == torch.uint8
+        b, t = frames.shape[:2]
+        h, w = (frames.shape[2], frames.shape[3]) if u8 else (frames.shape[3], frames.shape[4])
+        if b == 0 or t == 0:
+            raise hip.VadError(f"score_stateful needs at least one stream and one frame, got {tuple(frames.shape)}")
+        if state is None or not inplace:
+            n = hip.lib().vad_vid_state_floats(b, h, w, self.lstm_hidden_dim, self.lstm_num_layers)
+            if n == 0:
+                raise hip.VadError(f"unsupported frame size {h}x{w}: H and W must be multiples of 16")
+            new = VideoState(torch.empty(n, dtype=torch.float32, device=frames.device), b, h, w, self.lstm_hidden_dim,
+                             self.lstm_num_layers)
+        else:
+            new = state
+        out = self._run_hip(frames, frame=True, errmap=errmap, recon=recon, state_in=state, state_out=new)
+        out["state"] = new
+        return out
 
     def score_seq_and_frames(self, x):
         """One pass returning {'seq': [B], 'frame': [B,T]} and nothing else (the reference's clip loop runs two forwards
