@@ -580,6 +580,32 @@ int vad_convlstm_seq(const float* x, int precision, long long b, int t, int gh, 
                      const float* packed_dev, void* workspace, size_t workspace_bytes, float* hseq_out, int all_layers,
                      const float* state_in, float* state_out, void* stream);
 
+/* ------------------------------------------------------------------ Resize of uint8 frames (csrc/resize_u8.hip)
+ * `transforms.Resize((S, S))` on a PIL image - the first step of every input pipeline of the reference (utils/dataset.py:65-70,
+ * utils/video_dataset.py:62-66, 191-195, 356-360, main.py:209-218) - is PIL's `Image.resize((S, S), BILINEAR)`: an antialiased,
+ * separable, integer fixed-point resample on uint8.  vad_resize_u8 reproduces it BIT FOR BIT on the device: src uint8
+ * [n, in_h, in_w, 3] (contiguous, as decoded) -> dst uint8 [n, out_h, out_w, 3], always RGB, i.e. the VAD_X_U8_NHWC form the
+ * scoring entry points take.  channel_order: 0 = src is RGB, 1 = src is BGR (what cv2.VideoCapture delivers; the reference
+ * converts with cv2.cvtColor first, utils/video_dataset.py:284, 389) - the swap happens on the load and is exact.
+ *
+ * Supported geometries: input sides 1..16384, output sides 1..4096, and on each axis in <= 64 * out; everything else is
+ * refused (vad_resize_plan_bytes returns 0).  out_h / out_w need not be multiples of 16 here (that is the models' rule).
+ *
+ * Plan: the coefficient tables of one geometry, computed once on the host in double (vad_resize_plan needs no GPU) and
+ * uploaded by the caller, who owns it like a packed weight blob (the library keeps no state); int32 words, 16-B aligned on the
+ * device, vad_resize_plan_bytes bytes (a few KB to ~200 KB).  It starts with a tagged header carrying the four sizes.  The
+ * sizes are ALSO arguments of vad_resize_u8: the host validates them, and every kernel compares them with the header ON THE
+ * DEVICE - with a plan made for another geometry (or not a plan at all) dst is filled with zeros, never with pixels, and no
+ * offset of that blob is followed.
+ *
+ * Workspace: the horizontal pass's uint8 result [n, rows the vertical pass reads, out_w, 3]; vad_resize_workspace_bytes (0 when
+ * at most one axis changes: NULL is then accepted).  A pass whose lengths are equal is skipped; with both equal dst is a copy. */
+size_t vad_resize_plan_bytes(int in_h, int in_w, int out_h, int out_w);                       /* 0 = unsupported geometry */
+int vad_resize_plan(int in_h, int in_w, int out_h, int out_w, void* plan_host);               /* host only */
+size_t vad_resize_workspace_bytes(long long n, int in_h, int in_w, int out_h, int out_w);
+int vad_resize_u8(const void* src, long long n, int in_h, int in_w, int channel_order, const void* plan_dev, void* dst, int out_h,
+                  int out_w, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ hipGraph capture / replay of a scoring call
  * vad_graph_begin(stream); <one vad_img_score* / vad_vid_score* call on `stream`>; vad_graph_end(stream, &exec) captures
  * the call's launch sequence (kernels, and the fork / join with the library's helper streams) into an instantiated

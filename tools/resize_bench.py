@@ -1,0 +1,157 @@
+"""Cost of the device Resize (developer tool; not part of the product path).  For 480p / 720p / 1080p / 2160p uint8 frames
+to SxS (default 256), in one run:
+
+  1. resize alone, N = 1 / 16 / 512 frames resident in HBM (N capped so that the raw buffer stays under --max-gb): us per
+     frame, bytes moved / time, and the fraction of the HBM floor of the same bytes at --hbm-tbps (6.29);
+  2. raw frames -> scores (`score_raw_images`, `score_raw_clips`, one stateful frame) against the SAME tree scoring frames that
+     are already SxS: the difference is the whole device cost of the feature;
+  3. the route without the feature: PIL `resize` on the CPU (a pool of at most 16 threads; PIL releases the GIL),
+     `torch.from_numpy`, upload of the SxS uint8 frames, score - against raw frames uploaded from pinned host memory, resized
+     and scored on the device (PCIe-bound at large frames: the raw bytes are many times the resized ones).
+Device-event timing around back-to-back calls after warm-up; alternatives alternate `--repeats` times, best and worst are
+reported.  Prints one JSON line.
+
+    python tools/resize_bench.py [--size 256] [--iters 20] [--warmup 5] [--repeats 3] [--max-gb 4] [--no-pil]
+"""
+import argparse
+import importlib
+import json
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+from pathlib import Path
+
+import numpy as np
+import torch
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+vad = importlib.import_module("video-anomaly-detection_amd")
+RES = {"480p": (480, 640), "720p": (720, 1280), "1080p": (1080, 1920), "2160p": (2160, 3840)}
+
+
+def timed(fn, iters: int, warmup: int) -> float:
+    """ms per call: device events around `iters` calls on the current stream."""
+    for _ in range(warmup):
+        fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def wall(fn, iters: int, warmup: int) -> float:
+    """ms per call by the host clock (the CPU route has host work the device events do not see)."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / iters
+
+
+def alternate(fns: dict, repeats: int, run) -> dict:
+    ms = {k: [] for k in fns}
+    for _ in range(repeats):
+        for k, fn in fns.items():
+            ms[k].append(run(fn))
+    return {k: (min(v), max(v)) for k, v in ms.items()}
+
+
+def load(model, seed):
+    shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
+    model.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in vad.synth.synthetic_state(shapes, seed).items()})
+    return model.cuda().eval()
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", type=int, default=256)
+    ap.add_argument("--res", nargs="+", default=list(RES))
+    ap.add_argument("--frames", type=int, nargs="+", default=[1, 16, 512])
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--max-gb", type=float, default=4.0)
+    ap.add_argument("--hbm-tbps", type=float, default=6.29)
+    ap.add_argument("--score-frames", type=int, default=64, help="images per call in parts 2 and 3 (clips: /16 clips of 16)")
+    ap.add_argument("--no-pil", action="store_true")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("resize_bench needs a GPU: a time is measured on the device or not at all")
+    S, lib = args.size, vad.hip.lib()
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    out = {"tool": "resize_bench", "size": S, "device": torch.cuda.get_device_name(0), "iters": args.iters, "repeats": args.repeats,
+           "hbm_tbps": args.hbm_tbps, "resize": [], "scores": [], "routes": []}
+    img, vid = load(vad.ConvAutoencoder(), 1), load(vad.VideoAutoencoder(), 2)
+    for name in args.res:
+        h, w = RES[name]
+        # ---- 1. resize alone
+        for n in args.frames:
+            n = max(1, min(n, int(args.max_gb * 1e9 // (h * w * 3))))
+            x = torch.randint(0, 256, (n, h, w, 3), dtype=torch.uint8, device="cuda", generator=gen)
+            rz = vad.scoring.FrameResizer(S)
+            dst = torch.empty(n, S, S, 3, dtype=torch.uint8, device="cuda")
+            ms = [timed(lambda: rz(x, out=dst), args.iters, args.warmup) for _ in range(args.repeats)]
+            mid = lib.vad_resize_workspace_bytes(n, h, w, S, S)
+            moved = x.numel() + 2 * mid + dst.numel()
+            out["resize"].append({"res": name, "frames": n, "us_per_frame": round(min(ms) * 1e3 / n, 3), "us_per_frame_max": round(max(ms) * 1e3 / n, 3),
+                                  "bytes_per_frame": moved // n, "GBps": round(moved / min(ms) / 1e6, 1),
+                                  "hbm_floor_fraction": round(moved / (args.hbm_tbps * 1e12) / (min(ms) * 1e-3), 4)})
+            del x, dst, rz
+        # ---- 2. raw frames -> scores against already-resized frames on the same tree
+        n = args.score_frames
+        raw = torch.randint(0, 256, (n, h, w, 3), dtype=torch.uint8, device="cuda", generator=gen)
+        rz = vad.scoring.FrameResizer(S)
+        small = rz(raw).clone()
+        b = max(1, n // 16)
+        raw_c, small_c = raw[:b * 16].view(b, 16, h, w, 3), small[:b * 16].view(b, 16, S, S, 3)
+        with torch.no_grad():
+            assert torch.equal(vad.scoring.score_raw_images(img, raw, resizer=rz), img.get_reconstruction_error(small))
+            state = vid.score_stateful(small_c[:1, :15])["state"]
+            forms = {
+                "images": (lambda: vad.scoring.score_raw_images(img, raw, resizer=rz), lambda: img.get_reconstruction_error(small), n),
+                "clips": (lambda: vad.scoring.score_raw_clips(vid, raw_c, resizer=rz), lambda: vid.get_reconstruction_error(small_c), b * 16),
+                "stateful_1": (lambda: vid.score_stateful(rz(raw_c[:1, 15:]), state), lambda: vid.score_stateful(small_c[:1, 15:], state), 1),
+            }
+            for form, (f_raw, f_small, frames) in forms.items():
+                r = alternate({"raw": f_raw, "resized": f_small}, args.repeats, lambda fn: timed(fn, args.iters, args.warmup))
+                out["scores"].append({"res": name, "form": form, "frames": frames, "raw_ms": round(r["raw"][0], 4), "raw_ms_max": round(r["raw"][1], 4),
+                                      "resized_ms": round(r["resized"][0], 4), "resized_ms_max": round(r["resized"][1], 4),
+                                      "ratio": round(r["raw"][0] / r["resized"][0], 4)})
+            # ---- 3. CPU resize + upload of small frames against raw frames uploaded from pinned memory
+            host_raw = raw.cpu().pin_memory()
+            dev_raw = torch.empty_like(raw)
+
+            def new_route():
+                dev_raw.copy_(host_raw, non_blocking=True)
+                return vad.scoring.score_raw_images(img, dev_raw, resizer=rz)
+            routes = {"pinned_raw_upload_resize_score": new_route}
+            if not args.no_pil:
+                from PIL import Image
+                frames_np = [f for f in host_raw.numpy()]
+                pool = ThreadPoolExecutor(max_workers=16)
+
+                def pil_route():
+                    small_np = np.stack(list(pool.map(lambda f: np.asarray(Image.fromarray(f, "RGB").resize((S, S), Image.BILINEAR)), frames_np)))
+                    return img.get_reconstruction_error(torch.from_numpy(small_np).cuda())
+                assert torch.equal(pil_route(), new_route())
+                routes["pil_16_threads_upload_score"] = pil_route
+            r = alternate(routes, args.repeats, lambda fn: wall(fn, max(3, args.iters // 4), 2))
+            row = {"res": name, "frames": n}
+            for k, (lo, hi) in r.items():
+                row[k + "_ms"], row[k + "_ms_max"], row[k + "_frames_per_s"] = round(lo, 3), round(hi, 3), round(n / lo * 1e3, 1)
+            out["routes"].append(row)
+            if not args.no_pil:
+                pool.shutdown()
+        del raw, small, dev_raw, host_raw
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

@@ -519,3 +519,111 @@ extern "C" int vad_convlstm_pack(const float* const* P, int nparams, int cin, co
     }
     return rc;
 }
+
+// --------------------------------------------------------------------------- resize plan (csrc/resize_u8.hip)
+// Coefficients of the antialiased bilinear (triangle) resample that `PIL.Image.resize(size, BILINEAR)` - i.e.
+// `transforms.Resize` on a PIL image, reference utils/dataset.py:65-70, utils/video_dataset.py:62-66 - runs on uint8, restated:
+// per axis, in IEEE double with every operation rounded on its own (no fused multiply-add, no reassociation; the pragma
+// below and -ffp-contract=off on this file both say so, tests/test_resize_plan.py compares integer for integer):
+//     scale = n_in / n_out, fs = max(scale, 1), support = 1.0 * fs, ss = 1 / fs
+//     center = (o + 0.5) * scale;  lo = (int)(center - support + 0.5) clamped to >= 0;  hi = (int)(center + support + 0.5) clamped to <= n_in
+//     w_j = max(0, 1 - |(j + lo - center + 0.5) * ss|), j in [0, hi - lo);  w_j /= sum (index order);  k_j = (int)(0.5 + w_j * 2^22)
+// The kernels evaluate out = clip((2^21 + sum_j in[lo + j] * k_j) >> 22) in 32-bit integers, horizontal pass first.
+namespace {
+struct AxisScale { double scale, support, ss; };
+AxisScale axis_scale(int n_in, int n_out) {
+#pragma clang fp contract(off)
+    AxisScale a;
+    a.scale = (double)n_in / (double)n_out;
+    const double fs = a.scale < 1.0 ? 1.0 : a.scale;
+    a.support = 1.0 * fs;
+    a.ss = 1.0 / fs;
+    return a;
+}
+void axis_bounds(const AxisScale& a, int n_in, int o, double* center, int* lo, int* hi) {
+#pragma clang fp contract(off)
+    const double c = ((double)o + 0.5) * a.scale;
+    int l = (int)(c - a.support + 0.5), h = (int)(c + a.support + 0.5);
+    if (l < 0) l = 0;
+    if (h > n_in) h = n_in;
+    *center = c; *lo = l; *hi = h;
+}
+int axis_kpad(int n_in, int n_out) {
+    if (n_in == n_out) return 0;
+    const AxisScale a = axis_scale(n_in, n_out);
+    int kmax = 0;
+    for (int o = 0; o < n_out; ++o) {
+        double c; int lo, hi;
+        axis_bounds(a, n_in, o, &c, &lo, &hi);
+        if (hi - lo > kmax) kmax = hi - lo;
+    }
+    return (kmax + 3) & ~3;
+}
+size_t axis_words(int n_out, int kpad) { return kpad ? align4((size_t)2 * n_out) + (size_t)kpad * n_out : 0; }
+
+// lo[n_out], count[n_out], weights [kpad/4][n_out][4] at `t`
+void axis_table(int n_in, int n_out, int kpad, int* t) {
+#pragma clang fp contract(off)
+    const AxisScale a = axis_scale(n_in, n_out);
+    int* lo_t = t, *cnt_t = t + n_out, *w_t = t + align4((size_t)2 * n_out);
+    std::vector<double> w;
+    for (int o = 0; o < n_out; ++o) {
+        double center; int lo, hi;
+        axis_bounds(a, n_in, o, &center, &lo, &hi);
+        const int cnt = hi - lo;
+        w.assign(cnt > 0 ? cnt : 0, 0.0);
+        double total = 0.0;
+        for (int j = 0; j < cnt; ++j) {
+            double x = ((double)(j + lo) - center + 0.5) * a.ss;
+            if (x < 0.0) x = -x;
+            w[j] = x < 1.0 ? 1.0 - x : 0.0;
+            total += w[j];
+        }
+        lo_t[o] = lo;
+        cnt_t[o] = cnt > 0 ? cnt : 0;
+        for (int j = 0; j < cnt; ++j) {
+            const double v = total != 0.0 ? w[j] / total : w[j];
+            const int k = v < 0.0 ? (int)(-0.5 + v * 4194304.0) : (int)(0.5 + v * 4194304.0);
+            w_t[((size_t)(j / 4) * n_out + o) * 4 + (j & 3)] = k;
+        }
+    }
+}
+}  // namespace
+
+void vad_resize_bounds(int n_in, int n_out, int o, int* lo, int* hi) {
+    double c;
+    axis_bounds(axis_scale(n_in, n_out), n_in, o, &c, lo, hi);
+}
+
+static int resize_geometry_ok(const char* who, int in_h, int in_w, int out_h, int out_w) {
+    REQ(vad_resize_axis_ok(in_h, out_h) && vad_resize_axis_ok(in_w, out_w),
+        "%s: unsupported geometry %dx%d -> %dx%d (input sides 1..%d, output sides 1..%d, at most a %d-fold reduction per axis)", who,
+        in_h, in_w, out_h, out_w, VAD_RESIZE_MAX_IN, VAD_RESIZE_MAX_OUT, VAD_RESIZE_MAX_RATIO);
+    return VAD_OK;
+}
+
+extern "C" size_t vad_resize_plan_bytes(int in_h, int in_w, int out_h, int out_w) {
+    if (resize_geometry_ok("resize_plan_bytes", in_h, in_w, out_h, out_w) != VAD_OK) return 0;
+    return (VAD_RESIZE_HEADER_WORDS + axis_words(out_w, axis_kpad(in_w, out_w)) + axis_words(out_h, axis_kpad(in_h, out_h))) * sizeof(int);
+}
+
+extern "C" int vad_resize_plan(int in_h, int in_w, int out_h, int out_w, void* plan_host) {
+    REQ(plan_host, "resize_plan: null pointer");
+    const int rc = resize_geometry_ok("resize_plan", in_h, in_w, out_h, out_w);
+    if (rc != VAD_OK) return rc;
+    int* p = (int*)plan_host;
+    const int kh = axis_kpad(in_w, out_w), kv = axis_kpad(in_h, out_h);
+    const size_t off_h = VAD_RESIZE_HEADER_WORDS, off_v = off_h + axis_words(out_w, kh), total = off_v + axis_words(out_h, kv);
+    memset(p, 0, total * sizeof(int));
+    int row0 = 0, row1 = in_h, unused;
+    if (kv) {
+        vad_resize_bounds(in_h, out_h, 0, &row0, &unused);
+        vad_resize_bounds(in_h, out_h, out_h - 1, &unused, &row1);
+    }
+    const unsigned hdr[VAD_RESIZE_HEADER_WORDS] = {VAD_RESIZE_MAGIC, vad_resize_tag(), (unsigned)in_h, (unsigned)in_w, (unsigned)out_h, (unsigned)out_w,
+        (unsigned)kh, (unsigned)kv, kh ? (unsigned)off_h : 0u, kv ? (unsigned)off_v : 0u, (unsigned)row0, (unsigned)(row1 - row0), (unsigned)total, 0, 0, 0};
+    memcpy(p, hdr, sizeof hdr);
+    if (kh) axis_table(in_w, out_w, kh, p + off_h);
+    if (kv) axis_table(in_h, out_h, kv, p + off_v);
+    return VAD_OK;
+}

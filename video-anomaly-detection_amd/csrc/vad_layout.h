@@ -68,3 +68,22 @@ inline VadSeqSlot vad_seq_slot(int cin_p, int hid_p, int layer) {
     }
     return s;
 }
+
+// ---- resize plan blob (vad_resize_plan, pack.cpp; read by csrc/resize_u8.hip), int32 words:
+//   header [16]: {VAD_RESIZE_MAGIC, tag, in_h, in_w, out_h, out_w, kpad_h, kpad_v, off_h, off_v, row0, rows, total words, 0, 0, 0}
+//   per axis that is resampled (h = horizontal: in_w -> out_w, v = vertical: in_h -> out_h), at word offset off_*:
+//       lo[n_out], count[n_out], (padding to a multiple of 4 words), weights [kpad / 4][n_out][4]
+//   weight (g, o, t) = coefficient of tap 4 g + t of output index o, 0 for taps >= count[o]; kpad = the axis' largest count
+//   rounded up to a multiple of 4.  An axis whose lengths are equal has no table (kpad 0, off 0): that pass is skipped.
+//   row0 / rows: the input rows the vertical pass reads, i.e. the rows the horizontal pass has to produce.
+constexpr unsigned VAD_RESIZE_MAGIC = 0x52444156u;   // "VADR"
+constexpr int VAD_RESIZE_HEADER_WORDS = 16;
+enum { RZ_MAGIC = 0, RZ_TAG, RZ_IN_H, RZ_IN_W, RZ_OUT_H, RZ_OUT_W, RZ_KPAD_H, RZ_KPAD_V, RZ_OFF_H, RZ_OFF_V, RZ_ROW0, RZ_ROWS, RZ_TOTAL };
+inline unsigned vad_resize_tag(void) { return ((unsigned)VAD_ABI_VERSION << 16) | 1u; }
+constexpr int VAD_RESIZE_MAX_IN = 16384, VAD_RESIZE_MAX_OUT = 4096, VAD_RESIZE_MAX_RATIO = 64;
+inline bool vad_resize_axis_ok(int n_in, int n_out) {
+    return n_in >= 1 && n_in <= VAD_RESIZE_MAX_IN && n_out >= 1 && n_out <= VAD_RESIZE_MAX_OUT &&
+           (long long)n_in <= (long long)VAD_RESIZE_MAX_RATIO * n_out;
+}
+// taps [lo, hi) of output index o of one axis (pack.cpp; double arithmetic, never contracted)
+void vad_resize_bounds(int n_in, int n_out, int o, int* lo, int* hi);

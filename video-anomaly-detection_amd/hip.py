@@ -16,7 +16,7 @@ PKG_DIR = Path(__file__).resolve().parent
 REPO_DIR = PKG_DIR.parent
 CSRC = PKG_DIR / "csrc"
 LIB_PATH = Path(os.environ.get("VAD_LIB", PKG_DIR / "libvad_hip.so"))
-SOURCES = ["conv_mfma.hip", "conv_wino.hip", "dec4_fused.hip", "tail.hip", "wide_io.hip", "state_io.hip", "ssim.hip", "train_ops.hip", "train_step.hip", "train_step_img.hip", "vad_api.hip", "pack.cpp"]
+SOURCES = ["conv_mfma.hip", "conv_wino.hip", "dec4_fused.hip", "tail.hip", "wide_io.hip", "state_io.hip", "resize_u8.hip", "ssim.hip", "train_ops.hip", "train_step.hip", "train_step_img.hip", "vad_api.hip", "pack.cpp"]
 
 VAD_OK = 0
 ABI_VERSION = 3
@@ -67,11 +67,13 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     objdir = PKG_DIR / "build"
     objdir.mkdir(exist_ok=True)
     flags = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", f"-I{REPO_DIR / 'include'}", f"-I{CSRC}"]
+    # pack.cpp: the resize planner's doubles must round operation by operation (its function-level pragma says the same)
+    extra = {"pack.cpp": ["-ffp-contract=off"]}
 
     def compile_one(src: Path) -> Path:
         obj = objdir / (src.name + ".o")
         if force or not obj.exists() or obj.stat().st_mtime < max(src.stat().st_mtime, hdr_time):
-            cmd = [hipcc, *flags, "-c", str(src), "-o", str(obj)]
+            cmd = [hipcc, *flags, *extra.get(src.name, []), "-c", str(src), "-o", str(obj)]
             if verbose:
                 print(" ".join(cmd), flush=True)
             subprocess.run(cmd, check=True)
@@ -246,6 +248,11 @@ SIGNATURES = {
     "vad_convlstm_pack": (_i, [_vp, _i, _i, _vp, _i, _i, _vp]),
     "vad_convlstm_seq_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i]),
     "vad_convlstm_seq": (_i, [_vp, _i, _ll, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _i, _vp, _vp, _vp]),
+    # PIL-exact Resize of uint8 frames (csrc/resize_u8.hip)
+    "vad_resize_plan_bytes": (_sz, [_i, _i, _i, _i]),
+    "vad_resize_plan": (_i, [_i, _i, _i, _i, _vp]),
+    "vad_resize_workspace_bytes": (_sz, [_ll, _i, _i, _i, _i]),
+    "vad_resize_u8": (_i, [_vp, _ll, _i, _i, _i, _vp, _vp, _i, _i, _vp, _sz, _vp]),
     "vad_graph_begin": (_i, [_vp]),
     "vad_graph_end": (_i, [_vp, C.POINTER(_vp)]),
     "vad_graph_launch": (_i, [_vp, _vp]),

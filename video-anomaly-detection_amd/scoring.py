@@ -84,18 +84,24 @@ def score_clips(model, loader: Iterable[dict], device, per_frame: bool = False):
     return np.array(seq), np.array(labels)
 
 
-def score_frames_stateful(model, frame_iter: Iterable, batch: int = 1, state=None, device=None):
+def score_frames_stateful(model, frame_iter: Iterable, batch: int = 1, state=None, device=None, image_size=None,
+                          channel_order: str = "rgb"):
     """Drive live streams through `VideoAutoencoder.score_stateful`: `frame_iter` yields the newest frames, one item per
     time step - `[B,C,H,W]` float (`[B,H,W,3]` uint8) for `batch` = B parallel streams, or `[B,T,...]` to hand over a few
     frames per stream at once.  Every frame goes through the encoder, ONE ConvLSTM step and the decoder once; the
     recurrent state is carried between calls (the reference's video-file mode re-scores a 16-frame window per new frame,
-    evaluate_video.py:322-352).  Returns (float32[B, frames] scores, final VideoState); `state` continues earlier streams."""
+    evaluate_video.py:322-352).  Returns (float32[B, frames] scores, final VideoState); `state` continues earlier streams.
+    With `image_size` (int or (h, w)) the items are decoded uint8 frames `[B,H,W,3]` / `[B,T,H,W,3]` at any one resolution, in
+    `channel_order` "rgb" or "bgr": they are resized on the device (`FrameResizer`, PIL-exact) before they are scored."""
     scores = []
+    resizer = FrameResizer(image_size, channel_order) if image_size is not None else None
     with torch.no_grad():
         for frames in frame_iter:
             frames = torch.as_tensor(frames)
             if device is not None:
                 frames = frames.to(device)
+            if resizer is not None:
+                frames = resizer(frames)
             if frames.dim() == 4:
                 frames = frames.unsqueeze(1)
             if frames.shape[0] != batch:
@@ -106,6 +112,96 @@ def score_frames_stateful(model, frame_iter: Iterable, batch: int = 1, state=Non
     if not scores:
         return np.zeros((batch, 0), np.float32), state
     return torch.cat(scores, dim=1).cpu().numpy(), state
+
+
+# ------------------------------------------------------------------------------ Resize on the device
+CHANNEL_ORDERS = {"rgb": 0, "bgr": 1}
+
+
+class FrameResizer:
+    """`transforms.Resize(size)` of the reference's input pipelines (utils/dataset.py:65-70, utils/video_dataset.py:62-66) for
+    decoded uint8 frames that are already on the GPU: `resizer(frames)` takes uint8 `[..., H, W, 3]` (contiguous, any number of
+    leading axes) and returns uint8 `[..., h, w, 3]` RGB, byte for byte what PIL's `Image.resize((w, h), BILINEAR)` gives - the
+    form the models take as uint8 input.  `channel_order="bgr"` for frames as `cv2.VideoCapture` delivers them.
+
+    The object owns the device plan blob of every input geometry it has seen (computed once on the host, like packed weights)
+    and the workspace of the horizontal pass; use one per thread / stream."""
+
+    def __init__(self, size=256, channel_order: str = "rgb"):
+        if isinstance(size, (tuple, list)):
+            if len(size) != 2:
+                raise hip.VadError(f"FrameResizer: size must be an int or (h, w), got {size!r}")
+            self.out_h, self.out_w = int(size[0]), int(size[1])
+        else:
+            self.out_h = self.out_w = int(size)
+        if channel_order not in CHANNEL_ORDERS:
+            raise hip.VadError(f"FrameResizer: channel_order must be one of {sorted(CHANNEL_ORDERS)}, got {channel_order!r}")
+        self.channel_order = channel_order
+        self._plans = {}
+        self._ws = None
+
+    def _plan(self, in_h: int, in_w: int, device) -> torch.Tensor:
+        key = (str(device), in_h, in_w)
+        if key not in self._plans:
+            l = hip.lib()
+            nbytes = l.vad_resize_plan_bytes(in_h, in_w, self.out_h, self.out_w)
+            blob = np.empty(max(nbytes // 4, 1), np.int32)
+            hip.check(l.vad_resize_plan(in_h, in_w, self.out_h, self.out_w, blob.ctypes.data), "vad_resize_plan")
+            self._plans[key] = torch.from_numpy(blob).to(device)
+        return self._plans[key]
+
+    def __call__(self, frames: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
+            raise hip.VadError("FrameResizer: frames must be a GPU tensor (the resize runs on the device; there is no CPU fallback)")
+        if frames.dtype != torch.uint8:
+            raise hip.VadError(f"FrameResizer: expected uint8 frames [..., H, W, 3], got dtype {frames.dtype}")
+        if frames.dim() < 3 or frames.shape[-1] != 3:
+            raise hip.VadError(f"FrameResizer: expected uint8 frames [..., H, W, 3], got {tuple(frames.shape)}")
+        if not frames.is_contiguous():
+            raise hip.VadError("FrameResizer: frames must be contiguous")
+        lead, in_h, in_w = tuple(frames.shape[:-3]), int(frames.shape[-3]), int(frames.shape[-2])
+        n = int(np.prod(lead, dtype=np.int64)) if lead else 1
+        shape = lead + (self.out_h, self.out_w, 3)
+        with torch.cuda.device(frames.device):
+            plan = self._plan(in_h, in_w, frames.device)
+            if out is None:
+                out = torch.empty(shape, dtype=torch.uint8, device=frames.device)
+            elif tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != frames.device or not out.is_contiguous():
+                raise hip.VadError(f"FrameResizer: out must be a contiguous uint8 tensor {shape} on {frames.device}")
+            if n == 0:
+                return out
+            l = hip.lib()
+            need = l.vad_resize_workspace_bytes(n, in_h, in_w, self.out_h, self.out_w)
+            if need and (self._ws is None or self._ws.numel() < need or self._ws.device != frames.device):
+                self._ws = torch.empty(need, dtype=torch.uint8, device=frames.device)
+            hip.check(l.vad_resize_u8(frames.data_ptr(), n, in_h, in_w, CHANNEL_ORDERS[self.channel_order], plan.data_ptr(), out.data_ptr(),
+                                      self.out_h, self.out_w, self._ws.data_ptr() if need else None, need, hip.current_stream()),
+                      "vad_resize_u8")
+        hip.calls["resize_u8"] = hip.calls.get("resize_u8", 0) + 1
+        return out
+
+
+def resize_frames(frames: torch.Tensor, size=256, channel_order: str = "rgb") -> torch.Tensor:
+    """One-shot form of `FrameResizer` (plans the geometry on every call: keep a FrameResizer in a loop)."""
+    return FrameResizer(size, channel_order)(frames)
+
+
+def score_raw_images(model, frames_u8: torch.Tensor, image_size=256, channel_order: str = "rgb", per_pixel: bool = False,
+                     resizer: Optional[FrameResizer] = None):
+    """Decoded uint8 images `[B, H, W, 3]` at camera resolution -> Resize on the device -> `ConvAutoencoder.
+    get_reconstruction_error(per_pixel=...)`: bit for bit the scores of the frames PIL resized.  Pass a `resizer` to reuse its
+    plans and workspace across calls (its size and channel order then apply)."""
+    resizer = resizer or FrameResizer(image_size, channel_order)
+    with torch.no_grad():
+        return model.get_reconstruction_error(resizer(frames_u8), per_pixel=per_pixel)
+
+
+def score_raw_clips(model, clips_u8: torch.Tensor, image_size=256, channel_order: str = "rgb", per_frame: bool = False,
+                    resizer: Optional[FrameResizer] = None):
+    """Decoded uint8 clips `[B, T, H, W, 3]` -> Resize on the device -> `VideoAutoencoder.get_reconstruction_error(per_frame=...)`."""
+    resizer = resizer or FrameResizer(image_size, channel_order)
+    with torch.no_grad():
+        return model.get_reconstruction_error(resizer(clips_u8), per_frame=per_frame)
 
 
 # ------------------------------------------------------------------------------ device synth
