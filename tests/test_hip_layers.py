@@ -24,6 +24,31 @@ def _conv_params(rng, cout, cin, k=3):
     return w, b, [a.astype(np.float32) for a in bn]
 
 
+def _with_precision(cases, split=lambda case: True):
+    """Every case at precision 0 (VAD_PREC_FP32) under the id it always had, and - where `split(case)` - at precision 1
+    (VAD_PREC_SPLIT: weights packed AND kernels launched with it, through hip_helpers.PRECISION) as `<id>-split`."""
+    out = []
+    for case in cases:
+        name = "-".join(str(v) for v in case)
+        out.append(pytest.param(*case, 0, id=name))
+        if split(case):
+            out.append(pytest.param(*case, 1, id=name + "-split"))
+    return out
+
+
+class _precision:
+    """`with _precision(H, p):` - the helpers pack and launch with arithmetic mode p inside, VAD_PREC_FP32 again after."""
+
+    def __init__(self, H, precision):
+        self.H, self.precision = H, precision
+
+    def __enter__(self):
+        self.H.PRECISION = self.precision
+
+    def __exit__(self, *exc):
+        self.H.PRECISION = 0
+
+
 def _ref_conv(x, w, b, bn, act, pool):
     y = c_oracle.conv2d(x, w, b, 3)
     if bn is not None:
@@ -37,21 +62,28 @@ def _ref_conv(x, w, b, bn, act, pool):
     return y
 
 
-@pytest.mark.parametrize("cin,cout,h,w,act,pool", [
+# (the first-layer form, cin == 3, takes no precision: its packed weights carry both forms)
+@pytest.mark.parametrize("cin,cout,h,w,act,pool,precision", _with_precision([
     (3, 32, 16, 16, 1, False), (3, 32, 20, 36, 1, True), (3, 32, 19, 23, 2, False), (3, 64, 32, 32, 0, True),
     (32, 32, 16, 16, 1, True), (32, 32, 18, 22, 2, False), (32, 64, 24, 40, 1, False), (64, 64, 16, 32, 1, True),
     (64, 128, 8, 8, 1, False), (128, 128, 12, 20, 2, False), (128, 256, 4, 4, 1, False), (256, 256, 6, 10, 1, True),
     (32, 96, 10, 10, 0, False), (64, 192, 5, 7, 2, False),
-])
-def test_conv3x3(cin, cout, h, w, act, pool):
+], split=lambda case: case[0] != 3))
+def test_conv3x3(cin, cout, h, w, act, pool, precision):
+    """Split-fp16 operands (22-bit products, fp32 accumulation) are held to the exact kernels' bound against the oracle.
+    Measured on MI355X, max over the cases: exact 2.1e-05, split 5.2e-06."""
     import hip_helpers as H
     rng = _rng(cin * 1000 + cout + h)
     x = rng.standard_normal((2, cin, h, w)).astype(np.float32)
     wt, b, bn = _conv_params(rng, cout, cin)
-    got = H.conv3x3(x, wt, b, bn, act, pool)
     ref = _ref_conv(x, wt, b, bn, act, pool)
+    with _precision(H, precision):
+        got = H.conv3x3(x, wt, b, bn, act, pool)
+    print(f"conv3x3 precision {precision}: max abs err {max_abs(got, ref):.3e}")
     assert got.shape == ref.shape and np.isfinite(got).all()
     assert max_abs(got, ref) < ATOL
+    if precision != 0:
+        return
     # Every exact-fp32 form of the layer is the same bits: whatever the cost model picked above, the persistent 32x32x2 kernels
     # only (bit 6: never the gate-split small-grid kernel), the gate-split kernel wherever it applies (bit 7: 8-wave form; cin >= 64,
     # cout % 64 == 0), and one tile per work-group (0).
@@ -87,33 +119,45 @@ def test_conv3x3_winograd(cin, cout, h, w, act, pool, n):
     assert max_abs(got, direct) < ATOL and not np.array_equal(got, direct)       # another rounding order, stated as such
 
 
-@pytest.mark.parametrize("h,w", [(16, 16), (32, 48), (22, 18), (64, 64)])
-def test_conv3x3_c3_fused(h, w):
-    """Fused enc1 block == the two separate layers of the oracle (halo recompute, zero padding of conv #2)."""
+@pytest.mark.parametrize("h,w,precision", _with_precision([(16, 16), (32, 48), (22, 18), (64, 64)]))
+def test_conv3x3_c3_fused(h, w, precision):
+    """Fused enc1 block == the two separate layers of the oracle (halo recompute, zero padding of conv #2); the split-fp16 form
+    of its second convolution at the same bound.  Measured on MI355X, max over the cases: exact 3.8e-06, split
+    1.5e-06."""
     import hip_helpers as H
     rng = _rng(h * 100 + w)
     x = rng.uniform(-1, 1, (2, 3, h, w)).astype(np.float32)
     w0, b0, bn0 = _conv_params(rng, 32, 3)
     w1, b1, bn1 = _conv_params(rng, 32, 32)
     ref = _ref_conv(_ref_conv(x, w0, b0, bn0, 1, False), w1, b1, bn1, 1, True)
-    got = H.conv3x3_c3_fused(x, w0, b0, bn0, w1, b1, bn1)
+    l = H.hip.lib()
+    with _precision(H, precision):
+        got = H.conv3x3_c3_fused(x, w0, b0, bn0, w1, b1, bn1)
+        try:                              # persistent kernel == one-tile-per-work-group kernel, bit for bit (split: one form)
+            l.vad_debug_set_conv_variant(0)
+            one_tile = H.conv3x3_c3_fused(x, w0, b0, bn0, w1, b1, bn1)
+        finally:
+            l.vad_debug_set_conv_variant(1)
+    print(f"conv3x3_c3_fused precision {precision}: max abs err {max_abs(got, ref):.3e}")
     assert got.shape == ref.shape and np.isfinite(got).all()
     assert max_abs(got, ref) < ATOL
-    l = H.hip.lib()                       # persistent kernel == one-tile-per-work-group kernel, bit for bit
-    try:
-        l.vad_debug_set_conv_variant(0)
-        one_tile = H.conv3x3_c3_fused(x, w0, b0, bn0, w1, b1, bn1)
-    finally:
-        l.vad_debug_set_conv_variant(1)
     assert np.array_equal(got, one_tile)
 
 
 def test_conv3x3_no_bn_and_frame_strides():
+    """No BatchNorm to fold, no activation; dense frames and both strided layouts, in both arithmetic modes (a loop, not a
+    parametrisation: the test keeps its id)."""
     import hip_helpers as H
     rng = _rng(5)
     x = rng.standard_normal((3, 32, 8, 8)).astype(np.float32)
     wt, b, _ = _conv_params(rng, 32, 32)
-    assert max_abs(H.conv3x3(x, wt, b, None, 0, False), _ref_conv(x, wt, b, None, 0, False)) < ATOL
+    ref = _ref_conv(x, wt, b, None, 0, False)
+    for precision in (0, 1):
+        with _precision(H, precision):
+            dense = H.conv3x3(x, wt, b, None, 0, False)
+            assert max_abs(dense, ref) < ATOL, precision
+            for fs in (H.FS_PAD, H.FS_TIME):
+                assert np.array_equal(dense, H.conv3x3(x, wt, b, None, 0, False, fs=fs)), (precision, fs)
 
 
 @pytest.mark.parametrize("cin,cout,h,w,act", [(256, 128, 4, 4, 2), (128, 64, 8, 6, 2), (64, 32, 16, 16, 2),
@@ -161,8 +205,11 @@ def test_convlstm_step_golden(vad, golden):
     assert max_abs(h1, g["h1"]) < 2e-5 and max_abs(c1, g["c1"]) < 2e-5
 
 
-@pytest.mark.parametrize("cx,hid,h,w,zero_state", [(32, 64, 8, 8, True), (128, 128, 16, 16, False), (64, 64, 5, 9, False)])
-def test_convlstm_step_oracle(cx, hid, h, w, zero_state):
+@pytest.mark.parametrize("cx,hid,h,w,zero_state,precision",
+                         _with_precision([(32, 64, 8, 8, True), (128, 128, 16, 16, False), (64, 64, 5, 9, False)]))
+def test_convlstm_step_oracle(cx, hid, h, w, zero_state, precision):
+    """The split-fp16 step at the exact step's bound; it shares one set of staging offsets between x and h and refuses
+    cin_x != hid.  Measured on MI355X, max over the cases (h, c): exact (9.5e-07, 1.9e-06), split (4.8e-07, 7.2e-07)."""
     import hip_helpers as H
     rng = _rng(cx + hid + h)
     x = rng.standard_normal((2, cx, h, w)).astype(np.float32)
@@ -175,7 +222,13 @@ def test_convlstm_step_oracle(cx, hid, h, w, zero_state):
         hp = h0 = (rng.standard_normal((2, hid, h, w)) * 0.5).astype(np.float32)
         cp = c0 = rng.standard_normal((2, hid, h, w)).astype(np.float32)
     rh, rc = c_oracle.convlstm_cell(x, h0, c0, wt, b)
-    gh, gc = H.convlstm_step(x, hp, cp, wt, b)
+    with _precision(H, precision):
+        if precision == 1 and cx != hid:
+            with pytest.raises(H.hip.VadError, match=rf"convlstm_step: split precision needs cin_x == hid \(got {cx}, {hid}\)"):
+                H.convlstm_step(x, hp, cp, wt, b)
+            return
+        gh, gc = H.convlstm_step(x, hp, cp, wt, b)
+    print(f"convlstm_step precision {precision}: max abs err h {max_abs(gh, rh):.3e} c {max_abs(gc, rc):.3e}")
     assert max_abs(gh, rh) < 2e-5 and max_abs(gc, rc) < 2e-5
 
 
@@ -282,7 +335,7 @@ def _dec4_case(rng, n, h, w):
     return x_in, wt, bt, bn, w3, b3, frames
 
 
-def _dec4_run(H, case, fused, band=0, u8=None):
+def _dec4_run(H, case, fused, band=0):
     """dec4 block + scoring through the C ABI: fused kernel, or the two launches it replaces.  -> (recon, errmap, scores)"""
     import ctypes as C
     x_in, wt, bt, bn, w3, b3, frames = case
@@ -341,3 +394,143 @@ def test_dec4_fused_kernel(n, h, w):
     for band in (1, 2, 3, 16, 1000):
         rb, eb, sb = _dec4_run(H, case, fused=True, band=band)
         assert np.array_equal(recon, rb) and np.array_equal(emap, eb) and np.array_equal(scores, sb), band
+
+
+def test_dec4_tails_saturated_tanh():
+    """vad_tanh = 1 - 2 * rcp(exp(2 v) + 1) in vad_conv3x3_to3_score and vad_dec4_score with pre-activations of about +-60 and a
+    share beyond +-44.4, where exp(2 v) overflows fp32: finite, |recon| <= 1, and test_dec4_fused_kernel's bounds against
+    float64 tanh.  (tests/test_hip_tails.py does the same for the video tail.)
+    Measured on MI355X (two launches / fused): recon 1.3e-05 / 9.2e-06, errmap 6.0e-06 / 3.9e-06, scores 3.1e-08 / 3.1e-08 relative."""
+    import hip_helpers as H
+    n, h, w = 2, 5, 24
+    x_in, wt, bt, bn, w3, b3, frames = _dec4_case(_rng(14), n, h, w)
+    w3, b3 = (w3 * np.float32(50)).astype(np.float32), (b3 * np.float32(50)).astype(np.float32)
+    case = (x_in, wt, bt, bn, w3, b3, frames)
+    act = np.maximum(c_oracle.batchnorm_eval(c_oracle.convt2x2(x_in, wt, bt), *bn), 0)
+    pre = c_oracle.conv2d(act, w3, b3, 3).astype(np.float64)
+    assert (pre > 44.4).mean() > 0.005 and (pre < -44.4).mean() > 0.005 and (np.abs(pre) < 1).mean() > 0.01
+    assert 60 < np.abs(pre).max() < 150
+    ref_recon = np.tanh(pre)
+    ref_emap = ((frames.astype(np.float64) - ref_recon) ** 2).mean(axis=1)
+    ref_scores = ref_emap.mean(axis=(1, 2))
+    for fused in (False, True):
+        recon, emap, scores = _dec4_run(H, case, fused=fused)
+        assert np.isfinite(recon).all() and np.isfinite(emap).all() and np.isfinite(scores).all() and np.abs(recon).max() <= 1.0
+        e_score = np.max(np.abs(scores - ref_scores) / ref_scores)
+        print(f"dec4 saturated fused {fused}: recon {max_abs(recon, ref_recon):.3e} errmap {max_abs(emap, ref_emap):.3e} score rel {e_score:.3e}")
+        assert max_abs(recon, ref_recon) < ATOL and max_abs(emap, ref_emap) < ATOL
+        assert e_score < 1e-5
+        sat = np.abs(pre) > 44.5
+        assert np.array_equal(recon[sat], np.sign(pre[sat]).astype(np.float32))
+
+
+# ---------------------------------------------------------------------------------------------- frame strides
+# Production always strides: the ConvLSTM recurrence runs step t of [B][T] tensors with x_fs = h_prev_fs = h_out_fs = T * dense,
+# and every kernel form rebuilds its per-frame buffer descriptors (whose out-of-range offsets ARE the zero padding) from those
+# strides.  The helpers put NaN between the input frames and a sentinel between the output frames: a read that leaves its frame
+# on a ragged map, or a store that does, cannot agree bit for bit with the dense call on the same data.
+CONV_VARIANTS = (1, 1 | 64, 1 | 128, 1 | 8, 0)
+LAYOUTS = pytest.mark.parametrize("fs", ["FS_PAD", "FS_TIME"])
+
+
+def _each_variant(H, run):
+    """run() under every vad_debug_set_conv_variant value the tests of the kernel forms use."""
+    l = H.hip.lib()
+    try:
+        for bits in CONV_VARIANTS:
+            l.vad_debug_set_conv_variant(bits)
+            run(bits)
+    finally:
+        l.vad_debug_set_conv_variant(1)
+
+
+@LAYOUTS
+@pytest.mark.parametrize("precision", [0, 1])
+@pytest.mark.parametrize("cin,cout,h,w,act,pool", [(32, 32, 18, 22, 2, False), (64, 128, 5, 7, 1, False), (64, 64, 16, 32, 1, True)])
+def test_conv3x3_frame_strides(cin, cout, h, w, act, pool, precision, fs):
+    import hip_helpers as H
+    rng = _rng(cin + cout + h + 3)
+    x = rng.standard_normal((3, cin, h, w)).astype(np.float32)
+    wt, b, bn = _conv_params(rng, cout, cin)
+
+    def run(bits):
+        dense = H.conv3x3(x, wt, b, bn, act, pool)
+        got = H.conv3x3(x, wt, b, bn, act, pool, fs=getattr(H, fs))
+        assert not np.isnan(got).any() and np.array_equal(got, dense), bits
+
+    with _precision(H, precision):
+        _each_variant(H, run)
+
+
+@LAYOUTS
+@pytest.mark.parametrize("cin,cout,h,w,act,pool", [(64, 64, 6, 10, 1, False), (32, 32, 16, 16, 2, True)])
+def test_conv3x3_winograd_frame_strides(cin, cout, h, w, act, pool, fs):
+    import hip_helpers as H
+    rng = _rng(cin + cout + h + 4)
+    x = rng.standard_normal((3, cin, h, w)).astype(np.float32)
+    wt, b, bn = _conv_params(rng, cout, cin)
+    dense = H.conv3x3_wino(x, wt, b, bn, act, pool)
+    got = H.conv3x3_wino(x, wt, b, bn, act, pool, fs=getattr(H, fs))
+    assert not np.isnan(got).any() and np.array_equal(got, dense)
+
+
+@LAYOUTS
+@pytest.mark.parametrize("precision", [0, 1])
+@pytest.mark.parametrize("cin,cout,h,w,act", [(32, 64, 3, 5, 0), (128, 64, 8, 6, 2)])
+def test_convt2x2_frame_strides(cin, cout, h, w, act, precision, fs):
+    import hip_helpers as H
+    rng = _rng(cin + cout + h + 5)
+    x = rng.standard_normal((3, cin, h, w)).astype(np.float32)
+    wt = (rng.standard_normal((cin, cout, 2, 2)) * np.sqrt(1.0 / cin)).astype(np.float32)
+    b = (rng.standard_normal(cout) * 0.1).astype(np.float32)
+    with _precision(H, precision):
+        dense = H.convt2x2(x, wt, b, None, act)
+        got = H.convt2x2(x, wt, b, None, act, fs=getattr(H, fs))
+    assert not np.isnan(got).any() and np.array_equal(got, dense)
+
+
+def _lstm_case(rng, n, cx, hid, h, w):
+    x = rng.standard_normal((n, cx, h, w)).astype(np.float32)
+    wt = (rng.standard_normal((4 * hid, cx + hid, 3, 3)) * np.sqrt(1.0 / ((cx + hid) * 9))).astype(np.float32)
+    b = (rng.standard_normal(4 * hid) * 0.1).astype(np.float32)
+    hp = (rng.standard_normal((n, hid, h, w)) * 0.5).astype(np.float32)
+    cp = rng.standard_normal((n, hid, h, w)).astype(np.float32)
+    return x, hp, cp, wt, b
+
+
+def _stride_kwargs(H, fs, which):
+    return {k: getattr(H, fs) for k in (("x_fs", "h_fs", "out_fs") if which == "all" else (which,))}
+
+
+@LAYOUTS
+@pytest.mark.parametrize("which", ["all", "x_fs", "h_fs", "out_fs"])
+@pytest.mark.parametrize("cx,hid,h,w", [(64, 64, 5, 9), (128, 64, 7, 18)])
+def test_convlstm_step_frame_strides(cx, hid, h, w, which, fs):
+    """x, h_prev and h_out strided at once and one at a time, under every kernel form; c_prev / c_out are dense and may be one
+    buffer."""
+    import hip_helpers as H
+    case = _lstm_case(_rng(cx + hid + h + 6), 3, cx, hid, h, w)
+    kw = _stride_kwargs(H, fs, which)
+
+    def run(bits):
+        dh, dc = H.convlstm_step(*case)
+        gh, gc = H.convlstm_step(*case, **kw)
+        assert not np.isnan(gh).any() and not np.isnan(gc).any()
+        assert np.array_equal(gh, dh) and np.array_equal(gc, dc), bits
+        if which == "all":
+            ah, ac = H.convlstm_step(*case, alias_c=True, **kw)
+            assert np.array_equal(ah, dh) and np.array_equal(ac, dc), bits
+
+    _each_variant(H, run)
+
+
+@LAYOUTS
+@pytest.mark.parametrize("which", ["all", "x_fs", "h_fs", "out_fs"])
+@pytest.mark.parametrize("n", [3, 70])          # two launches (z scratch + pointwise cell) / the cell in the convolution's epilogue
+def test_convlstm_step_winograd_frame_strides(n, which, fs):
+    import hip_helpers as H
+    case = _lstm_case(_rng(n + 7), n, 64, 64, 3, 5)
+    dh, dc = H.convlstm_step_wino(*case)
+    gh, gc = H.convlstm_step_wino(*case, **_stride_kwargs(H, fs, which))
+    assert not np.isnan(gh).any() and not np.isnan(gc).any()
+    assert np.array_equal(gh, dh) and np.array_equal(gc, dc)
