@@ -253,6 +253,18 @@ size_t vad_conv_wgrad_ws_floats(int n, int h, int taps, int cin, int ncols);
  * fp32 split-K partials. */
 int vad_conv_wgrad(const float* a, const float* g, float* dw, float* ws, int n, int h, int w, int cin, int ncols,
                    int taps, int layout, int precision, void* stream);
+/* Which kernel form vad_conv_wgrad runs for these arguments under the current vad_debug_set_wgrad_* switches, the partial slots
+ * (taps*cin*ncols floats each) it writes into ws and its work items (waves or work-groups).  Host arithmetic only: nothing is
+ * launched and no GPU is needed.  VAD_ERR_ARG for arguments vad_conv_wgrad rejects. */
+#define VAD_WGRAD_WAVE_F32 0    /* one wave per 32 x 32 tile, exact fp32 (conv_wgrad_kernel) */
+#define VAD_WGRAD_WAVE_BF16 1   /* the same tiling on bf16 operands, fp32 or bf16 tensors (conv_wgrad_bf16_kernel) */
+#define VAD_WGRAD_WAVE_SPLIT 2  /* the same tiling on split-fp16 operands (conv_wgrad_split_kernel) */
+#define VAD_WGRAD_SPLIT_LDS 3   /* split fp16, LDS-staged work-group tiles, 3x3 layers (conv_wgrad_split_lds_kernel) */
+#define VAD_WGRAD_RING 4        /* 3x3 layers, every operand row staged once per work-group (conv_wgrad_ring_kernel) */
+#define VAD_WGRAD_PAIRS 5       /* bf16 tensors, paired channels, 64 x 64 wave tiles (conv_wgrad_bf16x2_kernel) */
+#define VAD_WGRAD_BF16_LDS 6    /* bf16 tensors, LDS-staged work-group tiles (conv_wgrad_bf16_lds_kernel) */
+int vad_conv_wgrad_plan(int precision, int n, int h, int w, int cin, int ncols, int taps, int* form, long long* slots,
+                        long long* items);
 /* First-layer weight gradient: x NCHW [n,3,h,w], g [n,h,w,cout] -> dw OIHW (cout,3,3,3). */
 size_t vad_conv_c3_wgrad_ws_floats(int n, int h, int cout);
 int vad_conv_c3_wgrad(const float* x_nchw, const float* g, float* dw, float* ws, int n, int h, int w, int cout,
@@ -307,7 +319,7 @@ int vad_lstm_gates_fwd_t(void* z, int io16, const float* c_prev, float* c_out, v
 int vad_lstm_gates_bwd_t(const void* gates, int io16, const float* c_prev, const float* c, const void* dh1, long long dh1_fs,
                          int dh1_ps, const void* dh2, long long dh2_fs, int dh2_ps, const float* dc_next, void* dz,
                          float* dc_prev, int nb, int hw, int hid, void* stream);
-/* Routed first-layer weight gradient of the bf16-tensor step (round 4; csrc/train_ops.hip conv_c3_wgrad_routed_kernel): BatchNorm's
+/* Routed first-layer weight gradient of the bf16-tensor step (round 4; csrc/wgrad.hip conv_c3_wgrad_routed_kernel): BatchNorm's
  * backward pass A with `codes` != NULL writes one routing byte per pooled element (argmax position | sign << 2) instead of running
  * pass B; vad_conv_c3_wgrad_routed then forms dW of Conv2d(3 -> 32) + BatchNorm + LeakyReLU + MaxPool2 from the POOLED gradient
  * d(out) ([n, h/2, w/2, 32]: bf16 with io16, bf16 MFMAs throughout; else fp32, T1 on the exact-fp32 MFMA and S in split-fp16), the codes, the input planes and the layer's own weights / statistics (dW = sc (T1 - k1 SX - k2
@@ -374,7 +386,7 @@ size_t vad_debug_train_decisions_used(void);
 /* A/B: 0 = the weight gradients of the bf16-tensor mode use the one-channel-per-lane kernel everywhere; 1 = the paired-channel
  * kernel (dword loads, 64 x 64 wave tiles) where cin and ncols are multiples of 64; 2 = its LDS-staged work-group
  * form where ncols is a multiple of 128; 3 (default) = the row-ring kernel for the 3x3 layers with ncols % 64 == 0 and cin % 64 == 0
- * or cin == 32 (every operand row staged once per work-group, csrc/train_ops.hip), 2 elsewhere. */
+ * or cin == 32 (every operand row staged once per work-group, csrc/wgrad.hip), 2 elsewhere. */
 int vad_debug_set_wgrad_pairs(int on);
 /* A/B: 0 = VAD_PREC_SPLIT weight gradients on the exact-fp32 kernel (rounds 2-3); 1 = the per-lane split-fp16 kernel; 2 = its
  * LDS-staged form for the 3x3 layers it takes; 3 (default) = the row-ring kernel for those layers. */

@@ -197,7 +197,7 @@ def test_conv1x1_on_bf16_tensors(vad, npix, cin, cout):
 @pytest.mark.parametrize("n,h,w", [(2, 16, 16), (3, 32, 48), (5, 12, 80), (2, 64, 256), (1, 8, 272), (1, 4, 768)])
 def test_routed_first_layer_weight_gradient(vad, n, h, w):
     """Round 4: the bf16-tensor step forms the first layer's weight gradient from the POOLED gradient, one routing byte per pooled
-    element and the Gram matrix of the input patches (csrc/train_ops.hip conv_c3_wgrad_routed_kernel) instead of writing the dense
+    element and the Gram matrix of the input patches (csrc/wgrad.hip conv_c3_wgrad_routed_kernel) instead of writing the dense
     conv-output gradient and reading it back.  Against a float64 evaluation of the same layer (Conv2d(3->32) on bf16 operands ->
     BatchNorm with batch statistics -> LeakyReLU(0.2) -> MaxPool2, every decision taken from the stored bf16 conv output as the
     kernels take it): the routed form and the form it

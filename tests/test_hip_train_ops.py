@@ -237,7 +237,7 @@ def test_convt2x2_weight_and_data_gradients(vad, n, h, w, cin, cout, precision):
 
 @pytest.mark.parametrize("n,h,w", [(2, 16, 16), (3, 32, 48), (5, 12, 80), (2, 64, 256), (1, 8, 272), (1, 4, 768)])
 def test_routed_first_layer_weight_gradient_fp32(vad, n, h, w):
-    """fp32 form of the routed first-layer weight gradient (csrc/train_ops.hip conv_c3_wgrad_routed_f32_kernel; the bf16 form:
+    """fp32 form of the routed first-layer weight gradient (csrc/wgrad.hip conv_c3_wgrad_routed_f32_kernel; the bf16 form:
     tests/test_hip_train_bf16.py): dW of Conv2d(3->32) + BatchNorm(batch statistics) + LeakyReLU(0.2) + MaxPool2 from the POOLED
     gradient, one routing byte per pooled element and the Gram matrix of the input patches, against a float64 evaluation that
     takes every decision from the stored fp32 conv output as the kernels do - and against the form it replaces (pass B + the plain
@@ -334,6 +334,28 @@ def test_split_weight_gradient_kernel_forms(vad, n, h, w, cin, ncols, taps):
         l.vad_debug_set_wgrad_ring_f32(1)
     assert torch.equal(dwp.cpu(), torch.from_numpy(out[0]))
     _close(dwr.cpu().numpy(), out[0], 2e-6, "exact row-ring kernel")
+
+
+def test_weight_gradients_are_bit_identical_to_the_recorded_digests(vad):
+    """Every kernel form of vad_conv_wgrad (csrc/wgrad.hip) that vad_conv_wgrad_plan reports for six small layers in the four
+    precisions, and the plain and routed first-layer forms: sha256 of dW on seeded inputs (tests/wgrad_identity.py) against the
+    digests the library produced before dispatch and workspace sizing were derived from one launch plan.  Partial slots and a
+    fixed-order reduce, no atomics: any change of kernel, grid, split-K or summation order shows as another digest."""
+    import json
+
+    import wgrad_identity as WI
+    from conftest import GOLDEN
+    l = vad.hip.lib()
+    want = json.loads((GOLDEN / "wgrad_digests.json").read_text())
+    cases = WI.cases(l)
+    keys = [WI.key(*c) for c in cases]
+    assert {c[2] for c in cases} == set(range(len(WI.FORMS)))          # the shapes reach every form
+    inputs = {shape: WI.wgrad_inputs(shape) for shape in WI.SHAPES}
+    got = {k: WI.wgrad_digest(l, shape, precision, sw, inputs[shape]) for k, (shape, precision, _, sw) in zip(keys, cases)}
+    for n, h, w in WI.C3_SHAPES:
+        got.update(WI.c3_digests(l, n, h, w))
+    assert sorted(got) == sorted(want)
+    assert {k: v for k, v in got.items() if want[k] != v} == {}
 
 
 def _check_convt2x2_gradients(vad, n, h, w, cin, cout, precision):

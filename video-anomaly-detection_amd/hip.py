@@ -16,7 +16,7 @@ PKG_DIR = Path(__file__).resolve().parent
 REPO_DIR = PKG_DIR.parent
 CSRC = PKG_DIR / "csrc"
 LIB_PATH = Path(os.environ.get("VAD_LIB", PKG_DIR / "libvad_hip.so"))
-SOURCES = ["conv_mfma.hip", "conv_wino.hip", "dec4_fused.hip", "tail.hip", "wide_io.hip", "state_io.hip", "resize_u8.hip", "ssim.hip", "train_ops.hip", "train_step.hip", "train_step_img.hip", "vad_api.hip", "pack.cpp"]
+SOURCES = ["conv_mfma.hip", "conv_wino.hip", "dec4_fused.hip", "tail.hip", "wide_io.hip", "state_io.hip", "resize_u8.hip", "ssim.hip", "train_ops.hip", "wgrad.hip", "train_step.hip", "train_step_img.hip", "vad_api.hip", "pack.cpp"]
 
 VAD_OK = 0
 ABI_VERSION = 3
@@ -153,6 +153,7 @@ SIGNATURES = {
     "vad_lstm_gates_bwd": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _vp, _ll, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "vad_conv_wgrad_ws_floats": (_sz, [_i, _i, _i, _i, _i]),
     "vad_conv_wgrad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "vad_conv_wgrad_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_ll), C.POINTER(_ll)]),
     "vad_conv_c3_wgrad_ws_floats": (_sz, [_i, _i, _i]),
     "vad_conv_c3_wgrad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "vad_convt_to3_mse_ws_floats": (_sz, [_i, _i, _i]),
