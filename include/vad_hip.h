@@ -5,6 +5,8 @@
  * (paths relative to the reference root).  Everything is plain pointers and sizes; `stream` is a
  * hipStream_t passed as void*.  All device pointers are fp32 unless stated.  Calls are
  * asynchronous on `stream`, never allocate and never synchronise (except vad_prof_read).
+ * Every `workspace` / `ws` argument is caller-owned device scratch of the size the matching size function reports: its contents
+ * on entry are irrelevant, and no byte outside [ws, ws + size) is read or written.
  *
  * Return value: VAD_OK or a negative VAD_ERR_*; vad_last_error() gives the text.
  */

@@ -311,3 +311,108 @@ def score_finalize(parts, h2, w2, t=1, want_frame=True, want_seq=True):
     if (not want_frame and not np.isnan(fs).all()) or (not want_seq and not np.isnan(sq).all()):
         raise AssertionError("score_finalize wrote an output it was given NULL for")
     return fs if want_frame else None, sq if want_seq else None
+
+
+# ------------------------------------------------------------------------------ guarded, poisoned workspaces
+#: bytes of guard on either side of an arena's body (a multiple of 256: the body keeps the allocation's alignment)
+GUARD_BYTES = 1 << 20
+GUARD_BYTE = 0xA5
+#: dirt this close to a guard's outer end means the stray access may reach beyond memory the test owns
+GUARD_EDGE = 4096
+#: body fills, the same in every element type: 0x00 = zero ("assumed cleared" hides here), 0xFF = NaN in fp32 and bf16, 0x7F =
+#: 3.39e38, the largest finite magnitudes (max / ReLU / max-pool swallow a NaN operand, never a huge finite one)
+POISONS = (0x00, 0xFF, 0x7F)
+
+
+class GuardedArena:
+    """One uint8 device allocation `lead | body | tail`: `body` is EXACTLY `nbytes` (what a size function reported, no rounding),
+    256-B aligned and filled with `poison`; `lead` and `tail` are GUARD_BYTES of GUARD_BYTE each.  `check()` asserts that
+    the guards still hold it: a write before or behind the workspace lands in memory the test owns and is reported."""
+
+    def __init__(self, nbytes, poison=0xFF, device="cuda"):
+        self.nbytes = int(nbytes)
+        assert self.nbytes >= 0 and GUARD_BYTES % 256 == 0
+        self.buf = torch.empty(2 * GUARD_BYTES + self.nbytes, dtype=torch.uint8, device=device)
+        assert self.buf.data_ptr() % 256 == 0, "the allocator no longer returns 256-B aligned blocks"
+        self.lead = self.buf[:GUARD_BYTES]
+        self.body = self.buf[GUARD_BYTES:GUARD_BYTES + self.nbytes]
+        self.tail = self.buf[GUARD_BYTES + self.nbytes:]
+        self.lead.fill_(GUARD_BYTE)
+        self.tail.fill_(GUARD_BYTE)
+        self.poison(poison)
+
+    def poison(self, byte):
+        self.fill = int(byte)
+        self.body.fill_(self.fill)
+        return self
+
+    def floats(self):
+        """The body as fp32 (nbytes a multiple of 4)."""
+        return self.body.view(torch.float32)
+
+    def ptr(self):
+        return self.body.data_ptr() if self.nbytes else None
+
+    def still_poison(self):
+        """Has nothing written the body since it was filled (a refused call launches nothing)?"""
+        torch.cuda.synchronize()
+        return bool((self.body == self.fill).all())
+
+    def check(self, what="workspace"):
+        torch.cuda.synchronize()
+        found = []
+        for name, guard in (("lead", self.lead), ("tail", self.tail)):
+            dirty = (guard != GUARD_BYTE).nonzero().flatten()
+            if dirty.numel() == 0:
+                continue
+            lo, hi = int(dirty[0]), int(dirty[-1])
+            if name == "lead":      # offsets relative to the body's first byte (negative: in front of it)
+                msg = f"bytes {lo - GUARD_BYTES}..{hi - GUARD_BYTES} relative to the start of the {self.nbytes}-byte body were written"
+                edge = lo < GUARD_EDGE
+            else:                   # offsets relative to the body's end (0 = the first byte behind it)
+                msg = f"bytes +{lo}..+{hi} behind the end of the {self.nbytes}-byte body were written"
+                edge = hi >= GUARD_BYTES - GUARD_EDGE
+            if edge:
+                msg += f" - the dirt reaches the outer {GUARD_EDGE} bytes of the guard: the overrun may be larger than the guard"
+            found.append(f"{what}: {int(dirty.numel())} guard {msg}")
+        assert not found, "; ".join(found)
+
+
+class ArenaPool:
+    """The arenas one test hands out: `floats(n)` / `bytes_(n)` make a fresh arena per call (layer tests), `shared(nbytes)` keeps
+    ONE arena per distinct size alive (the models' allocation points: a captured graph's workspace pointer stays valid) and fills
+    it again on every request unless `refill` is off.  `check()` checks every arena handed out so far."""
+
+    def __init__(self, poison=0xFF):
+        self.fill, self.refill = poison, True
+        self.arenas, self.by_size = [], {}
+
+    def new(self, nbytes, what="workspace"):
+        a = GuardedArena(nbytes, self.fill)
+        self.arenas.append((what, a))
+        return a
+
+    def floats(self, n):
+        return self.new(4 * max(int(n), 1), f"scratch of {int(n)} floats").floats()
+
+    def shared(self, nbytes):
+        nbytes = int(nbytes)
+        if nbytes not in self.by_size:
+            self.by_size[nbytes] = self.new(nbytes, f"workspace of {nbytes} bytes")
+        elif self.refill:
+            self.by_size[nbytes].poison(self.fill)
+        return self.by_size[nbytes].body
+
+    def poison(self, byte):
+        self.fill = byte
+        for _, a in self.arenas:
+            a.poison(byte)
+
+    def check(self):
+        for what, a in self.arenas:
+            a.check(what)
+
+
+def same_bits(a, b):
+    """Bit identity of two tensors (NaN payloads included)."""
+    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(a.contiguous().reshape(-1).view(torch.uint8), b.contiguous().reshape(-1).view(torch.uint8))

@@ -21,8 +21,23 @@ def _rng(seed):
     return np.random.default_rng(seed)
 
 
+_ARENAS = None
+
+
+@pytest.fixture(autouse=True)
+def _guarded_scratch():
+    """Every `_ws` buffer of a test is the body of a `hip_helpers.GuardedArena`: exactly the requested size, NaN on entry (0xFF
+    bytes), between two guards that must be untouched when the test ends."""
+    import hip_helpers as H
+    global _ARENAS
+    _ARENAS = H.ArenaPool(0xFF)
+    yield
+    pool, _ARENAS = _ARENAS, None
+    pool.check()
+
+
 def _ws(n):
-    return torch.empty(max(int(n), 1), dtype=torch.float32, device="cuda")
+    return _ARENAS.floats(n)
 
 
 def _rep(a):

@@ -32,8 +32,23 @@ def _close(got, ref, rtol=1e-4, what=""):
     assert np.isfinite(got).all() and err < rtol, f"{what}: max err {err:.3e} of scale {scale:.3e}"
 
 
+_ARENAS = None
+
+
+@pytest.fixture(autouse=True)
+def _guarded_scratch():
+    """Every `_ws` buffer of a test is the body of a `hip_helpers.GuardedArena`: exactly the requested size, NaN on entry (0xFF
+    bytes), between two guards that must be untouched when the test ends."""
+    import hip_helpers as H
+    global _ARENAS
+    _ARENAS = H.ArenaPool(0xFF)
+    yield
+    pool, _ARENAS = _ARENAS, None
+    pool.check()
+
+
 def _ws(n):
-    return torch.empty(max(int(n), 1), dtype=torch.float32, device="cuda")
+    return _ARENAS.floats(n)
 
 
 @pytest.mark.parametrize("n,h,w,c,act,pool", [(3, 8, 12, 32, 1, 1), (2, 6, 6, 64, 2, 0), (5, 4, 4, 128, 1, 1),
