@@ -11,11 +11,14 @@ accuracy tests of the other files then hold for any workspace contents.
 The models' and trainers' only allocation points (`_HipScorer.workspace`, `_FlatTrainer._ensure_ws`) are monkeypatched per test
 to hand out arena bodies; criteria, resize and the refusals go through the C ABI directly.  Shapes are the smallest at which
 the carving of a workspace can still disagree with its size function."""
+import hashlib
+import json
+
 import numpy as np
 import pytest
 import torch
 
-from conftest import load_synthetic
+from conftest import GOLDEN, load_synthetic
 
 pytestmark = pytest.mark.gpu
 
@@ -50,12 +53,23 @@ def _finite(name, t, label):
         assert bool(torch.isfinite(t).all()), f"{label}: {name} of the plain run is not finite"
 
 
-def _contract(vad, call, label, plain=None):
-    """`call()` -> nested tensors.  Plain run, then the three fills on guarded arenas: same bits, clean guards."""
+def _same_as_recorded(label, plain):
+    """Scoring has no atomics: every output of a scoring case is the bits an MI355X gave before the workspaces were laid out by
+    one carve each (tests/golden/scoring_digests.json names the commit)."""
+    want = json.loads((GOLDEN / "scoring_digests.json").read_text())["sha256"]
+    got = {k: hashlib.sha256(v.detach().cpu().contiguous().view(torch.uint8).numpy().tobytes()).hexdigest() for k, v in plain.items()}
+    assert got == want[label], f"{label}: {[k for k in got if got[k] != want[label].get(k)]} are not the recorded bits"
+
+
+def _contract(vad, call, label, plain=None, recorded=True):
+    """`call()` -> nested tensors.  Plain run, then the three fills on guarded arenas: same bits, clean guards.  The plain run of
+    a scoring case (`plain` not given) is also compared with its recorded digests."""
     import hip_helpers as H
     if plain is None:
         with torch.no_grad():
             plain = {k: v.clone() for k, v in _flat(call()).items()}
+        if recorded:
+            _same_as_recorded(label, plain)
     torch.cuda.synchronize()
     assert plain, label
     for k, v in plain.items():
@@ -163,7 +177,7 @@ def test_image_scoring_workspace_wide_latent(vad):
     m = vad.ConvAutoencoder(latent_dim=2049).cuda().eval()          # (as initialised: a synthetic state of 38 M values takes seconds)
     m.chunk = 2
     x = torch.from_numpy(vad.synth.frames(78, 0, 3, 3, 16, 16)).cuda()
-    _contract(vad, _img_call(m, x, "all"), "image latent 2049 16x16")
+    _contract(vad, _img_call(m, x, "all"), "image latent 2049 16x16", recorded=False)       # (weights as torch initialises them)
 
 
 # ------------------------------------------------------------------------------ video scoring

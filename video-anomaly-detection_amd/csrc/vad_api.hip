@@ -120,7 +120,37 @@ extern "C" int vad_graph_destroy(void* exec) {
 
 static std::atomic<int> g_vad_tail_group{0};   // debug: frames per dec4.0 -> tail sub-group (0 = the whole launch group)
 extern "C" int vad_debug_set_tail_group(int frames) { g_vad_tail_group = frames; return VAD_OK; }
-#define REQ_PREC(who) VAD_REQUIRE(precision == VAD_PREC_FP32 || precision == VAD_PREC_SPLIT || precision == VAD_PREC_WINO, who ": precision=%d must be VAD_PREC_FP32 (0), VAD_PREC_SPLIT (1) or VAD_PREC_WINO (4)", precision)
+
+// ------------------------------------------------------------------------------ argument checks of the scoring entry points
+// `who` is the entry point's name in the message.  The size functions use the predicates and return 0 silently.
+static bool frame_shape_ok(int h, int w) { return h > 0 && w > 0 && h % 16 == 0 && w % 16 == 0; }
+static bool in_ch_ok(int in_ch) { return in_ch >= 3 && in_ch <= VAD_MAX_IN_CH; }
+static bool aligned(const void* p, uintptr_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
+
+static int req_frame_shape(const char* who, int h, int w, const char* why) {
+    VAD_REQUIRE(frame_shape_ok(h, w), "%s: H=%d W=%d must be positive multiples of 16%s", who, h, w, why);
+    return VAD_OK;
+}
+static int req_precision(const char* who, int p) {
+    VAD_REQUIRE(p == VAD_PREC_FP32 || p == VAD_PREC_SPLIT || p == VAD_PREC_WINO, "%s: precision=%d must be VAD_PREC_FP32 (0), VAD_PREC_SPLIT (1) or VAD_PREC_WINO (4)", who, p);
+    return VAD_OK;
+}
+static int req_input(const char* who, int x_format, int in_ch) {
+    VAD_REQUIRE(x_format == VAD_X_F32_NCHW || x_format == VAD_X_U8_NHWC, "%s: unknown input format %d", who, x_format);
+    VAD_REQUIRE(in_ch_ok(in_ch), "%s: in_channels=%d out of range [3,%d]", who, in_ch, VAD_MAX_IN_CH);
+    VAD_REQUIRE(in_ch == 3 || x_format == VAD_X_F32_NCHW, "%s: uint8 frames are 3-channel images (in_channels=%d)", who, in_ch);
+    return VAD_OK;
+}
+// the caller's workspace holds what the carve needs, and it and the weight blob are aligned
+static int req_workspace(const char* who, const void* ws, size_t ws_bytes, size_t need, const void* packed) {
+    if (ws_bytes < need) return vad_fail(VAD_ERR_WS, "%s: workspace %zu B < required %zu B", who, ws_bytes, need);
+    VAD_REQUIRE(aligned(ws, 256) && aligned(packed, 16), "%s: workspace must be 256-B and weights 16-B aligned", who);
+    return VAD_OK;
+}
+static int req_state_aligned(const char* who, const float* state_in, const float* state_out) {
+    VAD_REQUIRE(aligned(state_in, 16) && aligned(state_out, 16), "%s: state blobs must be 16-B aligned", who);
+    return VAD_OK;
+}
 
 // A 3x3 convolution behind the first layer in the model's arithmetic mode: VAD_PREC_WINO blobs hold the Winograd form of these
 // layers (csrc/conv_wino.hip); every other kernel of such a model runs the VAD_PREC_FP32 arithmetic (`bprec`).
@@ -130,7 +160,13 @@ static int conv3x3_mode(const float* in, const float* w, const float* bias, floa
     return vad_conv3x3(in, 0, w, bias, out, 0, n, h, wd, cin, cout, act, pool, precision, s);
 }
 
-static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+// A workspace is laid out ONCE, by a function that takes pieces from a Carve in order: over base == NULL it only counts, over the
+// caller's workspace it hands out the pointers, and either way `off` ends at the size.  Every piece is rounded up to 256 B.
+struct Carve {
+    char* base;
+    size_t off;
+    float* take(size_t bytes) { float* p = base ? (float*)(base + off) : nullptr; off += (bytes + 255) & ~(size_t)255; return p; }
+};
 
 // ------------------------------------------------------------------------------ image model
 static size_t img_act_floats(int h, int w, int latent) {
@@ -148,17 +184,24 @@ static size_t img_partials(int h, int w) {
 static std::atomic<int> g_vad_dec4_fused{1};   // debug / A-B: 0 = dec4.0 and the scoring tail as two launches (the round-2 path)
 extern "C" int vad_debug_set_dec4_fused(int on) { g_vad_dec4_fused = on; return VAD_OK; }
 
+// two ping-pong activation buffers and the partial sums, for `chunk` frames
+struct ImgWs { float *A, *B, *parts; size_t bytes; };
+static ImgWs img_carve(void* ws, int chunk, int h, int w, int latent_real) {
+    Carve c{(char*)ws, 0};
+    const size_t act = sizeof(float) * chunk * img_act_floats(h, w, vad_img_latent_p(latent_real));
+    ImgWs z{c.take(act), c.take(act), c.take(sizeof(float) * chunk * img_partials(h, w)), 0};      // (a braced list is evaluated in order)
+    z.bytes = c.off;
+    return z;
+}
+
 extern "C" size_t vad_img_workspace_bytes_c(int chunk, int h, int w, int latent, int in_ch) {
-    if (in_ch < 3 || in_ch > VAD_MAX_IN_CH) return 0;
+    if (!in_ch_ok(in_ch)) return 0;
     return vad_img_workspace_bytes(chunk, h, w, latent);          // (the planes of a wide model pad to 32 channels: the size of the largest map either way)
 }
 
 extern "C" size_t vad_img_workspace_bytes(int chunk, int h, int w, int latent) {
-    if (chunk <= 0 || h <= 0 || w <= 0 || h % 16 || w % 16 || latent <= 0 || latent > VAD_MAX_WIDTH) return 0;
-    latent = vad_img_latent_p(latent);
-    const size_t act = up256(sizeof(float) * chunk * img_act_floats(h, w, latent));
-    const size_t parts = up256(sizeof(float) * chunk * img_partials(h, w));
-    return 2 * act + parts;
+    if (chunk <= 0 || !frame_shape_ok(h, w) || latent <= 0 || latent > VAD_MAX_WIDTH) return 0;
+    return img_carve(nullptr, chunk, h, w, latent).bytes;
 }
 
 extern "C" int vad_img_score(const float* x, long long b, int h, int w, int latent, const float* packed,
@@ -178,29 +221,22 @@ extern "C" int vad_img_score_c(const void* xv, int x_format, int precision, int 
                                const float* packed, void* ws, size_t ws_bytes, int chunk, float* scores, float* errmap,
                                float* recon, float* latent_out, void* stream) {
     VAD_REQUIRE(xv && packed && ws, "img_score: null pointer");
-    REQ_PREC("img_score");
-    VAD_REQUIRE(x_format == VAD_X_F32_NCHW || x_format == VAD_X_U8_NHWC, "img_score: unknown input format %d", x_format);
-    VAD_REQUIRE(in_ch >= 3 && in_ch <= VAD_MAX_IN_CH, "img_score: in_channels=%d out of range [3,%d]", in_ch, VAD_MAX_IN_CH);
-    VAD_REQUIRE(in_ch == 3 || x_format == VAD_X_F32_NCHW, "img_score: uint8 frames are 3-channel images (in_channels=%d)", in_ch);
+    TRY(req_precision("img_score", precision));
+    TRY(req_input("img_score", x_format, in_ch));
     const size_t xelem = x_format == VAD_X_U8_NHWC ? 1 : 4;
     const char* x = (const char*)xv;
     VAD_REQUIRE(b > 0 && chunk > 0, "img_score: batch=%lld chunk=%d must be positive", b, chunk);
-    VAD_REQUIRE(h > 0 && w > 0 && h % 16 == 0 && w % 16 == 0,
-                "img_score: H=%d W=%d must be positive multiples of 16 (4 MaxPool2d(2) stages)", h, w);
+    TRY(req_frame_shape("img_score", h, w, " (4 MaxPool2d(2) stages)"));
     VAD_REQUIRE(latent_real > 0 && latent_real <= VAD_MAX_WIDTH, "img_score: latent_dim=%d out of range [1,%d]", latent_real, VAD_MAX_WIDTH);
     VAD_REQUIRE(scores || errmap || recon || latent_out, "img_score: no output requested");
-    const size_t need = vad_img_workspace_bytes(chunk, h, w, latent_real);
-    if (ws_bytes < need) return vad_fail(VAD_ERR_WS, "img_score: workspace %zu B < required %zu B", ws_bytes, need);
-    VAD_REQUIRE(((uintptr_t)ws & 255) == 0 && ((uintptr_t)packed & 15) == 0, "img_score: workspace must be 256-B and weights 16-B aligned");
+    const ImgWs Z = img_carve(ws, chunk, h, w, latent_real);
+    TRY(req_workspace("img_score", ws, ws_bytes, Z.bytes, packed));
 
     hipStream_t s = (hipStream_t)stream;
     const ImgLayout L = img_layout(in_ch, latent_real);
     const int latent = L.latent_p;                  // the width the kernels see (zero-padded to a multiple of 32, vad_layout.h)
     const int wide = L.wide;                        // in_channels > 3: generic first / last layers over planes padded to `wide` channels
-    const size_t act = up256(sizeof(float) * chunk * img_act_floats(h, w, latent));
-    float* A = (float*)ws;
-    float* B = (float*)((char*)ws + act);
-    float* parts = (float*)((char*)ws + 2 * act);
+    float *const A = Z.A, *const B = Z.B, *const parts = Z.parts;
     const int nparts_tail = vad_score_partials(0, h, w);
     const bool need_decoder = scores || errmap || recon;
     const int ch[5] = {3, 32, 64, 128, latent};
@@ -299,33 +335,9 @@ extern "C" int vad_img_score_c(const void* xv, int x_format, int precision, int 
 // c's frame t straight from that shared feature buffer (its state still restarts from zero per window, as in
 // models/video_autoencoder.py:144-145).
 namespace {
-struct VidWs {
-    size_t act, enc, hseq, cst, proj, parts, zx0, zxl, zw, total;
-};
 // work-groups of one ConvLSTM step in the large (32x32x2) tiling: below one per CU the layers run as a wavefront on helper
 // streams and the steps' x halves are computed ahead of the recurrence
 long long vid_lstm_groups(int nc, int h16, int w16, int hid) { return (long long)nc * ((w16 + 15) / 16) * ((h16 + 3) / 4) * (hid / 64); }
-VidWs vid_ws(int chunk, int t, int cs, int h, int w, int latent_real, int hid_real, int layers, int in_ch) {
-    VidWs z{};
-    const bool wide = in_ch > 3;
-    const int latent = vad_vid_latent_p(latent_real, hid_real), hid = vad_vid_hid_p(latent_real, hid_real);
-    const size_t n = (size_t)chunk * t, nf = (size_t)(chunk - 1) * cs + t, p16 = (size_t)(h / 16) * (w / 16);
-    const size_t nmax = n > nf ? n : nf;
-    z.act = up256(sizeof(float) * nmax * (size_t)h * w * (wide ? 32 : 8));       // [frames, H/2, W/2, 32]; wide models: [frames, H, W, 32] padded planes
-    z.enc = up256(sizeof(float) * nf * p16 * latent);
-    z.hseq = up256(sizeof(float) * n * p16 * hid);
-    z.cst = up256(sizeof(float) * (size_t)chunk * p16 * hid);
-    z.proj = (hid_real != latent_real) ? up256(sizeof(float) * n * p16 * latent) : 0;
-    z.parts = up256(sizeof(float) * n * (size_t)(wide ? vad_wide_score_partials(h, w) : vad_score_partials(1, h, w)));
-    // small launch groups: bias + x half of every step's gate pre-activations, [frames][h/16][w/16][4*hid] - layer 0 per SOURCE
-    // frame (overlapping windows share them), the layers above per (clip, t)
-    const bool small = vid_lstm_groups(chunk, h / 16, w / 16, hid) < 256;
-    z.zx0 = small ? up256(sizeof(float) * nf * p16 * 4 * hid) : 0;
-    z.zxl = small ? up256(sizeof(float) * n * p16 * 4 * hid) : 0;
-    z.zw = up256(sizeof(float) * (size_t)chunk * p16 * 4 * hid);   // VAD_PREC_WINO: one step's gate pre-activations (vad_convlstm_step_wino)
-    z.total = 2 * z.act + z.enc + (size_t)layers * (z.hseq + z.cst + z.zw) + z.proj + z.parts + z.zx0 + (size_t)(layers - 1) * z.zxl;   // h sequence + cell state (+ z) per layer
-    return z;
-}
 
 // Helper streams for the ConvLSTM layer wavefront (small batches): layer l runs on side stream l-1 and step t of layer l
 // waits only for step t of layer l-1, so layer 1 step t overlaps layer 0 step t+1 (the reference's loop is strictly
@@ -381,150 +393,156 @@ struct LstmRun {
     bool wino;                 // the blob holds Winograd-form gate weights where both sources have one width
 };
 
+// The ConvLSTM buffers of launch groups of nc clips x t steps on a gh x gw grid, in workspace order: the h sequences of the first
+// `hs_in_ws` layers (the others live in the caller's buffer), a cell state per layer, whatever `between` takes, then - small launch
+// groups only - bias + x half of every step's gate pre-activations, [frames][gh][gw][4*hid]: layer 0 per SOURCE frame (nf0 of
+// them: overlapping windows share them), the layers above per (clip, t); last one step's gate pre-activations per layer
+// (VAD_PREC_WINO, vad_convlstm_step_wino: the layers of a small launch group run concurrently).
+template <class Between>
+void lstm_carve(Carve& c, LstmRun& R, int nc, int t, size_t nf0, int gh, int gw, int hid, int layers, int hs_in_ws, Between between) {
+    const size_t n = (size_t)nc * t, p = (size_t)gh * gw;
+    for (int l = 0; l < hs_in_ws; ++l) R.HS[l] = c.take(sizeof(float) * n * p * hid);
+    for (int l = 0; l < layers; ++l) R.CS[l] = c.take(sizeof(float) * (size_t)nc * p * hid);
+    between();
+    if (vid_lstm_groups(nc, gh, gw, hid) < 256) {
+        R.ZX[0] = c.take(sizeof(float) * nf0 * p * 4 * hid);
+        for (int l = 1; l < layers; ++l) R.ZX[l] = c.take(sizeof(float) * n * p * 4 * hid);
+    }
+    for (int l = 0; l < layers; ++l) R.ZW[l] = c.take(sizeof(float) * (size_t)nc * p * 4 * hid);
+}
+
 int lstm_rollout(const LstmRun& R, hipStream_t s) {
-    const float* E = R.x;
-    float* const* HS = R.HS; float* const* CS = R.CS; float* const* ZX = R.ZX; float* const* ZW = R.ZW;
-    const int nc = R.nc, t = R.t, cs = R.cs, nf = R.nf_x, h16 = R.h16, w16 = R.w16, latent = R.cin, hid = R.hid, layers = R.layers;
-    const int precision = R.precision;
-    const bool wino = R.wino;
-    const long long fs_lat = R.fs_x, fs_hid = (long long)h16 * w16 * hid;
-#define W_(i) (R.W[(i) - 4])
-#define B_(i) (R.B[(i) - 4])
-    {
-        // Step (l, t) needs (l, t-1) and (l-1, t) only.
-        const long long fs_zx = (long long)h16 * w16 * 4 * hid;
-        // x halves ahead of the recurrence (small launch groups, exact fp32): a step's accumulator chain runs over the x chunks
-        // first and the h chunks second, so bias + x half can be computed for ALL steps of layer 0 in one batched convolution
-        // (per source frame: overlapping windows share it) and per step for the layers above, stored as fp32 and resumed by
-        // the step kernel - bit-identical, and the serial K loop of a step halves (models/video_autoencoder.py:67-70 multiplies
-        // cat([x, h]) inside the recurrence).
+    const int nc = R.nc, t = R.t, h16 = R.h16, w16 = R.w16, hid = R.hid, layers = R.layers;
+    const long long fs_hid = (long long)h16 * w16 * hid, fs_zx = 4 * fs_hid;
+    // x halves ahead of the recurrence (small launch groups, exact fp32): a step's accumulator chain runs over the x chunks
+    // first and the h chunks second, so bias + x half can be computed for ALL steps of layer 0 in one batched convolution
+    // (per source frame: overlapping windows share it) and per step for the layers above, stored as fp32 and resumed by
+    // the step kernel - bit-identical, and the serial K loop of a step halves (models/video_autoencoder.py:67-70 multiplies
+    // cat([x, h]) inside the recurrence).
+    const bool hoist = !R.wino && R.precision == VAD_PREC_FP32 && R.ZX[0] && vad_convlstm_hoist_ok();
+    // Large launch groups fill the chip with one step: layers outer, time inner on the caller's stream (the reference's
+    // order).  Small ones (the reference's batch sizes; a step is then one wave's serial K loop on a fraction of the
+    // CUs) run the layers as a wavefront on helper streams: step (l, t) needs (l, t-1) and (l-1, t) only.
+    const int wf = g_vad_lstm_wavefront.load(std::memory_order_relaxed);
+    const bool wavefront = layers > 1 && ((vid_lstm_groups(nc, h16, w16, hid) < 256 && wf) || wf == 2);
+    // per-step x halves of the layers above 0 (a helper-stream launch and two event hops per step) pay while a step is a
+    // long serial K loop; with the gate-split kernel (one window: ~11 us per step) they cost more than they save - measured
+    // 0.78 -> 0.70 ms for one 16-frame window, 1.05 -> 0.97 for two clips - so those steps run their whole K loop
+    const bool hoist_upper = hoist && !(wavefront && vad_convlstm_gate_wins(nc, h16, w16, hid));
+
+    auto lstm_step = [&](int l, int ti, hipStream_t st) -> int {
+        const float* xin_l = l ? R.HS[l - 1] : R.x;
+        const long long fs_in = l ? fs_hid : R.fs_x;
+        const long long clip_in = l ? t * fs_hid : R.clip_x;                      // layer 0 reads the shared features
+        // h(t-1), c(t-1): the previous step's, or at step 0 the caller's initial state (NULL = zero)
+        const float* hp = ti ? R.HS[l] + (size_t)(ti - 1) * fs_hid : R.h0[l];
+        const long long hp_fs = ti ? t * fs_hid : fs_hid;
+        const float* cp = ti ? R.CS[l] : R.c0[l];
+        float* h_out = R.HS[l] + (size_t)ti * fs_hid;
+        VadProfScope ps(4, st);
         // VAD_PREC_WINO: every step's gate convolution in Winograd form (both sources of every layer have one width), whatever
         // the launch group's size - the arithmetic of a model never depends on the batch
         // (layer 0 stays direct when latent_dim and lstm_hidden_dim pad to different widths - the packer makes the same test)
-        auto wino_layer = [&](int l) { return wino && (l > 0 || latent == hid); };
-        const bool hoist = !wino && precision == VAD_PREC_FP32 && ZX[0] && vad_convlstm_hoist_ok();
-        bool hoist_upper = hoist;
-        auto lstm_step = [&](int l, int ti, hipStream_t st) -> int {
-            const float* xin_l = (l == 0) ? E : HS[l - 1];
-            const long long fs_in = (l == 0) ? fs_lat : fs_hid;
-            const long long clip_in = (l == 0) ? R.clip_x : (long long)t * fs_hid;   // layer 0 reads the shared features
-            // h(t-1), c(t-1): the previous step's, or at step 0 the caller's initial state (NULL = zero)
-            const float* hp = ti ? HS[l] + (size_t)(ti - 1) * fs_hid : R.h0[l];
-            const long long hp_fs = ti ? (long long)t * fs_hid : fs_hid;
-            const float* cp = ti ? CS[l] : R.c0[l];
-            const long long clip_zx = (l == 0) ? (long long)cs * fs_zx : (long long)t * fs_zx;
-            VadProfScope ps(4, st);
-            if (wino_layer(l))
-                return vad_convlstm_step_wino(xin_l + (size_t)ti * fs_in, clip_in, hp, hp_fs,
-                                              cp, W_(4 + l), B_(4 + l), HS[l] + (size_t)ti * fs_hid, (long long)t * fs_hid, CS[l], ZW[l],
-                                              nc, h16, w16, hid, hid, st);
-            return vad_convlstm_step_zx(xin_l + (size_t)ti * fs_in, clip_in, (hoist && (l == 0 || hoist_upper)) ? ZX[l] + (size_t)ti * fs_zx : nullptr, clip_zx,
-                                        hp, hp_fs,
-                                        cp, W_(4 + l), B_(4 + l),
-                                        HS[l] + (size_t)ti * fs_hid, (long long)t * fs_hid, CS[l],
-                                        nc, h16, w16, (l == 0) ? latent : hid, hid, precision, st);
-        };
-        // bias + x half of layer l's step ti for the nc clips (l >= 1), or of every source frame (l == 0, ti < 0)
-        auto lstm_xhalf = [&](int l, int ti, hipStream_t st) -> int {
-            VadProfScope ps(4, st);
-            if (l == 0)
-                return vad_conv3x3_kpart(E, 0, W_(4), B_(4), ZX[0], 0, nf, h16, w16, latent, latent + hid, 4 * hid, VAD_ACT_NONE, 0,
-                                         VAD_PREC_FP32, nullptr, nullptr, st);
-            return vad_conv3x3_kpart(HS[l - 1] + (size_t)ti * fs_hid, (long long)t * fs_hid, W_(4 + l), B_(4 + l), ZX[l] + (size_t)ti * fs_zx,
-                                     (long long)t * fs_zx, nc, h16, w16, hid, 2 * hid, 4 * hid, VAD_ACT_NONE, 0, VAD_PREC_FP32, nullptr, nullptr, st);
-        };
-        // Large launch groups fill the chip with one step: layers outer, time inner on the caller's stream (the reference's
-        // order).  Small ones (the reference's batch sizes; a step is then one wave's serial K loop on a fraction of the
-        // CUs) run the layers as a wavefront on helper streams.
-        const long long lstm_groups = vid_lstm_groups(nc, h16, w16, hid);
-        const int wf = g_vad_lstm_wavefront.load(std::memory_order_relaxed);
-        if (hoist) TRY(lstm_xhalf(0, -1, s));
-        if (layers > 1 && ((lstm_groups < 256 && wf) || wf == 2)) {   // (Winograd steps share ONE z buffer: layers strictly in order)
-            // per-step x halves of the layers above 0 (a helper-stream launch and two event hops per step) pay while a step is a
-            // long serial K loop; with the gate-split kernel (one window: ~11 us per step) they cost more than they save - measured
-            // 0.78 -> 0.70 ms for one 16-frame window, 1.05 -> 0.97 for two clips - so those steps run their whole K loop
-            hoist_upper = hoist && !vad_convlstm_gate_wins(nc, h16, w16, hid);
-            VadSideStreams* S = nullptr;
-            TRY(side_streams(layers, &S));
-            VAD_HIP_TRY(hipEventRecord(S->fork, s));                          // the encoder's output (and layer 0's x halves) are ready
-            for (int l = 1; l < layers; ++l) {
-                VAD_HIP_TRY(hipStreamWaitEvent(S->st[l - 1], S->fork, 0));
-                if (hoist_upper) VAD_HIP_TRY(hipStreamWaitEvent(S->xs[l - 1], S->fork, 0));
-            }
-            for (int ti = 0; ti < t; ++ti)
-                for (int l = 0; l < layers; ++l) {
-                    hipStream_t st = l ? S->st[l - 1] : s;
-                    if (l && hoist_upper) {                                            // (l-1, ti) finished -> x half of (l, ti) -> step (l, ti)
-                        hipStream_t xs = S->xs[l - 1];
-                        VAD_HIP_TRY(hipStreamWaitEvent(xs, S->done[l - 1], 0));
-                        TRY(lstm_xhalf(l, ti, xs));
-                        VAD_HIP_TRY(hipEventRecord(S->xdone[l], xs));
-                        VAD_HIP_TRY(hipStreamWaitEvent(st, S->xdone[l], 0));
-                    } else if (l) {
-                        VAD_HIP_TRY(hipStreamWaitEvent(st, S->done[l - 1], 0));     // (l-1, ti) finished
-                    }
-                    TRY(lstm_step(l, ti, st));
-                    if (l + 1 < layers || ti + 1 == t) VAD_HIP_TRY(hipEventRecord(S->done[l], st));
-                }
-            for (int l = 1; l < layers; ++l) VAD_HIP_TRY(hipStreamWaitEvent(s, S->done[l], 0));   // join (the x streams end before their steps)
-        } else {
-            for (int l = 0; l < layers; ++l) {
-                if (l && hoist) {                        // one batched launch per layer: its whole input sequence exists
-                    VadProfScope ps(4, s);
-                    TRY(vad_conv3x3_kpart(HS[l - 1], 0, W_(4 + l), B_(4 + l), ZX[l], 0, nc * t, h16, w16, hid, 2 * hid, 4 * hid, VAD_ACT_NONE, 0,
-                                          VAD_PREC_FP32, nullptr, nullptr, s));
-                }
-                for (int ti = 0; ti < t; ++ti) TRY(lstm_step(l, ti, s));
-            }
+        if (R.wino && (l > 0 || R.cin == hid))
+            return vad_convlstm_step_wino(xin_l + (size_t)ti * fs_in, clip_in, hp, hp_fs, cp, R.W[l], R.B[l], h_out, t * fs_hid, R.CS[l], R.ZW[l],
+                                          nc, h16, w16, hid, hid, st);
+        const float* zx = (l ? hoist_upper : hoist) ? R.ZX[l] + (size_t)ti * fs_zx : nullptr;
+        return vad_convlstm_step_zx(xin_l + (size_t)ti * fs_in, clip_in, zx, (l ? t : R.cs) * fs_zx, hp, hp_fs, cp, R.W[l], R.B[l],
+                                    h_out, t * fs_hid, R.CS[l], nc, h16, w16, l ? hid : R.cin, hid, R.precision, st);
+    };
+    // bias + x half of n frames of layer l: of step ti of the nc clips (l >= 1), or (ti < 0) of all its source frames, which lie densely
+    auto lstm_xhalf = [&](int l, int ti, int n, hipStream_t st) -> int {
+        const float* in = l ? R.HS[l - 1] : R.x;
+        const int cin = l ? hid : R.cin;
+        const long long step = ti < 0 ? 0 : ti, clip = ti < 0 ? 0 : t;
+        VadProfScope ps(4, st);
+        return vad_conv3x3_kpart(in + step * fs_hid, clip * fs_hid, R.W[l], R.B[l], R.ZX[l] + step * fs_zx, clip * fs_zx, n, h16, w16, cin, cin + hid,
+                                 4 * hid, VAD_ACT_NONE, 0, VAD_PREC_FP32, nullptr, nullptr, st);
+    };
+
+    if (hoist) TRY(lstm_xhalf(0, -1, R.nf_x, s));
+    if (!wavefront) {
+        for (int l = 0; l < layers; ++l) {
+            if (l && hoist) TRY(lstm_xhalf(l, -1, nc * t, s));                  // one batched launch per layer: its whole input sequence exists
+            for (int ti = 0; ti < t; ++ti) TRY(lstm_step(l, ti, s));
         }
+        return VAD_OK;
     }
-#undef W_
-#undef B_
+    VadSideStreams* S = nullptr;                                                // (Winograd steps have a z buffer per layer)
+    TRY(side_streams(layers, &S));
+    VAD_HIP_TRY(hipEventRecord(S->fork, s));                                    // the encoder's output (and layer 0's x halves) are ready
+    for (int l = 1; l < layers; ++l) {
+        VAD_HIP_TRY(hipStreamWaitEvent(S->st[l - 1], S->fork, 0));
+        if (hoist_upper) VAD_HIP_TRY(hipStreamWaitEvent(S->xs[l - 1], S->fork, 0));
+    }
+    for (int ti = 0; ti < t; ++ti)
+        for (int l = 0; l < layers; ++l) {
+            hipStream_t st = l ? S->st[l - 1] : s;
+            if (l && hoist_upper) {                                             // (l-1, ti) finished -> x half of (l, ti) -> step (l, ti)
+                hipStream_t xs = S->xs[l - 1];
+                VAD_HIP_TRY(hipStreamWaitEvent(xs, S->done[l - 1], 0));
+                TRY(lstm_xhalf(l, ti, nc, xs));
+                VAD_HIP_TRY(hipEventRecord(S->xdone[l], xs));
+                VAD_HIP_TRY(hipStreamWaitEvent(st, S->xdone[l], 0));
+            } else if (l) {
+                VAD_HIP_TRY(hipStreamWaitEvent(st, S->done[l - 1], 0));         // (l-1, ti) finished
+            }
+            TRY(lstm_step(l, ti, st));
+            if (l + 1 < layers || ti + 1 == t) VAD_HIP_TRY(hipEventRecord(S->done[l], st));
+        }
+    for (int l = 1; l < layers; ++l) VAD_HIP_TRY(hipStreamWaitEvent(s, S->done[l], 0));   // join (the x streams end before their steps)
     return VAD_OK;
+}
+
+// The video model's workspace for launch groups of `chunk` clips whose clip c starts at source frame c*cs: two ping-pong buffers
+// ([frames, H/2, W/2, 32]; wide models: [frames, H, W, 32] padded planes), the encoder's features per source frame, the ConvLSTM
+// buffers (into R) with the projection (only when the widths differ) and the partial sums among them.
+struct VidWs { float *A, *B, *E, *P, *parts; long long hs_stride, cs_stride; size_t bytes; };
+VidWs vid_carve(void* ws, LstmRun& R, int chunk, int t, int cs, int h, int w, int latent_real, int hid_real, int layers, int in_ch) {
+    Carve c{(char*)ws, 0};
+    const bool wide = in_ch > 3;
+    const int latent = vad_vid_latent_p(latent_real, hid_real), hid = vad_vid_hid_p(latent_real, hid_real);
+    const size_t n = (size_t)chunk * t, nf = (size_t)(chunk - 1) * cs + t, p16 = (size_t)(h / 16) * (w / 16);
+    const size_t act = sizeof(float) * (n > nf ? n : nf) * (size_t)h * w * (wide ? 32 : 8);
+    VidWs z{c.take(act), c.take(act), c.take(sizeof(float) * nf * p16 * latent)};                      // (a braced list is evaluated in order)
+    lstm_carve(c, R, chunk, t, nf, h / 16, w / 16, hid, layers, layers, [&] {
+        if (hid_real != latent_real) z.P = c.take(sizeof(float) * n * p16 * latent);
+        z.parts = c.take(sizeof(float) * n * (size_t)(wide ? vad_wide_score_partials(h, w) : vad_score_partials(1, h, w)));
+    });
+    // layer strides of the h sequences and the cell states (vad_state_store), in floats: equal pieces, one behind the other
+    z.hs_stride = R.CS[0] - R.HS[layers - 1];
+    z.cs_stride = (z.P ? z.P : z.parts) - R.CS[layers - 1];
+    z.bytes = c.off;
+    return z;
 }
 
 // clips [c0, c0+nc) of a stream whose clip c starts at source frame c*cs; x points at source frame 0 of the stream
 int vid_run(const void* xv, int x_format, int precision, int in_ch, long long nclips, int t, int cs, int h, int w, int latent_real, int hid_real, int layers,
             const float* packed, void* ws, size_t ws_bytes, int chunk, float* seq_scores, float* frame_scores,
             float* errmap, float* recon, const float* state_in, float* state_out, hipStream_t s, const char* who) {
-    VAD_REQUIRE(x_format == VAD_X_F32_NCHW || x_format == VAD_X_U8_NHWC, "%s: unknown input format %d", who, x_format);
-    VAD_REQUIRE(precision == VAD_PREC_FP32 || precision == VAD_PREC_SPLIT || precision == VAD_PREC_WINO, "%s: precision=%d must be VAD_PREC_FP32 (0), VAD_PREC_SPLIT (1) or VAD_PREC_WINO (4)", who, precision);
+    TRY(req_input(who, x_format, in_ch));
+    TRY(req_precision(who, precision));
     const int mprec = precision;                                                  // the blob's mode (device-side tag check)
     const bool wino = precision == VAD_PREC_WINO;
     if (wino) precision = VAD_PREC_FP32;                                          // everything but the encoder's 3x3 convolutions
     const size_t xelem = x_format == VAD_X_U8_NHWC ? 1 : 4;
     const char* x = (const char*)xv;
-    VAD_REQUIRE(in_ch >= 3 && in_ch <= VAD_MAX_IN_CH, "%s: in_channels=%d out of range [3,%d]", who, in_ch, VAD_MAX_IN_CH);
-    VAD_REQUIRE(in_ch == 3 || x_format == VAD_X_F32_NCHW, "%s: uint8 frames are 3-channel images (in_channels=%d)", who, in_ch);
-    const VidWs Z = vid_ws(chunk, t, cs, h, w, latent_real, hid_real, layers, in_ch);
-    if (ws_bytes < Z.total) return vad_fail(VAD_ERR_WS, "%s: workspace %zu B < required %zu B", who, ws_bytes, Z.total);
-    VAD_REQUIRE(((uintptr_t)ws & 255) == 0 && ((uintptr_t)packed & 15) == 0, "%s: workspace must be 256-B and weights 16-B aligned", who);
+    LstmRun R{};
+    const VidWs Z = vid_carve(ws, R, chunk, t, cs, h, w, latent_real, hid_real, layers, in_ch);
+    TRY(req_workspace(who, ws, ws_bytes, Z.bytes, packed));
     const VidLayout L = vid_layout(in_ch, latent_real, hid_real, layers);
     const int latent = L.latent_p, hid = L.hid_p;   // the widths the kernels see (zero-padded, vad_layout.h)
     const int wide = L.wide;                        // in_channels > 3: generic first / last layers over planes padded to `wide` channels
-    char* base = (char*)ws;
-    float* A = (float*)base; base += Z.act;
-    float* Bf = (float*)base; base += Z.act;
-    float* E = (float*)base; base += Z.enc;
-    float* HS[8];
-    float* CS[8];
-    for (int l = 0; l < layers; ++l) { HS[l] = (float*)base; base += Z.hseq; }
-    for (int l = 0; l < layers; ++l) { CS[l] = (float*)base; base += Z.cst; }
-    float* P = nullptr;
-    if (L.has_proj) { P = (float*)base; base += Z.proj; }
-    float* parts = (float*)base; base += Z.parts;
-    float* ZX[8] = {};
-    if (Z.zx0) {
-        ZX[0] = (float*)base; base += Z.zx0;
-        for (int l = 1; l < layers; ++l) { ZX[l] = (float*)base; base += Z.zxl; }
-    }
-    float* ZW[8];                                   // per layer: the layers of a small launch group run concurrently (wavefront)
-    for (int l = 0; l < layers; ++l) { ZW[l] = (float*)base; base += Z.zw; }
+    float *const A = Z.A, *const Bf = Z.B, *const E = Z.E, *const P = Z.P, *const parts = Z.parts;
     const int nparts = wide ? vad_wide_score_partials(h, w) : vad_score_partials(1, h, w);
     const int h16 = h / 16, w16 = w / 16;
     const long long fs_lat = (long long)h16 * w16 * latent, fs_hid = (long long)h16 * w16 * hid;
 #define W_(i) (packed + L.layer[i].w)
 #define B_(i) (packed + L.layer[i].b)
+    R.x = E; R.fs_x = fs_lat; R.clip_x = (long long)cs * fs_lat; R.cs = cs;
+    R.t = t; R.h16 = h16; R.w16 = w16; R.cin = latent; R.hid = hid; R.layers = layers;
+    R.precision = precision; R.wino = wino;
+    for (int l = 0; l < layers; ++l) { R.W[l] = W_(4 + l); R.B[l] = B_(4 + l); }
 
     for (long long c0 = 0; c0 < nclips; c0 += chunk) {
         const int nc = (int)((nclips - c0 < chunk) ? (nclips - c0) : chunk);
@@ -542,28 +560,19 @@ int vid_run(const void* xv, int x_format, int precision, int in_ch, long long nc
         { VadProfScope ps(2, s); TRY(conv3x3_mode(Bf, W_(2), B_(2), A, nf, h / 4, w / 4, 64, 128, VAD_ACT_LEAKY, 1, mprec, s)); }
         { VadProfScope ps(3, s); TRY(conv3x3_mode(A, W_(3), B_(3), E, nf, h / 8, w / 8, 128, latent, VAD_ACT_LEAKY, 1, mprec, s)); }
         // ConvLSTM (models/video_autoencoder.py:144-166): zero initial state, or rows [c0, c0+nc) of the caller's state blob
-        {
-            LstmRun R{};
-            R.x = E; R.fs_x = fs_lat; R.clip_x = (long long)cs * fs_lat; R.nf_x = nf; R.cs = cs;
-            for (int l = 0; l < layers; ++l) {
-                R.W[l] = W_(4 + l); R.B[l] = B_(4 + l); R.HS[l] = HS[l]; R.CS[l] = CS[l]; R.ZX[l] = ZX[l]; R.ZW[l] = ZW[l];
-                if (state_in) {
-                    R.h0[l] = state_in + ((size_t)2 * l * nclips + (size_t)c0) * fs_hid;
-                    R.c0[l] = R.h0[l] + (size_t)nclips * fs_hid;
-                }
-            }
-            R.nc = nc; R.t = t; R.h16 = h16; R.w16 = w16; R.cin = latent; R.hid = hid; R.layers = layers;
-            R.precision = precision; R.wino = wino;
-            TRY(lstm_rollout(R, s));
-            // the final (h, c) of every layer into rows [c0, c0+nc) of state_out: after every step of this launch group has
-            // read its inputs (the join above), so state_out may be state_in
-            if (state_out) {
-                VadProfScope ps(4, s);
-                TRY(vad_state_store(HS[0], (long long)(Z.hseq / sizeof(float)), CS[0], (long long)(Z.cst / sizeof(float)), state_out, nclips, c0, nc, t,
-                                    fs_hid, layers, s));
-            }
+        R.nc = nc; R.nf_x = nf;
+        for (int l = 0; l < layers && state_in; ++l) {
+            R.h0[l] = state_in + ((size_t)2 * l * nclips + (size_t)c0) * fs_hid;
+            R.c0[l] = R.h0[l] + (size_t)nclips * fs_hid;
         }
-        const float* dec_in = HS[layers - 1];
+        TRY(lstm_rollout(R, s));
+        // the final (h, c) of every layer into rows [c0, c0+nc) of state_out: after every step of this launch group has
+        // read its inputs (the join above), so state_out may be state_in
+        if (state_out) {
+            VadProfScope ps(4, s);
+            TRY(vad_state_store(R.HS[0], Z.hs_stride, R.CS[0], Z.cs_stride, state_out, nclips, c0, nc, t, fs_hid, layers, s));
+        }
+        const float* dec_in = R.HS[layers - 1];
         int li = 4 + layers;
         if (L.has_proj) {   // models/video_autoencoder.py:346-349
             VadProfScope ps(5, s);
@@ -602,9 +611,7 @@ extern "C" size_t vad_vid_workspace_bytes(int chunk, int t, int h, int w, int la
     return vad_vid_workspace_bytes_c(chunk, t, h, w, latent, hid, layers, 3);
 }
 extern "C" size_t vad_vid_workspace_bytes_c(int chunk, int t, int h, int w, int latent, int hid, int layers, int in_ch) {
-    if (chunk <= 0 || t <= 0 || h <= 0 || w <= 0 || h % 16 || w % 16) return 0;
-    if (vad_vid_packed_floats_c(in_ch, latent, hid, layers) == 0) return 0;
-    return vid_ws(chunk, t, t, h, w, latent, hid, layers, in_ch).total;
+    return vad_vid_windows_workspace_bytes_c(chunk, t, t, h, w, latent, hid, layers, in_ch);     // clips: windows at stride T
 }
 
 extern "C" int vad_vid_score(const float* x, long long b, int t, int h, int w, int latent, int hid, int layers,
@@ -634,13 +641,12 @@ extern "C" int vad_vid_score_s(const void* x, int x_format, int precision, int i
                                const float* state_in, float* state_out, void* stream) {
     VAD_REQUIRE(x && packed && ws, "vid_score: null pointer");
     VAD_REQUIRE(b > 0 && t > 0 && chunk > 0, "vid_score: clips=%lld T=%d chunk=%d must be positive", b, t, chunk);
-    VAD_REQUIRE(h > 0 && w > 0 && h % 16 == 0 && w % 16 == 0,
-                "vid_score: H=%d W=%d must be positive multiples of 16 (4 MaxPool2d(2) stages)", h, w);
+    TRY(req_frame_shape("vid_score", h, w, " (4 MaxPool2d(2) stages)"));
     if (vad_vid_packed_floats(latent, hid, layers) == 0) return VAD_ERR_ARG;   // message already set
     VAD_REQUIRE(seq_scores || frame_scores || errmap || recon || state_out, "vid_score: no output requested");
     if (state_in || state_out) {
         VAD_REQUIRE(b < (1ll << 31) && vad_vid_state_floats((int)b, h, w, hid, layers) != 0, "vid_score: no state blob exists for %lld streams of %dx%d", b, h, w);
-        VAD_REQUIRE(((uintptr_t)state_in & 15) == 0 && ((uintptr_t)state_out & 15) == 0, "vid_score: state blobs must be 16-B aligned");
+        TRY(req_state_aligned("vid_score", state_in, state_out));
     }
     return vid_run(x, x_format, precision, in_ch, b, t, t, h, w, latent, hid, layers, packed, ws, ws_bytes, chunk, seq_scores, frame_scores, errmap,
                    recon, state_in, state_out, (hipStream_t)stream, "vid_score");
@@ -648,18 +654,11 @@ extern "C" int vad_vid_score_s(const void* x, int x_format, int precision, int i
 
 // ------------------------------------------------------------------------------ layer-level ConvLSTM roll-out
 namespace {
-struct SeqWs { size_t hseq, cst, zx0, zxl, zw, total; };
-SeqWs seq_ws(int b, int t, int gh, int gw, int hid_p, int layers, int all_layers) {
-    SeqWs z{};
-    const size_t n = (size_t)b * t, p = (size_t)gh * gw;
-    z.hseq = up256(sizeof(float) * n * p * hid_p);
-    z.cst = up256(sizeof(float) * (size_t)b * p * hid_p);
-    const bool small = vid_lstm_groups(b, gh, gw, hid_p) < 256;       // as in vid_ws: x halves ahead of the recurrence
-    z.zx0 = small ? up256(sizeof(float) * n * p * 4 * hid_p) : 0;
-    z.zxl = z.zx0;
-    z.zw = up256(sizeof(float) * (size_t)b * p * 4 * hid_p);
-    z.total = (size_t)(all_layers ? 0 : layers - 1) * z.hseq + (size_t)layers * (z.cst + z.zw) + z.zx0 + (size_t)(layers - 1) * z.zxl;
-    return z;
+// every layer's sequence in the caller's buffer (all_layers), or the last layer's only: the others' are workspace
+size_t seq_carve(void* ws, LstmRun& R, int b, int t, int gh, int gw, int hid_p, int layers, int all_layers) {
+    Carve c{(char*)ws, 0};
+    lstm_carve(c, R, b, t, (size_t)b * t, gh, gw, hid_p, layers, all_layers ? 0 : layers - 1, [] {});
+    return c.off;
 }
 int seq_dims_ok(const char* who, long long b, int t, int gh, int gw, int cin_p, int hid_p, int layers) {
     VAD_REQUIRE(b > 0 && b < (1ll << 24) && t > 0 && gh > 0 && gw > 0, "%s: bad shape b=%lld T=%d grid=%dx%d", who, b, t, gh, gw);
@@ -671,7 +670,8 @@ int seq_dims_ok(const char* who, long long b, int t, int gh, int gw, int cin_p, 
 
 extern "C" size_t vad_convlstm_seq_workspace_bytes(int b, int t, int gh, int gw, int cin_p, int hid_p, int layers, int all_layers) {
     if (b <= 0 || t <= 0 || gh <= 0 || gw <= 0 || vad_convlstm_packed_floats(cin_p, hid_p, layers) == 0) return 0;
-    const size_t n = seq_ws(b, t, gh, gw, hid_p, layers, all_layers).total;
+    LstmRun R{};
+    const size_t n = seq_carve(nullptr, R, b, t, gh, gw, hid_p, layers, all_layers);
     return n ? n : 256;
 }
 
@@ -679,30 +679,19 @@ extern "C" int vad_convlstm_seq(const float* x, int precision, long long b, int 
                                 const float* packed, void* ws, size_t ws_bytes, float* hseq_out, int all_layers,
                                 const float* state_in, float* state_out, void* stream) {
     VAD_REQUIRE(x && packed && ws && hseq_out, "convlstm_seq: null pointer");
-    REQ_PREC("convlstm_seq");
+    TRY(req_precision("convlstm_seq", precision));
     TRY(seq_dims_ok("convlstm_seq", b, t, gh, gw, cin_p, hid_p, layers));
     VAD_REQUIRE(precision == VAD_PREC_FP32 || cin_p == hid_p, "convlstm_seq: split / Winograd steps need cin_p == hid_p (got %d, %d)", cin_p, hid_p);
-    const SeqWs Z = seq_ws((int)b, t, gh, gw, hid_p, layers, all_layers);
-    if (ws_bytes < Z.total) return vad_fail(VAD_ERR_WS, "convlstm_seq: workspace %zu B < required %zu B", ws_bytes, Z.total);
-    VAD_REQUIRE(((uintptr_t)ws & 255) == 0 && ((uintptr_t)packed & 15) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)hseq_out & 15) == 0,
+    LstmRun R{};
+    const size_t need = seq_carve(ws, R, (int)b, t, gh, gw, hid_p, layers, all_layers);
+    if (ws_bytes < need) return vad_fail(VAD_ERR_WS, "convlstm_seq: workspace %zu B < required %zu B", ws_bytes, need);
+    VAD_REQUIRE(aligned(ws, 256) && aligned(packed, 16) && aligned(x, 16) && aligned(hseq_out, 16),
                 "convlstm_seq: workspace must be 256-B, weights / x / hseq_out 16-B aligned");
-    VAD_REQUIRE(((uintptr_t)state_in & 15) == 0 && ((uintptr_t)state_out & 15) == 0, "convlstm_seq: state blobs must be 16-B aligned");
+    TRY(req_state_aligned("convlstm_seq", state_in, state_out));
     hipStream_t s = (hipStream_t)stream;
     const long long fs_hid = (long long)gh * gw * hid_p, fs_x = (long long)gh * gw * cin_p;
     const size_t seq_floats = (size_t)b * t * fs_hid;
-    LstmRun R{};
-    char* base = (char*)ws;
-    for (int l = 0; l < layers; ++l) {
-        if (all_layers) R.HS[l] = hseq_out + (size_t)l * seq_floats;
-        else if (l == layers - 1) R.HS[l] = hseq_out;
-        else { R.HS[l] = (float*)base; base += Z.hseq; }
-    }
-    for (int l = 0; l < layers; ++l) { R.CS[l] = (float*)base; base += Z.cst; }
-    if (Z.zx0) {
-        R.ZX[0] = (float*)base; base += Z.zx0;
-        for (int l = 1; l < layers; ++l) { R.ZX[l] = (float*)base; base += Z.zxl; }
-    }
-    for (int l = 0; l < layers; ++l) { R.ZW[l] = (float*)base; base += Z.zw; }
+    for (int l = all_layers ? 0 : layers - 1; l < layers; ++l) R.HS[l] = hseq_out + (all_layers ? (size_t)l * seq_floats : 0);
     for (int l = 0; l < layers; ++l) {
         const VadSeqSlot sl = vad_seq_slot(cin_p, hid_p, l);
         R.W[l] = packed + sl.w; R.B[l] = packed + sl.b;
@@ -730,9 +719,10 @@ extern "C" size_t vad_vid_windows_workspace_bytes(int chunk, int t, int stride, 
     return vad_vid_windows_workspace_bytes_c(chunk, t, stride, h, w, latent, hid, layers, 3);
 }
 extern "C" size_t vad_vid_windows_workspace_bytes_c(int chunk, int t, int stride, int h, int w, int latent, int hid, int layers, int in_ch) {
-    if (chunk <= 0 || t <= 0 || stride <= 0 || stride > t || h <= 0 || w <= 0 || h % 16 || w % 16) return 0;
+    if (chunk <= 0 || t <= 0 || stride <= 0 || stride > t || !frame_shape_ok(h, w)) return 0;
     if (vad_vid_packed_floats_c(in_ch, latent, hid, layers) == 0) return 0;
-    return vid_ws(chunk, t, stride, h, w, latent, hid, layers, in_ch).total;
+    LstmRun R{};
+    return vid_carve(nullptr, R, chunk, t, stride, h, w, latent, hid, layers, in_ch).bytes;
 }
 
 extern "C" int vad_vid_score_windows(const float* frames, long long nframes, int t, int stride, int h, int w,
@@ -758,7 +748,7 @@ extern "C" int vad_vid_score_windows_c(const void* frames, int x_format, int pre
     VAD_REQUIRE(frames && packed && ws, "vid_score_windows: null pointer");
     VAD_REQUIRE(t > 0 && stride > 0 && stride <= t && chunk > 0, "vid_score_windows: need 0 < stride <= T (got T=%d stride=%d) and chunk > 0", t, stride);
     VAD_REQUIRE(nframes >= t, "vid_score_windows: %lld frames are fewer than one window of %d", nframes, t);
-    VAD_REQUIRE(h > 0 && w > 0 && h % 16 == 0 && w % 16 == 0, "vid_score_windows: H=%d W=%d must be positive multiples of 16", h, w);
+    TRY(req_frame_shape("vid_score_windows", h, w, ""));
     if (vad_vid_packed_floats(latent, hid, layers) == 0) return VAD_ERR_ARG;
     VAD_REQUIRE(seq_scores || frame_scores || errmap || recon, "vid_score_windows: no output requested");
     return vid_run(frames, x_format, precision, in_ch, vad_vid_num_windows(nframes, t, stride), t, stride, h, w, latent, hid, layers, packed, ws,
