@@ -203,6 +203,20 @@ int vad_ssim_mse(const float* pred, const float* target, long long planes, int h
 size_t vad_ssim_grad_workspace_floats(long long planes, int h, int w);
 int vad_ssim_mse_backward(const float* pred, const float* target, long long planes, int h, int w, int window_size,
                           float alpha, const float* grad_out, float* workspace, float* grad_pred, void* stream);
+/* Row f-7 - the same criteria as SCORES: one value per frame, and the per-pixel map they are the mean of.
+ * recon_nchw: float32 [frames,c,h,w] (a model's reconstruction); x: the original frames, x_format VAD_X_F32_NCHW
+ * ([frames,c,h,w] float32) or VAD_X_U8_NHWC ([frames,h,w,3] uint8, c == 3 only, normalised on the load: the bits of the
+ * normalised fp32 copy).  Window contract of vad_ssim_mse.  Outputs (device):
+ *   ssim_out[f] = 1 - mean over (c,h,w) of the SSIM map of frame f      = SSIMLoss on that frame as a batch of one;
+ *   comb_out[f] = (1-alpha)*mse_in[f] + alpha*ssim_out[f]               (NULL, or with mse_in = the frames' squared error);
+ *   map_out[f,0,y,x] = mean over c of (1 - SSIM)                        (NULL: no map is written).
+ * No atomics; a frame's values do not depend on the other frames of the call.  fp32 whatever mode produced recon.
+ * workspace: vad_ssim_score_workspace_floats(frames,h,w) floats (host only; 0 = unsupported shape).  Every argument
+ * error is reported before anything is launched. */
+size_t vad_ssim_score_workspace_floats(long long frames, int h, int w);
+int vad_ssim_score(const float* recon_nchw, const void* x, int x_format, long long frames, int c, int h, int w,
+                   int window_size, float alpha, const float* mse_in, float* workspace, float* ssim_out, float* comb_out,
+                   float* map_out, void* stream);
 
 /* ------------------------------------------------------------------ training-step kernels
  * The pieces of one optimisation step of train_video.py:44-65 (model.train(); MSELoss; backward; Adam), exact fp32,

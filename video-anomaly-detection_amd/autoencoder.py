@@ -359,5 +359,27 @@ class ConvAutoencoder(nn.Module):
             raise hip.VadError("score_all is an inference entry point: call under eval() and torch.no_grad()")
         return self._run_hip(x, scores=True, errmap=True, recon=True)
 
+    def score_criteria(self, x, window_size: int = 11, alpha: float = 0.5, ssim_map: bool = False, errmap: bool = False,
+                       recon: bool = False):
+        """The reference's three criteria (train.py:149-158) per image from ONE forward: {'mse': [B] - the tensor
+        `get_reconstruction_error(x)` returns -, 'ssim': [B] = SSIMLoss(window_size) of every image as a batch of one,
+        'combined': [B] = (1-alpha)*mse + alpha*ssim} (+ 'ssim_map' [B,1,H,W], 'errmap', 'recon' on request).  The
+        reference's validation loop runs two forwards and the batch criterion for these (train.py:74-79).  SSIM runs over
+        the model's own channels (a 1- / 2-channel model: the narrowed reconstruction), always in fp32."""
+        if not self._use_hip():
+            raise hip.VadError("score_criteria is an inference entry point: call under eval() and torch.no_grad()")
+        from .losses import ssim_per_frame
+        out = self._run_hip(x, scores=True, errmap=errmap, recon=True)
+        target = x if x.dtype == torch.uint8 else x.float()
+        crit = ssim_per_frame(out["recon"], target, window_size, alpha, mse=out["scores"], ssim_map=ssim_map)
+        res = {"mse": out["scores"], "ssim": crit["ssim"], "combined": crit["combined"]}
+        if ssim_map:
+            res["ssim_map"] = crit["ssim_map"]
+        if errmap:
+            res["errmap"] = out["errmap"]
+        if recon:
+            res["recon"] = out["recon"]
+        return res
+
 
 Autoencoder = ConvAutoencoder  # name used by BASELINE.json's north_star

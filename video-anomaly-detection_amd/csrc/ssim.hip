@@ -11,6 +11,7 @@
 // the SSIM value and the squared error of the centre pixel are formed in registers and reduced to one partial per
 // work-group (wave butterfly + LDS).  HBM traffic = 8 B per element (+ halo overlap), no intermediate map is written.
 // A second single-block kernel adds the partials in a fixed order (deterministic) and forms the three scalars.
+// ssim_frame_kernel (below) is the same scheme kept per frame and per pixel: the criteria as scores.
 #include <hip/hip_runtime.h>
 
 #include "vad_common.h"
@@ -247,6 +248,123 @@ __global__ __launch_bounds__(256) void ssim_finalize_kernel(const float* parts, 
     }
 }
 
+// ------------------------------------------------------------------------------------------- per-frame scoring
+// SSIM as a SCORE: one value per frame instead of one per call, plus the per-pixel map
+// 1 - S averaged over the channels.  A work-group owns one (frame, 32x32 tile) and walks the frame's C channels with the
+// scheme of ssim_partials_kernel (same LDS arrays, same fmaf order, same S expression), keeping the tile's sum of S and
+// the four per-pixel sums of 1 - S of each thread in registers; one partial per (frame, tile), no atomics, so a frame's
+// value depends on nothing but that frame.  The input side is fp32 NCHW or raw uint8 NHWC (normalised on the load).
+struct SsimFrameP {
+    const float* recon; const void* x;
+    float* parts;               // [frames][tiles]
+    float* map;                 // [frames][h][w] or null
+    int c, h, w, r, tiles_x, tiles_y;
+    float g[2 * SR_MAX + 1];
+};
+
+template <int FMT>
+__global__ __launch_bounds__(256) void ssim_frame_kernel(SsimFrameP a) {
+    __shared__ float sp[SH * (SH + 1)], st[SH * (SH + 1)];
+    __shared__ float hz[5][SH * (ST + 1)];
+    __shared__ float red[4];
+    const int tid = threadIdx.x, r = a.r, hh = ST + 2 * r, pitch = hh + 1;
+    unsigned b = blockIdx.x;
+    const int tx = b % a.tiles_x; b /= a.tiles_x;
+    const int ty = b % a.tiles_y;
+    const size_t f = b / a.tiles_y, hw = (size_t)a.h * a.w;
+    const int y0 = ty * ST - r, x0 = tx * ST - r;
+    const int xx = tid & 31;
+    constexpr float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;      // utils/losses.py:82-83
+    float ssum = 0.f, msum[4] = {0.f, 0.f, 0.f, 0.f};
+
+    for (int ch = 0; ch < a.c; ++ch) {
+        const float* rp = a.recon + (f * a.c + ch) * hw;
+        // halo tile, zero outside the image (= F.conv2d's zero padding).  The arrays are free: every read of the previous
+        // channel's sp / st lies before its second barrier, every read of its hz before this channel's first one.
+        for (int i = tid; i < hh * hh; i += 256) {
+            const int yy = i / hh, hx = i - yy * hh;
+            const int y = y0 + yy, x = x0 + hx;
+            float p = 0.f, t = 0.f;
+            if (y >= 0 && y < a.h && x >= 0 && x < a.w) {
+                const size_t o = (size_t)y * a.w + x;
+                p = rp[o];
+                if (FMT == VAD_X_U8_NHWC) t = vad_norm_u8(((const unsigned char*)a.x)[(f * hw + o) * 3 + ch]);
+                else t = ((const float*)a.x)[(f * a.c + ch) * hw + o];
+            }
+            sp[yy * pitch + hx] = p;
+            st[yy * pitch + hx] = t;
+        }
+        __syncthreads();
+
+        // horizontal pass: hh rows x 32 columns x 5 quantities
+        for (int i = tid; i < hh * ST; i += 256) {
+            const int yy = i >> 5, hx = i & 31;
+            float m0 = 0.f, m1 = 0.f, m2 = 0.f, m3 = 0.f, m4 = 0.f;
+            for (int k = 0; k <= 2 * r; ++k) {
+                const float g = a.g[k], p = sp[yy * pitch + hx + k], t = st[yy * pitch + hx + k];
+                m0 = fmaf(g, p, m0);
+                m1 = fmaf(g, t, m1);
+                m2 = fmaf(g, p * p, m2);
+                m3 = fmaf(g, t * t, m3);
+                m4 = fmaf(g, p * t, m4);
+            }
+            const int o = yy * (ST + 1) + hx;
+            hz[0][o] = m0; hz[1][o] = m1; hz[2][o] = m2; hz[3][o] = m3; hz[4][o] = m4;
+        }
+        __syncthreads();
+
+        // vertical pass + SSIM; thread -> column tid&31, rows (tid>>5) + 8j
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int yy = (tid >> 5) + 8 * j;
+            float m0 = 0.f, m1 = 0.f, m2 = 0.f, m3 = 0.f, m4 = 0.f;
+            for (int k = 0; k <= 2 * r; ++k) {
+                const float g = a.g[k];
+                const int o = (yy + k) * (ST + 1) + xx;
+                m0 = fmaf(g, hz[0][o], m0);
+                m1 = fmaf(g, hz[1][o], m1);
+                m2 = fmaf(g, hz[2][o], m2);
+                m3 = fmaf(g, hz[3][o], m3);
+                m4 = fmaf(g, hz[4][o], m4);
+            }
+            const float mpp = m0 * m0, mtt = m1 * m1, mpt = m0 * m1;
+            const float num = (2.f * mpt + C1) * (2.f * (m4 - mpt) + C2);
+            const float den = (mpp + mtt + C1) * ((m2 - mpp) + (m3 - mtt) + C2);
+            const bool in = (ty * ST + yy) < a.h && (tx * ST + xx) < a.w;
+            if (in) { const float s = num / den; ssum += s; msum[j] += 1.f - s; }
+        }
+    }
+
+    if (a.map) {
+        const float cf = (float)a.c;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int y = ty * ST + (tid >> 5) + 8 * j, x = tx * ST + xx;
+            if (y < a.h && x < a.w) a.map[f * hw + (size_t)y * a.w + x] = msum[j] / cf;
+        }
+    }
+    ssum = wave_sum64(ssum);
+    if ((tid & 63) == 0) red[tid >> 6] = ssum;
+    __syncthreads();
+    if (tid == 0) a.parts[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// One wave per frame: that frame's tile partials in a fixed order, in double.  ssim[f] = 1 - mean S; with a per-frame MSE
+// handed in, comb[f] = (1-alpha)*mse[f] + alpha*ssim[f] (CombinedLoss on the frame as a batch of one).
+__global__ __launch_bounds__(64) void ssim_frame_finalize_kernel(const float* parts, unsigned tiles, double count, float alpha,
+                                                                 const float* mse, float* ssim, float* comb) {
+    const size_t f = blockIdx.x;
+    double s = 0.0;
+    for (unsigned i = threadIdx.x; i < tiles; i += 64) s += (double)parts[f * tiles + i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (threadIdx.x == 0) {
+        const float l_ssim = (float)(1.0 - s / count);
+        ssim[f] = l_ssim;
+        if (comb) comb[f] = (1.f - alpha) * mse[f] + alpha * l_ssim;
+    }
+}
+
 }  // namespace
 
 extern "C" size_t vad_ssim_workspace_floats(long long planes, int h, int w) {
@@ -320,6 +438,53 @@ extern "C" int vad_ssim_mse_backward(const float* pred, const float* target, lon
     VAD_LAUNCH_CHECK();
     hipLaunchKernelGGL(ssim_grad_kernel, dim3(a.nblocks), dim3(256), 0, s, a, (const float*)workspace, grad_out, alpha,
                        (float)(1.0 / ((double)planes * h * w)), grad_pred);
+    VAD_LAUNCH_CHECK();
+    return VAD_OK;
+}
+
+// work-groups (= partials) of a vad_ssim_score call, or 0 when the shape is bad or the grid would not fit: the ONE rule behind
+// the size query and the launch (no product is formed before it is known to fit)
+static long long ssim_score_blocks(long long frames, int h, int w) {
+    if (frames <= 0 || h <= 0 || w <= 0) return 0;
+    const long long tiles = (long long)((w + ST - 1) / ST) * ((h + ST - 1) / ST);
+    return tiles < (1ll << 31) && frames < (1ll << 31) / tiles ? frames * tiles : 0;
+}
+
+extern "C" size_t vad_ssim_score_workspace_floats(long long frames, int h, int w) {
+    const long long nb = ssim_score_blocks(frames, h, w);
+    return nb > 0 ? (size_t)nb : 0;
+}
+
+extern "C" int vad_ssim_score(const float* recon_nchw, const void* x, int x_format, long long frames, int c, int h, int w,
+                              int window_size, float alpha, const float* mse_in, float* workspace, float* ssim_out, float* comb_out,
+                              float* map_out, void* stream) {
+    VAD_REQUIRE(recon_nchw && x && workspace && ssim_out, "ssim_score: null pointer");
+    VAD_REQUIRE(!comb_out || mse_in, "ssim_score: comb_out needs mse_in (the per-frame squared error it is combined with)");
+    VAD_REQUIRE(x_format == VAD_X_F32_NCHW || x_format == VAD_X_U8_NHWC, "ssim_score: unknown x_format %d", x_format);
+    VAD_REQUIRE(frames > 0 && c > 0 && h > 0 && w > 0, "ssim_score: bad shape");
+    VAD_REQUIRE(x_format != VAD_X_U8_NHWC || c == 3, "ssim_score: uint8 frames are [N,H,W,3], got c=%d", c);
+    VAD_REQUIRE(window_size >= 1 && (window_size & 1) && window_size <= 2 * SR_MAX + 1,
+                "ssim_score: window_size=%d must be odd and at most %d", window_size, 2 * SR_MAX + 1);
+    SsimFrameP a{};
+    a.recon = recon_nchw; a.x = x; a.parts = workspace; a.map = map_out;
+    a.c = c; a.h = h; a.w = w; a.r = window_size / 2;
+    a.tiles_x = (w + ST - 1) / ST; a.tiles_y = (h + ST - 1) / ST;
+    const long long tiles = (long long)a.tiles_x * a.tiles_y, nb = ssim_score_blocks(frames, h, w);
+    VAD_REQUIRE(nb > 0, "ssim_score: grid too large");
+    // 1-D Gaussian, sigma 1.5, normalised in fp32 like utils/losses.py:36-40
+    float g[2 * SR_MAX + 1], gs = 0.f;
+    for (int k = 0; k < window_size; ++k) {
+        const float d = (float)(k - window_size / 2);
+        g[k] = expf(-(d * d) / (2.f * 1.5f * 1.5f));
+        gs += g[k];
+    }
+    for (int k = 0; k < 2 * SR_MAX + 1; ++k) a.g[k] = k < window_size ? g[k] / gs : 0.f;
+    hipStream_t s = (hipStream_t)stream;
+    if (x_format == VAD_X_U8_NHWC) hipLaunchKernelGGL(ssim_frame_kernel<VAD_X_U8_NHWC>, dim3((unsigned)nb), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(ssim_frame_kernel<VAD_X_F32_NCHW>, dim3((unsigned)nb), dim3(256), 0, s, a);
+    VAD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ssim_frame_finalize_kernel, dim3((unsigned)frames), dim3(64), 0, s, (const float*)workspace, (unsigned)tiles,
+                       (double)c * h * w, alpha, mse_in, ssim_out, comb_out);
     VAD_LAUNCH_CHECK();
     return VAD_OK;
 }

@@ -125,3 +125,49 @@ class CombinedLoss(nn.Module):
         if _hip_eligible(pred, target):
             return _hip_loss(pred, target, self.ssim.window_size, float(self.alpha), 2)
         return (1 - self.alpha) * self.mse(pred, target) + self.alpha * self.ssim(pred, target)
+
+
+def ssim_per_frame(pred: torch.Tensor, target: torch.Tensor, window_size: int = 11, alpha: float = 0.5, mse=None,
+                   ssim_map: bool = False) -> dict:
+    """The criteria as per-frame SCORES (vad_ssim_score, csrc/ssim.hip): `pred` fp32 `[N,C,H,W]` on the GPU, `target` the same
+    shape or raw uint8 `[N,H,W,3]` (normalised inside the kernel).  Returns {'ssim': [N]} - `SSIMLoss(window_size)` on every
+    frame as a batch of one - plus 'combined' [N] = (1-alpha)*mse + alpha*ssim when the frames' squared error `mse` [N] is
+    handed in, plus 'ssim_map' [N,1,H,W] (channel mean of 1 - SSIM per pixel) on request.  A frame's values are the same
+    bits whatever else is in the batch.  Inference only (no gradient); there is no CPU form."""
+    if not (isinstance(pred, torch.Tensor) and isinstance(target, torch.Tensor) and pred.is_cuda and target.is_cuda
+            and pred.device == target.device):
+        raise hip.VadError("ssim_per_frame runs only on the MI355X HIP path: pred and target must be on one GPU "
+                           "(SSIMLoss / CombinedLoss are the CPU forms)")
+    u8 = target.dtype == torch.uint8
+    if pred.dim() != 4 or pred.dtype != torch.float32:
+        raise hip.VadError(f"ssim_per_frame: pred must be float32 [N,C,H,W], got {pred.dtype} {tuple(pred.shape)}")
+    n, c, h, w = pred.shape
+    want = (n, h, w, 3) if u8 else (n, c, h, w)
+    if tuple(target.shape) != want or (u8 and c != 3) or (not u8 and target.dtype != torch.float32):
+        raise hip.VadError(f"ssim_per_frame: target must be float32 {(n, c, h, w)}" + (f" or uint8 {(n, h, w, 3)}" if c == 3 else "")
+                           + f", got {target.dtype} {tuple(target.shape)}")
+    dev = pred.device
+    if mse is not None:
+        if tuple(mse.shape) != (n,) or mse.device != dev:
+            raise hip.VadError(f"ssim_per_frame: mse must be a float32 [{n}] tensor on {dev}, got {tuple(mse.shape)} on {mse.device}")
+        mse = mse.detach().contiguous().float()
+    out = {"ssim": torch.empty(n, dtype=torch.float32, device=dev)}
+    if mse is not None:
+        out["combined"] = torch.empty(n, dtype=torch.float32, device=dev)
+    if ssim_map:
+        out["ssim_map"] = torch.empty(n, 1, h, w, dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    l = hip.lib()
+    pred, target = pred.detach().contiguous(), target.detach().contiguous()
+    nws = l.vad_ssim_score_workspace_floats(n, h, w)
+    if nws == 0:
+        raise hip.VadError(f"ssim_per_frame: unsupported shape {tuple(pred.shape)}")
+    ws = torch.empty(nws, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        hip.check(l.vad_ssim_score(pred.data_ptr(), target.data_ptr(), hip.X_U8_NHWC if u8 else hip.X_F32_NCHW, n, c, h, w,
+                                   int(window_size), float(alpha), hip.ptr(mse), ws.data_ptr(), out["ssim"].data_ptr(),
+                                   hip.ptr(out.get("combined")), hip.ptr(out.get("ssim_map")), hip.current_stream()),
+                  "vad_ssim_score")
+    hip.calls["ssim_score"] = hip.calls.get("ssim_score", 0) + 1
+    return out

@@ -114,6 +114,36 @@ def score_frames_stateful(model, frame_iter: Iterable, batch: int = 1, state=Non
     return torch.cat(scores, dim=1).cpu().numpy(), state
 
 
+CRITERIA = ("mse", "ssim", "combined")     # train.py --loss
+
+
+def validate(model, loader: Iterable[dict], device, criterion: str = "mse", ssim_weight: float = 0.5, window_size: int = 11):
+    """The validation loop of the reference's train.py:54-91 / train_video.py:68-98 with ONE forward per batch (the reference
+    runs `model(images)`, the criterion and `get_reconstruction_error`): batches {'image' | 'frames', 'label'}; `criterion` is
+    train.py's --loss choice ('mse', 'ssim', 'combined' with `ssim_weight` = its alpha).  Returns (avg_loss, avg_normal,
+    avg_anomaly): the batch losses averaged over batches, and the mean reconstruction error of the samples labelled 0 and of
+    the others (0 when there are none).  A batch's loss is the mean of its samples' criterion (`score_criteria`); the samples
+    of a batch are equally large, so that is the criterion of the batch (for clips: of its frames as one batch, the one way
+    SSIMLoss takes them)."""
+    if criterion not in CRITERIA:
+        raise hip.VadError(f"validate: criterion must be one of {CRITERIA}, got {criterion!r}")
+    model.eval()
+    total, batches, normal, anomaly = 0.0, 0, [], []
+    with torch.no_grad():
+        for batch in loader:
+            video = "frames" in batch
+            x = batch["frames" if video else "image"].to(device)
+            out = model.score_criteria(x, window_size=window_size, alpha=ssim_weight)
+            errors = out["seq_mse" if video else "mse"]
+            total += float(out[("seq_" if video else "") + criterion].mean())
+            batches += 1
+            for err, label in zip(errors.cpu().numpy(), np.asarray(batch["label"])):
+                (normal if label == 0 else anomaly).append(err)
+    if batches == 0:
+        raise ValueError("validate needs at least one batch")
+    return (total / batches, sum(normal) / len(normal) if normal else 0, sum(anomaly) / len(anomaly) if anomaly else 0)
+
+
 # ------------------------------------------------------------------------------ Resize on the device
 CHANNEL_ORDERS = {"rgb": 0, "bgr": 1}
 

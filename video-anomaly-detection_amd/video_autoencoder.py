@@ -584,3 +584,31 @@ class VideoAutoencoder(nn.Module):
         if not self._use_hip():
             raise hip.VadError("score_all is an inference entry point: call under eval() and torch.no_grad()")
         return self._run_hip(x, seq=True, frame=True, errmap=True, recon=True)
+
+    def score_criteria(self, x, window_size: int = 11, alpha: float = 0.5, ssim_map: bool = False, errmap: bool = False,
+                       recon: bool = False):
+        """The three criteria per FRAME from one forward of clips `x` [B,T,C,H,W] (uint8 [B,T,H,W,3]): {'mse', 'ssim', 'combined':
+        [B,T]} - a frame is one SSIM sample, the only shape the reference's SSIMLoss takes (utils/losses.py:51-93) -, the clip
+        values {'seq_mse': [B] - the tensor `get_reconstruction_error(x)` returns -, 'seq_ssim', 'seq_combined': [B]} as means
+        over T (+ 'ssim_map' [B,T,1,H,W], 'errmap', 'recon' on request).  Every arithmetic mode of `precision` applies to the
+        forward; the SSIM kernel is fp32."""
+        if not self._use_hip():
+            raise hip.VadError("score_criteria is an inference entry point: call under eval() and torch.no_grad()")
+        from .losses import ssim_per_frame
+        out = self._run_hip(x, seq=True, frame=True, errmap=errmap, recon=True)
+        b, t = out["frame"].shape
+        u8 = x.dtype == torch.uint8
+        target = x.contiguous() if u8 else x.contiguous().float()
+        rec = out["recon"]
+        crit = ssim_per_frame(rec.reshape(b * t, *rec.shape[2:]), target.reshape(b * t, *target.shape[2:]), window_size, alpha,
+                              mse=out["frame"].reshape(b * t), ssim_map=ssim_map)
+        res = {"mse": out["frame"], "ssim": crit["ssim"].view(b, t), "combined": crit["combined"].view(b, t), "seq_mse": out["seq"]}
+        res["seq_ssim"] = res["ssim"].mean(dim=1)
+        res["seq_combined"] = res["combined"].mean(dim=1)
+        if ssim_map:
+            res["ssim_map"] = crit["ssim_map"].view(b, t, 1, *rec.shape[3:])
+        if errmap:
+            res["errmap"] = out["errmap"]
+        if recon:
+            res["recon"] = rec
+        return res
