@@ -359,6 +359,17 @@ int vad_conv_c3_wgrad_t(const float* x_nchw, const void* g, int io16, float* dw,
 int vad_convt_to3_mse_t(const void* in_nhwc, int io16, const float* w_iohw, const float* bias3, const float* x_nchw, float* recon,
                         void* din, void* dpre32, float* loss, float* dbias3, float* ws, int n, int h, int w, float grad_mul,
                         void* stream);
+/* The same layer as separate launches, for a criterion evaluated between them (SSIMLoss / CombinedLoss need the whole
+ * reconstruction before any gradient exists).  io16 != 0: in / din / dpre32 are bf16, everything else fp32.
+ *   fwd: recon [n,3,2h,2w] = tanh(convT(in) + bias), the bits vad_convt_to3_mse_t writes for the same input.
+ *   bwd: from recon and drecon = d loss / d recon (both NCHW fp32; the layer's input is not read): dpre32 [n*h*w][32]
+ *        (column q*3+c = grad_mul * drecon * (1 - recon^2), columns 12..31 zero), din [n,h,w,32] (nullable) and dbias3
+ *        (nullable; needs ws of vad_convt_to3_tanh_bwd_ws_floats floats).  grad_mul: a power of two, as above. */
+size_t vad_convt_to3_tanh_bwd_ws_floats(int n, int h, int w);
+int vad_convt_to3_tanh_fwd_t(const void* in_nhwc, int io16, const float* w_iohw, const float* bias3, float* recon, int n, int h, int w,
+                             void* stream);
+int vad_convt_to3_tanh_bwd_t(const float* recon, const float* drecon, const float* w_iohw, void* din, void* dpre32, int io16,
+                             float* dbias3, float* ws, int n, int h, int w, float grad_mul, void* stream);
 /* p[i] *= mul, i < n. */
 int vad_scale_floats(float* p, long long n, float mul, void* stream);
 /* Conv2d k1 with `precision`: VAD_PREC_BF16S = bf16 tensors and bf16 operands (weights from vad_train_pack_conv1x1_p with the
@@ -421,6 +432,16 @@ int vad_vid_train_debug_layout(int b, int t, int h, int w, int latent, int hid, 
 int vad_vid_train_fwd_bwd(const float* x, int b, int t, int h, int w, int latent, int hid, int layers,
                           const float* params, float* grads, float* running, void* workspace, size_t workspace_bytes,
                           int precision, float* loss, float* recon, void* stream);
+/* The same step with the criterion as an argument (`_l`): loss_kind 0 = nn.MSELoss - exactly the two entry points above, which
+ * are these with loss_kind 0 -, 1 = SSIMLoss(window_size), 2 = CombinedLoss(alpha, window_size), on the frames of the batch as one
+ * [B*T,3,H,W] batch (the one way SSIMLoss takes clips, as in scoring.validate).  Kinds 1 / 2 run the last layer as
+ * vad_convt_to3_tanh_fwd_t, vad_ssim_mse, vad_ssim_mse_backward, vad_convt_to3_tanh_bwd_t; the criterion is fp32 in every
+ * precision mode.  The workspace of kinds 1 / 2 is that of kind 0 plus, behind it, recon, d recon and the criterion's scratch;
+ * 0 = unsupported shape or loss_kind. */
+size_t vad_vid_train_workspace_bytes_l(int b, int t, int h, int w, int latent, int hid, int layers, int loss_kind);
+int vad_vid_train_fwd_bwd_l(const float* x, int b, int t, int h, int w, int latent, int hid, int layers,
+                            const float* params, float* grads, float* running, void* workspace, size_t workspace_bytes,
+                            int loss_kind, float alpha, int window_size, int precision, float* loss, float* recon, void* stream);
 
 /* Image autoencoder counterpart (train.py:28-52; not a SURVEY section 8 row): ConvAutoencoder(in_channels=3, latent_dim), x
  * [N,3,H,W]; loss_kind 0 = nn.MSELoss (train.py default), 1 = SSIMLoss(window_size), 2 = CombinedLoss(alpha, window_size)

@@ -588,6 +588,103 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(const float* parts, 
         dbias3[threadIdx.x] = (colsum32[threadIdx.x] + colsum32[3 + threadIdx.x]) + (colsum32[6 + threadIdx.x] + colsum32[9 + threadIdx.x]);
 }
 
+// The same layer as three launches, for criteria whose gradient is not a function of the pixel alone (SSIM: an 11x11
+// neighbourhood): forward, the criterion on `recon` (csrc/ssim.hip), then the backward from an arbitrary d loss / d recon.
+// A thread owns one input pixel = 2x2x3 outputs; per channel these are two rows of one adjacent float pair, so adjacent lanes
+// touch contiguous 8-byte pieces of the NCHW planes.
+struct To3FwdP { const void* in; const float* w; const float* bias; float* recon; int h, w_; long long total; };
+
+// recon = tanh(convT(in) + b): the fmaf chain from the bias and vad_tanh of convt_to3_mse_kernel - the same bits.
+template <typename T>
+__global__ __launch_bounds__(256) void convt_to3_tanh_fwd_kernel(To3FwdP p) {
+    typedef vad_io4<T> io;
+    __shared__ float ws[32 * 12], bs[3];
+    for (int i = threadIdx.x; i < 384; i += 256) ws[i] = p.w[i];     // [ci][c][q]
+    if (threadIdx.x < 3) bs[threadIdx.x] = p.bias[threadIdx.x];
+    __syncthreads();
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= p.total) return;
+    const int x = (int)(idx % p.w_), y = (int)((idx / p.w_) % p.h);
+    const long long n = idx / ((long long)p.w_ * p.h);
+    float r[32];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const f32x4 v = io::ld((const T*)p.in + idx * 32 + 4 * k);
+        r[4 * k] = v[0]; r[4 * k + 1] = v[1]; r[4 * k + 2] = v[2]; r[4 * k + 3] = v[3];
+    }
+    const int H2 = 2 * p.h, W2 = 2 * p.w_;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy) {
+            f32x2 o;
+#pragma unroll
+            for (int dx = 0; dx < 2; ++dx) {
+                const int q = 2 * dy + dx;
+                float pre = bs[c];
+#pragma unroll
+                for (int ci = 0; ci < 32; ++ci) pre = fmaf(r[ci], ws[ci * 12 + c * 4 + q], pre);
+                o[dx] = vad_tanh(pre);
+            }
+            *(f32x2*)&p.recon[(((size_t)n * 3 + c) * H2 + 2 * y + dy) * W2 + 2 * x] = o;
+        }
+}
+
+struct To3BwdP { const float* recon; const float* drecon; const float* w; void* din; void* dpre; int h, w_; float grad_mul; long long total; };
+
+// dp[q*3+c] = grad_mul * drecon * (1 - recon^2); din = dp . W in convt_to3_mse_kernel's summation order; dpre = the 32-column
+// weight-gradient operand.  Reads the reconstruction and its gradient only: neither the layer's input nor its forward.
+template <typename T>
+__global__ __launch_bounds__(256) void convt_to3_tanh_bwd_kernel(To3BwdP p) {
+    typedef vad_io4<T> io;
+    __shared__ float ws[32 * 12];
+    for (int i = threadIdx.x; i < 384; i += 256) ws[i] = p.w[i];     // [ci][c][q]
+    __syncthreads();
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= p.total) return;
+    const int x = (int)(idx % p.w_), y = (int)((idx / p.w_) % p.h);
+    const long long n = idx / ((long long)p.w_ * p.h);
+    const int H2 = 2 * p.h, W2 = 2 * p.w_;
+    float dp[12];       // index q*3 + c
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy) {
+            const size_t o = (((size_t)n * 3 + c) * H2 + 2 * y + dy) * W2 + 2 * x;
+            const f32x2 rec = *(const f32x2*)&p.recon[o], d = *(const f32x2*)&p.drecon[o];
+#pragma unroll
+            for (int dx = 0; dx < 2; ++dx) dp[(2 * dy + dx) * 3 + c] = p.grad_mul * d[dx] * (1.f - rec[dx] * rec[dx]);
+        }
+    if (p.din) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            f32x4 o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float s = 0.f;
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) s = fmaf(dp[q * 3 + c], ws[(4 * k + e) * 12 + c * 4 + q], s);
+                o[e] = s;
+            }
+            io::st((T*)p.din + idx * 32 + 4 * k, o);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        f32x4 o = {0.f, 0.f, 0.f, 0.f};
+        if (k < 3) o = f32x4{dp[4 * k], dp[4 * k + 1], dp[4 * k + 2], dp[4 * k + 3]};
+        io::st((T*)p.dpre + idx * 32 + 4 * k, o);
+    }
+}
+
+// db[c] = sum_q colsum[q*3+c], in loss_finalize_kernel's order
+__global__ void to3_dbias_kernel(const float* colsum32, float* dbias3) {
+    if (threadIdx.x < 3)
+        dbias3[threadIdx.x] = (colsum32[threadIdx.x] + colsum32[3 + threadIdx.x]) + (colsum32[6 + threadIdx.x] + colsum32[9 + threadIdx.x]);
+}
+
 // ------------------------------------------------------------------------------------------------ optimiser
 // torch.optim.Adam (train_video.py:175): g += wd*p; m = b1*m + (1-b1)*g; v = b2*v + (1-b2)*g*g;
 // p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
@@ -1054,6 +1151,55 @@ int vad_convt_to3_mse_t(const void* in_nhwc, int io16, const float* w_iohw, cons
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, s, (const float*)ws, (int)nb, count, loss,
                        (const float*)colsum, dbias3);
     VAD_LAUNCH_CHECK();
+    return VAD_OK;
+}
+
+// ws = [64: column sums of dpre][partials of that column reduction]
+extern "C" size_t vad_convt_to3_tanh_bwd_ws_floats(int n, int h, int w) {
+    if (n <= 0 || h <= 0 || w <= 0) return 0;
+    return 64 + vad_chan_ws_floats((long long)n * h * w, 32);
+}
+
+int vad_convt_to3_tanh_fwd_t(const void* in_nhwc, int io16, const float* w_iohw, const float* bias3, float* recon, int n, int h, int w,
+                             void* stream) {
+    VAD_REQUIRE(in_nhwc && w_iohw && bias3 && recon && n > 0 && h > 0 && w > 0, "convt_to3_tanh_fwd: bad arguments");
+    const long long total = (long long)n * h * w;
+    const long long nb = (total + 255) / 256;
+    VAD_REQUIRE(nb < (1ll << 31), "convt_to3_tanh_fwd: grid too large");
+    To3FwdP p{in_nhwc, w_iohw, bias3, recon, h, w, total};
+    hipStream_t s = (hipStream_t)stream;
+    if (io16) hipLaunchKernelGGL(convt_to3_tanh_fwd_kernel<vad_bf16>, dim3((unsigned)nb), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(convt_to3_tanh_fwd_kernel<float>, dim3((unsigned)nb), dim3(256), 0, s, p);
+    VAD_LAUNCH_CHECK();
+    return VAD_OK;
+}
+
+int vad_convt_to3_tanh_bwd_t(const float* recon, const float* drecon, const float* w_iohw, void* din, void* dpre32, int io16,
+                             float* dbias3, float* ws, int n, int h, int w, float grad_mul, void* stream) {
+    VAD_REQUIRE(recon && drecon && w_iohw && dpre32 && n > 0 && h > 0 && w > 0, "convt_to3_tanh_bwd: bad arguments");
+    VAD_REQUIRE(vad_is_pow2f(grad_mul), "convt_to3_tanh_bwd: grad_mul=%g must be a power of two (an exact rescaling of every gradient)", (double)grad_mul);
+    VAD_REQUIRE(!dbias3 || ws, "convt_to3_tanh_bwd: the bias gradient needs the workspace");
+    const long long total = (long long)n * h * w;
+    const long long nb = (total + 255) / 256;
+    VAD_REQUIRE(nb < (1ll << 31), "convt_to3_tanh_bwd: grid too large");
+    To3BwdP p{recon, drecon, w_iohw, din, dpre32, h, w, grad_mul, total};
+    hipStream_t s = (hipStream_t)stream;
+    if (io16) hipLaunchKernelGGL(convt_to3_tanh_bwd_kernel<vad_bf16>, dim3((unsigned)nb), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(convt_to3_tanh_bwd_kernel<float>, dim3((unsigned)nb), dim3(256), 0, s, p);
+    VAD_LAUNCH_CHECK();
+    if (dbias3) {       // the route of vad_convt_to3_mse_t: column sums of dpre, then the four positions of a channel
+        const long long chunk = stats_chunk(total);
+        const int cb = (int)((total + chunk - 1) / chunk);
+        float *colsum = ws, *cws = ws + 64;
+        if (io16) hipLaunchKernelGGL(chan_sums_kernel<vad_bf16>, dim3(cb), dim3(256), 0, s, (const vad_bf16*)dpre32, total, 32, chunk, (const float*)nullptr, cws);
+        else hipLaunchKernelGGL(chan_sums_kernel<float>, dim3(cb), dim3(256), 0, s, (const float*)dpre32, total, 32, chunk, (const float*)nullptr, cws);
+        VAD_LAUNCH_CHECK();
+        hipLaunchKernelGGL(chan_finalize_kernel, dim3(32), dim3(256), 0, s, (const float*)cws, cb, 32, (double)total, 2, 0.f, 0.f,
+                           (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, colsum, (const float*)nullptr);
+        VAD_LAUNCH_CHECK();
+        hipLaunchKernelGGL(to3_dbias_kernel, dim3(1), dim3(64), 0, s, (const float*)colsum, dbias3);
+        VAD_LAUNCH_CHECK();
+    }
     return VAD_OK;
 }
 

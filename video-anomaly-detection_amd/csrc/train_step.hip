@@ -1,6 +1,8 @@
 // One optimisation step of the ConvLSTM video autoencoder (reference train_video.py:44-65: model.train(); out = model(x);
 // loss = MSELoss(out, x); zero_grad; backward; Adam.step) as an explicit launch sequence over the kernels of
 // train_ops.hip and the forward convolution kernels.  Host orchestration only: no kernels in this file.
+// The `_l` entry points take the criterion as an argument: nn.MSELoss (the reference's), or the SSIMLoss / CombinedLoss of
+// utils/losses.py on the frames of the batch as one [B*T,3,H,W] batch (csrc/ssim.hip), as the image step offers them.
 //
 // Parameters live in ONE flat fp32 buffer in torch layouts and torch named_parameters() order, gradients in a buffer of
 // the same shape (the Python module's nn.Parameters are views into them), so the optimiser is one launch and a
@@ -43,13 +45,17 @@ struct Plan {
     size_t pk_e[4], pk_e_dg[4], pk_l[8], pk_l_dg[8], pk_d[3], pk_d_dg[3];
     size_t y[4], a[3], st_e[4], cat[8], z[8], c[8], hseq, pseq, pk_pj, pk_pj_dg, u[3], r[3], st_d[3], dpre;
     size_t g[3], dcat[8], dzl[8], dc[8], ksums, zeros, chan_ws, wgrad_ws, to3_ws;
+    int kind;                                    // criterion: 0 mse, 1 ssim, 2 combined
+    size_t recon, drecon, ssim_ws, out3, ones;   // kind != 0 only, behind everything else
     size_t ws_floats;
     int lstm_cin(int l) const { return l == 0 ? L : Hd; }
 };
 
 size_t align64(size_t v) { return (v + 63) & ~(size_t)63; }
 
-bool make_plan(Plan& p, int B, int T, int H, int W, int L, int Hd, int NL) {
+bool make_plan(Plan& p, int B, int T, int H, int W, int L, int Hd, int NL, int kind = 0) {
+    if (kind < 0 || kind > 2) return false;
+    p.kind = kind;
     if (B <= 0 || T <= 0 || H <= 0 || W <= 0 || H % 16 || W % 16 || L <= 0 || L % 32 || Hd <= 0 || Hd % 32 || Hd > 256 || NL < 1 || NL > 8) return false;
     if ((long long)B * T > (1 << 20)) return false;
     p.B = B; p.T = T; p.H = H; p.W = W; p.L = L; p.Hd = Hd; p.NL = NL; p.N = B * T;
@@ -165,7 +171,17 @@ bool make_plan(Plan& p, int B, int T, int H, int W, int L, int Hd, int NL) {
     for (int j = 0; j < 3; ++j) { const size_t v = vad_convt2x2_stats_floats(p.decC[j + 1]); if (v > max_chan) max_chan = v; }  // and the decoder's transposed ones
     p.chan_ws = take(max_chan);
     p.wgrad_ws = take(max_wgrad);
-    p.to3_ws = take(vad_convt_to3_mse_ws_floats(p.N, H / 2, W / 2));
+    p.to3_ws = take(vad_convt_to3_mse_ws_floats(p.N, H / 2, W / 2));      // (holds vad_convt_to3_tanh_bwd_ws_floats too: the same minus the loss partials)
+    p.recon = p.drecon = p.ssim_ws = p.out3 = p.ones = 0;
+    if (kind != 0) {      // the SSIM / combined criteria: reconstruction, its gradient, the criterion's scratch and device scalars
+        const size_t img = N * 3 * (size_t)H * W;
+        p.recon = take(img);
+        p.drecon = take(img);
+        const size_t sf = vad_ssim_workspace_floats((long long)N * 3, H, W), sb = vad_ssim_grad_workspace_floats((long long)N * 3, H, W);
+        p.ssim_ws = take(sf > sb ? sf : sb);
+        p.out3 = take(64);
+        p.ones = take(64);
+    }
     p.ws_floats = w;
     return true;
 }
@@ -239,9 +255,13 @@ extern "C" size_t vad_vid_train_nstats(int latent, int hid, int layers) {
     return make_plan(p, 1, 1, 16, 16, latent, hid, layers) ? p.nstats : 0;
 }
 
-extern "C" size_t vad_vid_train_workspace_bytes(int b, int t, int h, int w, int latent, int hid, int layers) {
+extern "C" size_t vad_vid_train_workspace_bytes_l(int b, int t, int h, int w, int latent, int hid, int layers, int loss_kind) {
     Plan p;
-    return make_plan(p, b, t, h, w, latent, hid, layers) ? p.ws_floats * sizeof(float) : 0;
+    return make_plan(p, b, t, h, w, latent, hid, layers, loss_kind) ? p.ws_floats * sizeof(float) : 0;
+}
+
+extern "C" size_t vad_vid_train_workspace_bytes(int b, int t, int h, int w, int latent, int hid, int layers) {
+    return vad_vid_train_workspace_bytes_l(b, t, h, w, latent, hid, layers, 0);
 }
 
 // Debug: float offsets of the saved forward buffers inside the workspace, in the order
@@ -272,7 +292,19 @@ extern "C" int vad_vid_train_debug_layout(int b, int t, int h, int w, int latent
 extern "C" int vad_vid_train_fwd_bwd(const float* x, int b, int t, int h, int w, int latent, int hid, int layers,
                                      const float* params, float* grads, float* running, void* workspace, size_t workspace_bytes,
                                      int precision, float* loss, float* recon, void* stream) {
+    return vad_vid_train_fwd_bwd_l(x, b, t, h, w, latent, hid, layers, params, grads, running, workspace, workspace_bytes, 0, 0.f, 11,
+                                   precision, loss, recon, stream);
+}
+
+// loss_kind: 0 = nn.MSELoss (train_video.py:175), 1 = SSIMLoss(window), 2 = CombinedLoss(alpha, window) - vad_img_train_fwd_bwd's
+extern "C" int vad_vid_train_fwd_bwd_l(const float* x, int b, int t, int h, int w, int latent, int hid, int layers,
+                                       const float* params, float* grads, float* running, void* workspace, size_t workspace_bytes,
+                                       int loss_kind, float alpha, int window_size, int precision, float* loss, float* recon, void* stream) {
     VAD_REQUIRE(x && params && grads && workspace && loss, "vid_train_fwd_bwd: null pointer");
+    VAD_REQUIRE(loss_kind >= 0 && loss_kind <= 2, "vid_train_fwd_bwd: loss_kind must be 0 (mse), 1 (ssim) or 2 (combined)");
+    // (vad_ssim_mse's own window contract, said here: a refusal in the middle of the step would leave it half done)
+    VAD_REQUIRE(loss_kind == 0 || (window_size >= 1 && (window_size & 1) && window_size <= 15),
+                "vid_train_fwd_bwd: window_size=%d must be odd and at most 15", window_size);
     VAD_REQUIRE(precision >= VAD_PREC_FP32 && precision <= VAD_PREC_WINO, "vid_train_fwd_bwd: precision=%d must be 0 (fp32), 1 (split fp16), 2 (bf16 operands), 3 (bf16 tensors) or 4 (Winograd)", precision);
     // VAD_PREC_WINO: the 3x3 convolutions behind the first layer - forward and data gradients, the ConvLSTM gate convolutions
     // included - in Winograd F(2x2,3x3) form on the exact-fp32 matrix pipe (csrc/conv_wino.hip); everything else is the
@@ -293,7 +325,7 @@ extern "C" int vad_vid_train_fwd_bwd(const float* x, int b, int t, int h, int w,
     // tensor of the workspace stored as bf16 (the buffers keep their fp32-sized slots and use the first half), the 1x1
     // data gradients and the first layer's forward on bf16 operands too.
     Plan p;
-    VAD_REQUIRE(make_plan(p, b, t, h, w, latent, hid, layers),
+    VAD_REQUIRE(make_plan(p, b, t, h, w, latent, hid, layers, loss_kind),
                 "vid_train_fwd_bwd: unsupported configuration (B=%d T=%d %dx%d latent=%d hid=%d layers=%d): H, W multiples of 16, "
                 "latent and hidden multiples of 32, hidden <= 256, 1..8 layers", b, t, h, w, latent, hid, layers);
     if (workspace_bytes < p.ws_floats * sizeof(float))
@@ -432,8 +464,20 @@ extern "C" int vad_vid_train_fwd_bwd(const float* x, int b, int t, int h, int w,
         (void)frexp((double)N * 3.0 * H * W, &e);            // count = m 2^e, m in [0.5, 1)
         grad_mul = (float)ldexp(1.0, e - 7);                  // 2 / count * 2^(e-7) = 2^-6 / m
     }
-    { PS(TS_LOSS);
+    if (loss_kind == 0) { PS(TS_LOSS);
     TRY(vad_convt_to3_mse_t(A(p.r[2]), io, P + p.t_w, P + p.t_b, x, recon, g0, A(p.dpre), loss, G + p.t_b, ws + p.to3_ws, N, H / 2, W / 2, grad_mul, s)); }
+    else {
+        // SSIM / combined (utils/losses.py:51-121 on [B*T,3,H,W]): a pixel's gradient depends on its window, so the layer runs as
+        // forward, criterion, backward; the criterion is fp32 in every mode and, like the MSE's, O(1 / count) - the same grad_mul
+        PS(TS_LOSS);
+        float* rec = recon ? recon : ws + p.recon;
+        const float a = loss_kind == 1 ? 1.f : alpha;
+        TRY(vad_convt_to3_tanh_fwd_t(A(p.r[2]), io, P + p.t_w, P + p.t_b, rec, N, H / 2, W / 2, s));
+        TRY(vad_ssim_mse(rec, x, (long long)N * 3, H, W, window_size, a, ws + p.ssim_ws, ws + p.out3, s));
+        TRY(vad_train_set_scalars(ws + p.ones, ws + p.out3, loss_kind == 1 ? 0 : 2, loss, s));
+        TRY(vad_ssim_mse_backward(rec, x, (long long)N * 3, H, W, window_size, a, ws + p.ones, ws + p.ssim_ws, ws + p.drecon, s));
+        TRY(vad_convt_to3_tanh_bwd_t(rec, ws + p.drecon, P + p.t_w, g0, A(p.dpre), io, G + p.t_b, ws + p.to3_ws, N, H / 2, W / 2, grad_mul, s));
+    }
 
     if (g_vad_train_stop == 20) return VAD_OK;      // debug: g0 = gradient of the last decoder activation, dpre intact
 

@@ -126,6 +126,13 @@ __global__ void set_scalars_kernel(float* ones, const float* out3, int which, fl
 
 }  // namespace
 
+// the criterion's device scalars, for both training steps: loss = out3[which] of vad_ssim_mse, upstream gradient ones[0] = 1
+int vad_train_set_scalars(float* ones, const float* out3, int which, float* loss, void* stream) {
+    hipLaunchKernelGGL(set_scalars_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, ones, out3, which, loss);
+    VAD_LAUNCH_CHECK();
+    return VAD_OK;
+}
+
 #define TRY(expr)                      \
     do {                               \
         const int rc_ = (expr);        \
@@ -229,8 +236,7 @@ extern "C" int vad_img_train_fwd_bwd(const float* x, int n, int h, int w, int la
     } else {
         const float a = loss_kind == 1 ? 1.f : alpha;
         TRY(vad_ssim_mse(recon, x, (long long)N * 3, H, W, window_size, a, ws + p.ssim_ws, ws + p.out3, s));
-        hipLaunchKernelGGL(set_scalars_kernel, dim3(1), dim3(64), 0, s, ws + p.ones, (const float*)(ws + p.out3), loss_kind == 1 ? 0 : 2, loss);
-        VAD_LAUNCH_CHECK();
+        TRY(vad_train_set_scalars(ws + p.ones, ws + p.out3, loss_kind == 1 ? 0 : 2, loss, s));
         TRY(vad_ssim_mse_backward(recon, x, (long long)N * 3, H, W, window_size, a, ws + p.ones, ws + p.ssim_ws, ws + p.drecon, s));
         drecon = ws + p.drecon;
     }

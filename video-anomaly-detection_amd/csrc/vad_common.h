@@ -199,6 +199,10 @@ int vad_convt2x2_to3_score_fmt(const float* in, const float* w_iohw, const float
 int vad_dec4_score_fmt(const float* in, const float* wt_packed, const float* bt, const float* w2_gemm, const float* bias3,
                        const void* x, int fmt, float* partials, float* recon, float* errmap, int n, int h, int w, void* stream);
 
+// csrc/train_step_img.hip: the device scalar hand-off between vad_ssim_mse and vad_ssim_mse_backward in a training step
+// (ones[0] = 1, loss[0] = out3[which]); shared by the image and the video step
+int vad_train_set_scalars(float* ones, const float* out3, int which, float* loss, void* stream);
+
 // per-layer profiling hooks (vad_api.hip)
 struct VadProfScope {
     int slot;

@@ -168,6 +168,9 @@ SIGNATURES = {
     "vad_lstm_gates_bwd_t": (_i, [_vp, _i, _vp, _vp, _vp, _ll, _i, _vp, _ll, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "vad_conv_c3_wgrad_t": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
     "vad_convt_to3_mse_t": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
+    "vad_convt_to3_tanh_bwd_ws_floats": (_sz, [_i, _i, _i]),
+    "vad_convt_to3_tanh_fwd_t": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "vad_convt_to3_tanh_bwd_t": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _f, _vp]),
     "vad_scale_floats": (_i, [_vp, _ll, _f, _vp]),
     "vad_train_pack_conv1x1_p": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp]),
     "vad_conv1x1_p": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i, _i, _vp]),
@@ -201,6 +204,8 @@ SIGNATURES = {
     "vad_split_grad_scale_enabled": (_i, []),
     "vad_vid_train_debug_layout": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _i]),
     "vad_vid_train_fwd_bwd": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _i, _vp, _vp, _vp]),
+    "vad_vid_train_workspace_bytes_l": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i]),
+    "vad_vid_train_fwd_bwd_l": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _i, _f, _i, _i, _vp, _vp, _vp]),
     "vad_img_train_nparams": (_sz, [_i]),
     "vad_img_train_nstats": (_sz, [_i]),
     "vad_img_train_workspace_bytes": (_sz, [_i, _i, _i, _i]),

@@ -6,9 +6,9 @@ Replaces the body of the reference's `train_one_epoch` loop (train_video.py:50-6
     optimizer.zero_grad(); loss.backward(); optimizer.step()                              # Adam(lr, weight_decay=1e-5)
 
 with `loss = trainer.step(sequences)`: forward in train() semantics (batch-statistics BatchNorm, running stats and
-num_batches_tracked updated), MSE loss, the whole backward and the Adam update run as hand-written HIP kernels through
-`vad_vid_train_fwd_bwd` + `vad_adam_step` (csrc/train_step.hip, csrc/train_ops.hip); there is no autograd graph and no
-CPU fallback.  The model's `nn.Parameter`s and BatchNorm buffers are re-pointed to views of flat device buffers, so
+num_batches_tracked updated), the criterion (MSE as in the reference; SSIMLoss / CombinedLoss of utils/losses.py on request),
+the whole backward and the Adam update run as hand-written HIP kernels through `vad_vid_train_fwd_bwd_l` + `vad_adam_step`
+(csrc/train_step.hip, csrc/train_ops.hip, csrc/ssim.hip); there is no autograd graph and no CPU fallback.  The model's `nn.Parameter`s and BatchNorm buffers are re-pointed to views of flat device buffers, so
 `state_dict()`, `load_state_dict()`, checkpoints and the eval-mode scoring path keep working on the same storage, the
 optimiser is one launch, and data-parallel training needs exactly one gradient all-reduce per step (RCCL through
 torch.distributed; BatchNorm statistics stay per rank, the reference has no SyncBN).
@@ -63,6 +63,13 @@ class _FlatTrainer:
 
     #: issue the gradient all-reduce in a one-rank process group too (tests: the RCCL call path on a one-GPU box)
     force_collective = False
+    #: `loss=` of both trainers -> loss_kind of the C ABI
+    _KINDS = {"mse": 0, "ssim": 1, "combined": 2}
+
+    def _set_criterion(self, loss, ssim_weight, window_size) -> None:
+        if loss not in self._KINDS:
+            raise hip.VadError(f"loss must be one of {sorted(self._KINDS)}, got {loss!r}")
+        self.loss, self.ssim_weight, self.window_size = loss, float(ssim_weight), int(window_size)
 
     def __init__(self, model: nn.Module, nparams: int, nstats: int, lr, weight_decay, betas, eps, process_group):
         params = list(model.parameters())
@@ -205,10 +212,13 @@ class _FlatTrainer:
 
 
 class VideoTrainer(_FlatTrainer):
-    """Adam-on-MSE training steps for a `VideoAutoencoder` living on a GPU (exact fp32, or split-fp16 convolutions)."""
+    """Native training steps for a `VideoAutoencoder` living on a GPU (reference train_video.py:44-65): Adam on `loss` = 'mse'
+    (train_video.py's criterion), 'ssim' or 'combined' (utils/losses.py, `ssim_weight` = alpha) - the criteria `ImageTrainer`
+    offers, taken over the frames of the batch as one [B*T,3,H,W] batch, which is how `scoring.validate` evaluates them."""
 
     def __init__(self, model: VideoAutoencoder, lr: float = 1e-4, weight_decay: float = 1e-5, betas=(0.9, 0.999),
-                 eps: float = 1e-8, process_group=None, precision: str = "fp32"):
+                 eps: float = 1e-8, process_group=None, precision: str = "fp32", loss: str = "mse", ssim_weight: float = 0.5,
+                 window_size: int = 11):
         self._check_model(model, VideoAutoencoder, "VideoTrainer")
         #: "fp32": exact fp32 everywhere (default, the parity path).  "split": the 3x3 / transposed convolutions (forward
         #: and data gradients) use split-fp16 operands - 22-bit products, fp32 accumulate - everything else stays fp32.
@@ -218,6 +228,7 @@ class VideoTrainer(_FlatTrainer):
         #: parameter gradients, loss and Adam stay fp32.  "bf16_operands" (round 2's form, kept for A/B): fp32 tensors in
         #: HBM, converted to bf16 while they are staged.  Both are gated by loss-curve agreement, not parity
         self.precision = hip.training_precision(precision, "VideoTrainer", tensors=True)
+        self._set_criterion(loss, ssim_weight, window_size)
         l = hip.lib()
         self.cfg = (model.latent_dim, model.lstm_hidden_dim, model.lstm_num_layers)
         super().__init__(model, l.vad_vid_train_nparams(*self.cfg), l.vad_vid_train_nstats(*self.cfg), lr, weight_decay, betas, eps,
@@ -225,13 +236,13 @@ class VideoTrainer(_FlatTrainer):
 
     # ------------------------------------------------------------------------------------------------------------
     def _workspace(self, b, t, h, w) -> torch.Tensor:
-        nbytes = hip.lib().vad_vid_train_workspace_bytes(b, t, h, w, *self.cfg)
+        nbytes = hip.lib().vad_vid_train_workspace_bytes_l(b, t, h, w, *self.cfg, self._KINDS[self.loss])
         if nbytes == 0:
             raise hip.VadError(f"unsupported training shape B={b} T={t} {h}x{w}: H and W must be multiples of 16")
         return self._ensure_ws(nbytes)
 
     def forward_backward(self, clips: torch.Tensor, recon: bool = False):
-        """Loss and gradients of one batch (train-mode forward, MSE, full backward) without the optimiser update.
+        """Loss and gradients of one batch (train-mode forward, the criterion, full backward) without the optimiser update.
         Returns (loss 0-dim device tensor, reconstruction or None); gradients are in `p.grad` of every parameter."""
         if clips.dim() != 5 or clips.shape[2] != 3 or not clips.is_cuda:
             raise hip.VadError(f"expected GPU clips [B,T,3,H,W], got {tuple(clips.shape)} on {clips.device}")
@@ -241,9 +252,10 @@ class VideoTrainer(_FlatTrainer):
         out = torch.empty_like(x) if recon else None
         l = hip.lib()
         with torch.cuda.device(self.device):
-            hip.check(l.vad_vid_train_fwd_bwd(x.data_ptr(), b, t, h, w, *self.cfg, self.flat.data_ptr(), self.grad.data_ptr(),
-                                              self.running.data_ptr(), ws.data_ptr(), ws.numel(), hip.precision_mode(self.precision),
-                                              self._loss.data_ptr(), hip.ptr(out), hip.current_stream()), "vad_vid_train_fwd_bwd")
+            hip.check(l.vad_vid_train_fwd_bwd_l(x.data_ptr(), b, t, h, w, *self.cfg, self.flat.data_ptr(), self.grad.data_ptr(),
+                                                self.running.data_ptr(), ws.data_ptr(), ws.numel(), self._KINDS[self.loss],
+                                                self.ssim_weight, self.window_size, hip.precision_mode(self.precision),
+                                                self._loss.data_ptr(), hip.ptr(out), hip.current_stream()), "vad_vid_train_fwd_bwd_l")
         self._after_forward_backward("train_step")
         return self._loss[0].clone(), out
 
@@ -251,8 +263,6 @@ class VideoTrainer(_FlatTrainer):
 class ImageTrainer(_FlatTrainer):
     """Native training step for `ConvAutoencoder` (reference train.py:28-52): `loss` is 'mse' (train.py's default),
     'ssim' or 'combined' (train.py:149-158, `--ssim-weight` = alpha); Adam(lr 1e-3, weight_decay 1e-5) as in train.py:159."""
-
-    _KINDS = {"mse": 0, "ssim": 1, "combined": 2}
 
     def __init__(self, model, lr: float = 1e-3, weight_decay: float = 1e-5, betas=(0.9, 0.999), eps: float = 1e-8,
                  process_group=None, loss: str = "mse", ssim_weight: float = 0.5, window_size: int = 11, precision: str = "fp32"):
@@ -263,9 +273,7 @@ class ImageTrainer(_FlatTrainer):
         #: "bf16" / "bf16_tensors" name the bf16-TENSOR mode of `VideoTrainer` and are rejected here by name: the image
         #: step has no such form (round 3 accepted "bf16" here with the operand meaning - the same string, other arithmetic)
         self.precision = hip.training_precision(precision, "ImageTrainer", tensors=False)
-        if loss not in self._KINDS:
-            raise hip.VadError(f"loss must be one of {sorted(self._KINDS)}, got {loss!r}")
-        self.loss, self.ssim_weight, self.window_size = loss, float(ssim_weight), int(window_size)
+        self._set_criterion(loss, ssim_weight, window_size)
         l = hip.lib()
         self.latent = model.latent_dim
         super().__init__(model, l.vad_img_train_nparams(self.latent), l.vad_img_train_nstats(self.latent), lr, weight_decay, betas, eps,
