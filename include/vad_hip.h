@@ -655,6 +655,32 @@ size_t vad_resize_workspace_bytes(long long n, int in_h, int in_w, int out_h, in
 int vad_resize_u8(const void* src, long long n, int in_h, int in_w, int channel_order, const void* plan_dev, void* dst, int out_h,
                   int out_w, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same Resize for the other pixel layouts a decoder delivers (the reference opens every file with
+ * `Image.open(path).convert('RGB')`, utils/dataset.py:141, utils/video_dataset.py:141, 295, main.py:218, and the MVTec masks with
+ * `convert('L')` + `mask_transform`, utils/dataset.py:74-77, 147-148).  Exact by construction: PIL's L -> RGB replicates the
+ * channel, RGBA -> RGB drops alpha, and the resample treats channels independently.
+ *   pixel_format   src (uint8, contiguous)                          dst (uint8)
+ *   VAD_PIX_RGB    [n, in_h, in_w, 3]                               [n, out_h, out_w, 3]   = vad_resize_u8, channel_order 0
+ *   VAD_PIX_BGR    [n, in_h, in_w, 3]                               [n, out_h, out_w, 3]   = vad_resize_u8, channel_order 1
+ *   VAD_PIX_L      [n, in_h, in_w]       one byte per pixel         [n, out_h, out_w, out_channels]: out_channels 3 = the resized
+ *                                                                   plane in all three channels (`convert('RGB')`), 1 = the plane (masks)
+ *   VAD_PIX_RGBA   [n, in_h, in_w, 4]    fourth byte ignored        [n, out_h, out_w, 3]
+ *   VAD_PIX_BGRA   [n, in_h, in_w, 4]    fourth byte ignored        [n, out_h, out_w, 3], B and R exchanged as VAD_PIX_BGR does
+ * out_channels is 3, or 1 with VAD_PIX_L; anything else, and an unknown format, is refused before any launch.  The plan blob is
+ * the one vad_resize_plan makes (the coefficients depend on the axis lengths only), with the same host checks and the same
+ * on-device header check: a plan of another geometry gives zeros.  Workspace: the horizontal pass's result, ONE byte per pixel
+ * for VAD_PIX_L (the value is replicated on the last store) and three otherwise; vad_resize_workspace_bytes_f (0 for arguments
+ * the launcher refuses and when at most one axis changes).  With both passes skipped dst is the replicated / alpha-stripped /
+ * swapped copy. */
+#define VAD_PIX_RGB 0
+#define VAD_PIX_BGR 1
+#define VAD_PIX_L 2
+#define VAD_PIX_RGBA 3
+#define VAD_PIX_BGRA 4
+size_t vad_resize_workspace_bytes_f(long long n, int in_h, int in_w, int out_h, int out_w, int pixel_format, int out_channels);
+int vad_resize_u8_f(const void* src, long long n, int in_h, int in_w, int pixel_format, const void* plan_dev, void* dst, int out_h,
+                    int out_w, int out_channels, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ hipGraph capture / replay of a scoring call
  * vad_graph_begin(stream); <one vad_img_score* / vad_vid_score* call on `stream`>; vad_graph_end(stream, &exec) captures
  * the call's launch sequence (kernels, and the fork / join with the library's helper streams) into an instantiated

@@ -11,7 +11,12 @@ to SxS (default 256), in one run:
 Device-event timing around back-to-back calls after warm-up; alternatives alternate `--repeats` times, best and worst are
 reported.  Prints one JSON line.
 
-    python tools/resize_bench.py [--size 256] [--iters 20] [--warmup 5] [--repeats 3] [--max-gb 4] [--no-pil]
+`--format` names the pixel layout(s) of the raw frames (`FrameResizer(pixel_format=)`: rgb, bgr, l, rgba, bgra).  With several,
+part 1 alternates them on the same resolution and frame count within one run (the 3-byte formats are the unchanged
+`vad_resize_u8` path: the yardstick of the others), and parts 2 and 3 run once per format; the CPU route then opens the frame
+as PIL would (`convert('RGB')` before the resize).
+
+    python tools/resize_bench.py [--size 256] [--iters 20] [--warmup 5] [--repeats 3] [--max-gb 4] [--no-pil] [--format rgb l rgba]
 """
 import argparse
 import importlib
@@ -27,6 +32,12 @@ import torch
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 vad = importlib.import_module("video-anomaly-detection_amd")
 RES = {"480p": (480, 640), "720p": (720, 1280), "1080p": (1080, 1920), "2160p": (2160, 3840)}
+FORMATS = {"rgb": (3, "RGB"), "bgr": (3, "RGB"), "l": (1, "L"), "rgba": (4, "RGBA"), "bgra": (4, "RGBA")}     # bytes per pixel, PIL mode
+
+
+def raw_frames(fmt: str, n: int, h: int, w: int, gen) -> torch.Tensor:
+    bpp = FORMATS[fmt][0]
+    return torch.randint(0, 256, (n, h, w) if bpp == 1 else (n, h, w, bpp), dtype=torch.uint8, device="cuda", generator=gen)
 
 
 def timed(fn, iters: int, warmup: int) -> float:
@@ -69,6 +80,62 @@ def load(model, seed):
     return model.cuda().eval()
 
 
+def score_parts(args, out, name, fmt, img, vid, gen) -> None:
+    """Parts 2 and 3 for one resolution and one pixel format."""
+    (h, w), S, n = RES[name], args.size, args.score_frames
+    bpp, mode = FORMATS[fmt]
+    pix = () if bpp == 1 else (bpp,)
+    # ---- 2. raw frames -> scores against already-resized frames on the same tree
+    raw = raw_frames(fmt, n, h, w, gen)
+    rz = vad.scoring.FrameResizer(S, pixel_format=fmt)
+    small = rz(raw).clone()
+    b = max(1, n // 16)
+    raw_c, small_c = raw[:b * 16].view(b, 16, h, w, *pix), small[:b * 16].view(b, 16, S, S, 3)
+    with torch.no_grad():
+        assert torch.equal(vad.scoring.score_raw_images(img, raw, resizer=rz), img.get_reconstruction_error(small))
+        state = vid.score_stateful(small_c[:1, :15])["state"]
+        forms = {
+            "images": (lambda: vad.scoring.score_raw_images(img, raw, resizer=rz), lambda: img.get_reconstruction_error(small), n),
+            "clips": (lambda: vad.scoring.score_raw_clips(vid, raw_c, resizer=rz), lambda: vid.get_reconstruction_error(small_c), b * 16),
+            "stateful_1": (lambda: vid.score_stateful(rz(raw_c[:1, 15:]), state), lambda: vid.score_stateful(small_c[:1, 15:], state), 1),
+        }
+        for form, (f_raw, f_small, frames) in forms.items():
+            r = alternate({"raw": f_raw, "resized": f_small}, args.repeats, lambda fn: timed(fn, args.iters, args.warmup))
+            out["scores"].append({"res": name, "format": fmt, "form": form, "frames": frames, "raw_ms": round(r["raw"][0], 4),
+                                  "raw_ms_max": round(r["raw"][1], 4), "resized_ms": round(r["resized"][0], 4),
+                                  "resized_ms_max": round(r["resized"][1], 4), "ratio": round(r["raw"][0] / r["resized"][0], 4)})
+        # ---- 3. CPU resize + upload of small frames against raw frames uploaded from pinned memory
+        host_raw = raw.cpu().pin_memory()
+        dev_raw = torch.empty_like(raw)
+
+        def new_route():
+            dev_raw.copy_(host_raw, non_blocking=True)
+            return vad.scoring.score_raw_images(img, dev_raw, resizer=rz)
+        routes = {"pinned_raw_upload_resize_score": new_route}
+        pool = None
+        if not args.no_pil:
+            from PIL import Image
+            frames_np = [f for f in host_raw.numpy()]
+            pool = ThreadPoolExecutor(max_workers=16)
+
+            def pil_small(f):                     # what the reference does with a decoded frame: (BGR -> RGB,) convert('RGB'), Resize
+                if fmt in ("bgr", "bgra"):
+                    f = np.ascontiguousarray(f[..., [2, 1, 0, 3][:bpp]])
+                return np.asarray(Image.fromarray(f, mode).convert("RGB").resize((S, S), Image.BILINEAR))
+
+            def pil_route():
+                return img.get_reconstruction_error(torch.from_numpy(np.stack(list(pool.map(pil_small, frames_np)))).cuda())
+            assert torch.equal(pil_route(), new_route())
+            routes["pil_16_threads_upload_score"] = pil_route
+        r = alternate(routes, args.repeats, lambda fn: wall(fn, max(3, args.iters // 4), 2))
+        row = {"res": name, "format": fmt, "frames": n, "raw_bytes_per_frame": h * w * bpp}
+        for k, (lo, hi) in r.items():
+            row[k + "_ms"], row[k + "_ms_max"], row[k + "_frames_per_s"] = round(lo, 3), round(hi, 3), round(n / lo * 1e3, 1)
+        out["routes"].append(row)
+        if pool is not None:
+            pool.shutdown()
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=256)
@@ -81,75 +148,40 @@ def main() -> None:
     ap.add_argument("--hbm-tbps", type=float, default=6.29)
     ap.add_argument("--score-frames", type=int, default=64, help="images per call in parts 2 and 3 (clips: /16 clips of 16)")
     ap.add_argument("--no-pil", action="store_true")
+    ap.add_argument("--format", nargs="+", default=["rgb"], choices=list(FORMATS), help="pixel layout(s) of the raw frames")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("resize_bench needs a GPU: a time is measured on the device or not at all")
     S, lib = args.size, vad.hip.lib()
     gen = torch.Generator(device="cuda").manual_seed(1)
-    out = {"tool": "resize_bench", "size": S, "device": torch.cuda.get_device_name(0), "iters": args.iters, "repeats": args.repeats,
+    codes = {k: v[0] for k, v in vad.scoring.PIXEL_FORMATS.items()}
+    widest = max(FORMATS[f][0] for f in args.format)
+    out = {"tool": "resize_bench", "size": S, "formats": args.format, "device": torch.cuda.get_device_name(0), "iters": args.iters, "repeats": args.repeats,
            "hbm_tbps": args.hbm_tbps, "resize": [], "scores": [], "routes": []}
     img, vid = load(vad.ConvAutoencoder(), 1), load(vad.VideoAutoencoder(), 2)
     for name in args.res:
         h, w = RES[name]
         # ---- 1. resize alone
         for n in args.frames:
-            n = max(1, min(n, int(args.max_gb * 1e9 // (h * w * 3))))
-            x = torch.randint(0, 256, (n, h, w, 3), dtype=torch.uint8, device="cuda", generator=gen)
-            rz = vad.scoring.FrameResizer(S)
+            n = max(1, min(n, int(args.max_gb * 1e9 // (h * w * widest))))          # the same frame count for every format
             dst = torch.empty(n, S, S, 3, dtype=torch.uint8, device="cuda")
-            ms = [timed(lambda: rz(x, out=dst), args.iters, args.warmup) for _ in range(args.repeats)]
-            mid = lib.vad_resize_workspace_bytes(n, h, w, S, S)
-            moved = x.numel() + 2 * mid + dst.numel()
-            out["resize"].append({"res": name, "frames": n, "us_per_frame": round(min(ms) * 1e3 / n, 3), "us_per_frame_max": round(max(ms) * 1e3 / n, 3),
-                                  "bytes_per_frame": moved // n, "GBps": round(moved / min(ms) / 1e6, 1),
-                                  "hbm_floor_fraction": round(moved / (args.hbm_tbps * 1e12) / (min(ms) * 1e-3), 4)})
-            del x, dst, rz
-        # ---- 2. raw frames -> scores against already-resized frames on the same tree
-        n = args.score_frames
-        raw = torch.randint(0, 256, (n, h, w, 3), dtype=torch.uint8, device="cuda", generator=gen)
-        rz = vad.scoring.FrameResizer(S)
-        small = rz(raw).clone()
-        b = max(1, n // 16)
-        raw_c, small_c = raw[:b * 16].view(b, 16, h, w, 3), small[:b * 16].view(b, 16, S, S, 3)
-        with torch.no_grad():
-            assert torch.equal(vad.scoring.score_raw_images(img, raw, resizer=rz), img.get_reconstruction_error(small))
-            state = vid.score_stateful(small_c[:1, :15])["state"]
-            forms = {
-                "images": (lambda: vad.scoring.score_raw_images(img, raw, resizer=rz), lambda: img.get_reconstruction_error(small), n),
-                "clips": (lambda: vad.scoring.score_raw_clips(vid, raw_c, resizer=rz), lambda: vid.get_reconstruction_error(small_c), b * 16),
-                "stateful_1": (lambda: vid.score_stateful(rz(raw_c[:1, 15:]), state), lambda: vid.score_stateful(small_c[:1, 15:], state), 1),
-            }
-            for form, (f_raw, f_small, frames) in forms.items():
-                r = alternate({"raw": f_raw, "resized": f_small}, args.repeats, lambda fn: timed(fn, args.iters, args.warmup))
-                out["scores"].append({"res": name, "form": form, "frames": frames, "raw_ms": round(r["raw"][0], 4), "raw_ms_max": round(r["raw"][1], 4),
-                                      "resized_ms": round(r["resized"][0], 4), "resized_ms_max": round(r["resized"][1], 4),
-                                      "ratio": round(r["raw"][0] / r["resized"][0], 4)})
-            # ---- 3. CPU resize + upload of small frames against raw frames uploaded from pinned memory
-            host_raw = raw.cpu().pin_memory()
-            dev_raw = torch.empty_like(raw)
-
-            def new_route():
-                dev_raw.copy_(host_raw, non_blocking=True)
-                return vad.scoring.score_raw_images(img, dev_raw, resizer=rz)
-            routes = {"pinned_raw_upload_resize_score": new_route}
-            if not args.no_pil:
-                from PIL import Image
-                frames_np = [f for f in host_raw.numpy()]
-                pool = ThreadPoolExecutor(max_workers=16)
-
-                def pil_route():
-                    small_np = np.stack(list(pool.map(lambda f: np.asarray(Image.fromarray(f, "RGB").resize((S, S), Image.BILINEAR)), frames_np)))
-                    return img.get_reconstruction_error(torch.from_numpy(small_np).cuda())
-                assert torch.equal(pil_route(), new_route())
-                routes["pil_16_threads_upload_score"] = pil_route
-            r = alternate(routes, args.repeats, lambda fn: wall(fn, max(3, args.iters // 4), 2))
-            row = {"res": name, "frames": n}
-            for k, (lo, hi) in r.items():
-                row[k + "_ms"], row[k + "_ms_max"], row[k + "_frames_per_s"] = round(lo, 3), round(hi, 3), round(n / lo * 1e3, 1)
-            out["routes"].append(row)
-            if not args.no_pil:
-                pool.shutdown()
-        del raw, small, dev_raw, host_raw
+            fns, moved = {}, {}
+            for fmt in args.format:
+                x = raw_frames(fmt, n, h, w, gen)
+                rz = vad.scoring.FrameResizer(S, pixel_format=fmt)
+                fns[fmt] = lambda rz=rz, x=x: rz(x, out=dst)
+                moved[fmt] = x.numel() + 2 * lib.vad_resize_workspace_bytes_f(n, h, w, S, S, codes[fmt], 3) + dst.numel()
+                del x, rz
+            r = alternate(fns, args.repeats, lambda fn: timed(fn, args.iters, args.warmup))
+            for fmt, (lo, hi) in r.items():
+                out["resize"].append({"res": name, "format": fmt, "frames": n, "us_per_frame": round(lo * 1e3 / n, 3),
+                                      "us_per_frame_max": round(hi * 1e3 / n, 3), "bytes_per_frame": moved[fmt] // n,
+                                      "GBps": round(moved[fmt] / lo / 1e6, 1),
+                                      "hbm_floor_fraction": round(moved[fmt] / (args.hbm_tbps * 1e12) / (lo * 1e-3), 4)})
+            del fns, dst
+        for fmt in args.format:
+            score_parts(args, out, name, fmt, img, vid, gen)
+        print(f"resize_bench: {name} done", file=sys.stderr, flush=True)
     print(json.dumps(out))
 
 

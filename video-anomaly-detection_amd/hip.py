@@ -261,6 +261,8 @@ SIGNATURES = {
     "vad_resize_plan": (_i, [_i, _i, _i, _i, _vp]),
     "vad_resize_workspace_bytes": (_sz, [_ll, _i, _i, _i, _i]),
     "vad_resize_u8": (_i, [_vp, _ll, _i, _i, _i, _vp, _vp, _i, _i, _vp, _sz, _vp]),
+    "vad_resize_workspace_bytes_f": (_sz, [_ll, _i, _i, _i, _i, _i, _i]),
+    "vad_resize_u8_f": (_i, [_vp, _ll, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
     "vad_graph_begin": (_i, [_vp]),
     "vad_graph_end": (_i, [_vp, C.POINTER(_vp)]),
     "vad_graph_launch": (_i, [_vp, _vp]),

@@ -85,16 +85,18 @@ def score_clips(model, loader: Iterable[dict], device, per_frame: bool = False):
 
 
 def score_frames_stateful(model, frame_iter: Iterable, batch: int = 1, state=None, device=None, image_size=None,
-                          channel_order: str = "rgb"):
+                          channel_order: str = "rgb", pixel_format: Optional[str] = None):
     """Drive live streams through `VideoAutoencoder.score_stateful`: `frame_iter` yields the newest frames, one item per
     time step - `[B,C,H,W]` float (`[B,H,W,3]` uint8) for `batch` = B parallel streams, or `[B,T,...]` to hand over a few
     frames per stream at once.  Every frame goes through the encoder, ONE ConvLSTM step and the decoder once; the
     recurrent state is carried between calls (the reference's video-file mode re-scores a 16-frame window per new frame,
     evaluate_video.py:322-352).  Returns (float32[B, frames] scores, final VideoState); `state` continues earlier streams.
     With `image_size` (int or (h, w)) the items are decoded uint8 frames `[B,H,W,3]` / `[B,T,H,W,3]` at any one resolution, in
-    `channel_order` "rgb" or "bgr": they are resized on the device (`FrameResizer`, PIL-exact) before they are scored."""
+    `channel_order` "rgb" or "bgr": they are resized on the device (`FrameResizer`, PIL-exact) before they are scored.
+    `pixel_format` names another layout of the items instead (`FrameResizer`: "l" = `[B,H,W]` / `[B,T,H,W]` grey frames, "rgba" /
+    "bgra" = four bytes per pixel)."""
     scores = []
-    resizer = FrameResizer(image_size, channel_order) if image_size is not None else None
+    resizer = FrameResizer(image_size, channel_order, pixel_format) if image_size is not None else None
     with torch.no_grad():
         for frames in frame_iter:
             frames = torch.as_tensor(frames)
@@ -146,6 +148,9 @@ def validate(model, loader: Iterable[dict], device, criterion: str = "mse", ssim
 
 # ------------------------------------------------------------------------------ Resize on the device
 CHANNEL_ORDERS = {"rgb": 0, "bgr": 1}
+# include/vad_hip.h VAD_PIX_*: name -> (code, bytes per pixel, the layout as the messages spell it)
+PIXEL_FORMATS = {"rgb": (0, 3, "[..., H, W, 3]"), "bgr": (1, 3, "[..., H, W, 3]"), "l": (2, 1, "[..., H, W]"),
+                 "rgba": (3, 4, "[..., H, W, 4]"), "bgra": (4, 4, "[..., H, W, 4]")}
 
 
 class FrameResizer:
@@ -154,10 +159,16 @@ class FrameResizer:
     leading axes) and returns uint8 `[..., h, w, 3]` RGB, byte for byte what PIL's `Image.resize((w, h), BILINEAR)` gives - the
     form the models take as uint8 input.  `channel_order="bgr"` for frames as `cv2.VideoCapture` delivers them.
 
+    `pixel_format` ("rgb" | "bgr" | "l" | "rgba" | "bgra"; None = the 3-byte layout in `channel_order`) takes the frames as the
+    decoder left them, where the reference runs `Image.open(path).convert('RGB')` first: "l" is `[..., H, W]` with no channel
+    axis (`np.asarray` of a mode-L image) and comes out as the resized plane in all three channels, or with `out_channels=1` as
+    `[..., h, w, 1]` (the ground-truth masks: `resize_masks`); "rgba" / "bgra" are `[..., H, W, 4]` with the fourth byte ignored,
+    "bgra" with B and R exchanged as "bgr" does.  Each is byte for byte `convert('RGB')` (`convert('L')`) followed by the resize.
+
     The object owns the device plan blob of every input geometry it has seen (computed once on the host, like packed weights)
     and the workspace of the horizontal pass; use one per thread / stream."""
 
-    def __init__(self, size=256, channel_order: str = "rgb"):
+    def __init__(self, size=256, channel_order: str = "rgb", pixel_format: Optional[str] = None, out_channels: int = 3):
         if isinstance(size, (tuple, list)):
             if len(size) != 2:
                 raise hip.VadError(f"FrameResizer: size must be an int or (h, w), got {size!r}")
@@ -167,6 +178,15 @@ class FrameResizer:
         if channel_order not in CHANNEL_ORDERS:
             raise hip.VadError(f"FrameResizer: channel_order must be one of {sorted(CHANNEL_ORDERS)}, got {channel_order!r}")
         self.channel_order = channel_order
+        if pixel_format is not None:
+            if pixel_format not in PIXEL_FORMATS:
+                raise hip.VadError(f"FrameResizer: pixel_format must be one of {sorted(PIXEL_FORMATS)} or None, got {pixel_format!r}")
+            if channel_order != "rgb":
+                raise hip.VadError(f"FrameResizer: give channel_order={channel_order!r} or pixel_format={pixel_format!r}, not both")
+        if out_channels != 3 and not (out_channels == 1 and pixel_format == "l"):
+            raise hip.VadError(f"FrameResizer: out_channels must be 3, or 1 with pixel_format='l', got {out_channels!r} "
+                               f"with pixel_format={pixel_format!r}")
+        self.pixel_format, self.out_channels = pixel_format, int(out_channels)
         self._plans = {}
         self._ws = None
 
@@ -183,15 +203,17 @@ class FrameResizer:
     def __call__(self, frames: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
             raise hip.VadError("FrameResizer: frames must be a GPU tensor (the resize runs on the device; there is no CPU fallback)")
+        code, bpp, layout = PIXEL_FORMATS[self.pixel_format or self.channel_order]
         if frames.dtype != torch.uint8:
-            raise hip.VadError(f"FrameResizer: expected uint8 frames [..., H, W, 3], got dtype {frames.dtype}")
-        if frames.dim() < 3 or frames.shape[-1] != 3:
-            raise hip.VadError(f"FrameResizer: expected uint8 frames [..., H, W, 3], got {tuple(frames.shape)}")
+            raise hip.VadError(f"FrameResizer: expected uint8 frames {layout}, got dtype {frames.dtype}")
+        axes = 2 if bpp == 1 else 3                               # H, W and, unless a pixel is one byte, the channel axis
+        if frames.dim() < axes or (bpp != 1 and frames.shape[-1] != bpp):
+            raise hip.VadError(f"FrameResizer: expected uint8 frames {layout}, got {tuple(frames.shape)}")
         if not frames.is_contiguous():
             raise hip.VadError("FrameResizer: frames must be contiguous")
-        lead, in_h, in_w = tuple(frames.shape[:-3]), int(frames.shape[-3]), int(frames.shape[-2])
+        lead, in_h, in_w = tuple(frames.shape[:-axes]), int(frames.shape[-axes]), int(frames.shape[1 - axes])
         n = int(np.prod(lead, dtype=np.int64)) if lead else 1
-        shape = lead + (self.out_h, self.out_w, 3)
+        shape = lead + (self.out_h, self.out_w, self.out_channels)
         with torch.cuda.device(frames.device):
             plan = self._plan(in_h, in_w, frames.device)
             if out is None:
@@ -201,35 +223,54 @@ class FrameResizer:
             if n == 0:
                 return out
             l = hip.lib()
-            need = l.vad_resize_workspace_bytes(n, in_h, in_w, self.out_h, self.out_w)
+            if self.pixel_format is None:
+                need = l.vad_resize_workspace_bytes(n, in_h, in_w, self.out_h, self.out_w)
+            else:
+                need = l.vad_resize_workspace_bytes_f(n, in_h, in_w, self.out_h, self.out_w, code, self.out_channels)
             if need and (self._ws is None or self._ws.numel() < need or self._ws.device != frames.device):
                 self._ws = torch.empty(need, dtype=torch.uint8, device=frames.device)
-            hip.check(l.vad_resize_u8(frames.data_ptr(), n, in_h, in_w, CHANNEL_ORDERS[self.channel_order], plan.data_ptr(), out.data_ptr(),
-                                      self.out_h, self.out_w, self._ws.data_ptr() if need else None, need, hip.current_stream()),
-                      "vad_resize_u8")
+            ws = self._ws.data_ptr() if need else None
+            if self.pixel_format is None:
+                hip.check(l.vad_resize_u8(frames.data_ptr(), n, in_h, in_w, CHANNEL_ORDERS[self.channel_order], plan.data_ptr(), out.data_ptr(),
+                                          self.out_h, self.out_w, ws, need, hip.current_stream()), "vad_resize_u8")
+            else:
+                hip.check(l.vad_resize_u8_f(frames.data_ptr(), n, in_h, in_w, code, plan.data_ptr(), out.data_ptr(), self.out_h, self.out_w,
+                                            self.out_channels, ws, need, hip.current_stream()), "vad_resize_u8_f")
         hip.calls["resize_u8"] = hip.calls.get("resize_u8", 0) + 1
         return out
 
 
-def resize_frames(frames: torch.Tensor, size=256, channel_order: str = "rgb") -> torch.Tensor:
+def resize_frames(frames: torch.Tensor, size=256, channel_order: str = "rgb", pixel_format: Optional[str] = None,
+                  out_channels: int = 3) -> torch.Tensor:
     """One-shot form of `FrameResizer` (plans the geometry on every call: keep a FrameResizer in a loop)."""
-    return FrameResizer(size, channel_order)(frames)
+    return FrameResizer(size, channel_order, pixel_format, out_channels)(frames)
+
+
+def resize_masks(masks_u8: torch.Tensor, size=256) -> torch.Tensor:
+    """The reference's `mask_transform` (`Resize` + `ToTensor` on a `convert('L')` image, utils/dataset.py:74-77, 147-148) for
+    uint8 masks `[..., H, W]` on the GPU: float32 `[..., 1, h, w]`, PIL's L resize divided by 255 - what `errmap` / `ssim_map` are
+    compared with at the model's resolution.  The 256 quotients are computed once on the host, so they are ToTensor's floats."""
+    small = FrameResizer(size, pixel_format="l", out_channels=1)(masks_u8)
+    quotients = (torch.arange(256, dtype=torch.float32) / 255).to(small.device)
+    return quotients[small.movedim(-1, -3).long()]
 
 
 def score_raw_images(model, frames_u8: torch.Tensor, image_size=256, channel_order: str = "rgb", per_pixel: bool = False,
-                     resizer: Optional[FrameResizer] = None):
+                     resizer: Optional[FrameResizer] = None, pixel_format: Optional[str] = None):
     """Decoded uint8 images `[B, H, W, 3]` at camera resolution -> Resize on the device -> `ConvAutoencoder.
     get_reconstruction_error(per_pixel=...)`: bit for bit the scores of the frames PIL resized.  Pass a `resizer` to reuse its
-    plans and workspace across calls (its size and channel order then apply)."""
-    resizer = resizer or FrameResizer(image_size, channel_order)
+    plans and workspace across calls (its size, channel order and pixel format then apply).  `pixel_format`: `FrameResizer`'s
+    ("l": `[B, H, W]` grey images, "rgba" / "bgra": `[B, H, W, 4]`) - the scores of `convert('RGB')` + Resize."""
+    resizer = resizer or FrameResizer(image_size, channel_order, pixel_format)
     with torch.no_grad():
         return model.get_reconstruction_error(resizer(frames_u8), per_pixel=per_pixel)
 
 
 def score_raw_clips(model, clips_u8: torch.Tensor, image_size=256, channel_order: str = "rgb", per_frame: bool = False,
-                    resizer: Optional[FrameResizer] = None):
-    """Decoded uint8 clips `[B, T, H, W, 3]` -> Resize on the device -> `VideoAutoencoder.get_reconstruction_error(per_frame=...)`."""
-    resizer = resizer or FrameResizer(image_size, channel_order)
+                    resizer: Optional[FrameResizer] = None, pixel_format: Optional[str] = None):
+    """Decoded uint8 clips `[B, T, H, W, 3]` (`pixel_format` "l": `[B, T, H, W]`, "rgba" / "bgra": `[B, T, H, W, 4]`) -> Resize on
+    the device -> `VideoAutoencoder.get_reconstruction_error(per_frame=...)`."""
+    resizer = resizer or FrameResizer(image_size, channel_order, pixel_format)
     with torch.no_grad():
         return model.get_reconstruction_error(resizer(clips_u8), per_frame=per_frame)
 
