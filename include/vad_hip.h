@@ -681,6 +681,21 @@ size_t vad_resize_workspace_bytes_f(long long n, int in_h, int in_w, int out_h, 
 int vad_resize_u8_f(const void* src, long long n, int in_h, int in_w, int pixel_format, const void* plan_dev, void* dst, int out_h,
                     int out_w, int out_channels, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ Frame bank -> batch (csrc/frame_gather.hip)
+ * Decoded, resized uint8 frames stay resident in HBM (`bank`, [bank_frames, h, w, 3] contiguous; it may point into the middle
+ * of a larger allocation, at any byte address) and every batch is ONE gather: output frame i = bank frame index[i], so the
+ * overlapping sequences of the reference's datasets (utils/video_dataset.py:113-131, 240-247) are index entries, not copies.
+ *   VAD_X_F32_NCHW  out float32 [n, 3, h, w], each value ToTensor + Normalize(0.5, 0.5) of its byte, the bits of
+ *                   (u8/255 - 0.5)/0.5 evaluated step by step in fp32 - what the float entry points and the trainers take
+ *   VAD_X_U8_NHWC   out uint8 [n, h, w, 3], a plain copy - what the uint8 ingest of the scoring entry points takes
+ * index: device int64 [n].  An entry outside [0, bank_frames) is the caller's error: that output frame is neither read for nor
+ * written (it keeps what it held), nothing is read out of bounds, and the call still returns VAD_OK - the host cannot see the
+ * device's indices without a synchronisation, so validate them before upload.  Any h, w >= 1 (h * w <= 2^27); 16-byte accesses
+ * are used where the addresses allow, a plain path otherwise.  n == 0 returns VAD_OK and launches nothing.  One launch on
+ * `stream`, no allocation, no host synchronisation: capturable in a graph. */
+int vad_gather_frames_u8(const unsigned char* bank, long long bank_frames, const long long* index, long long n, int h, int w,
+                         int out_format, void* out, void* stream);
+
 /* ------------------------------------------------------------------ hipGraph capture / replay of a scoring call
  * vad_graph_begin(stream); <one vad_img_score* / vad_vid_score* call on `stream`>; vad_graph_end(stream, &exec) captures
  * the call's launch sequence (kernels, and the fork / join with the library's helper streams) into an instantiated

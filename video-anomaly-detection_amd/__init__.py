@@ -13,3 +13,6 @@ from .losses import CombinedLoss, SSIMLoss                           # noqa: F40
 from . import training                                                 # noqa: F401
 from .training import ImageTrainer, VideoTrainer                                    # noqa: F401
 from . import scoring                                                 # noqa: F401
+from .scoring import FrameResizer                                    # noqa: F401
+from . import frame_bank                                              # noqa: F401
+from .frame_bank import FrameBank                                    # noqa: F401

@@ -16,7 +16,7 @@ PKG_DIR = Path(__file__).resolve().parent
 REPO_DIR = PKG_DIR.parent
 CSRC = PKG_DIR / "csrc"
 LIB_PATH = Path(os.environ.get("VAD_LIB", PKG_DIR / "libvad_hip.so"))
-SOURCES = ["conv_mfma.hip", "conv_wino.hip", "dec4_fused.hip", "tail.hip", "wide_io.hip", "state_io.hip", "resize_u8.hip", "ssim.hip", "train_ops.hip", "wgrad.hip", "train_step.hip", "train_step_img.hip", "vad_api.hip", "pack.cpp"]
+SOURCES = ["conv_mfma.hip", "conv_wino.hip", "dec4_fused.hip", "tail.hip", "wide_io.hip", "state_io.hip", "resize_u8.hip", "frame_gather.hip", "ssim.hip", "train_ops.hip", "wgrad.hip", "train_step.hip", "train_step_img.hip", "vad_api.hip", "pack.cpp"]
 
 VAD_OK = 0
 ABI_VERSION = 3
@@ -263,6 +263,8 @@ SIGNATURES = {
     "vad_resize_u8": (_i, [_vp, _ll, _i, _i, _i, _vp, _vp, _i, _i, _vp, _sz, _vp]),
     "vad_resize_workspace_bytes_f": (_sz, [_ll, _i, _i, _i, _i, _i, _i]),
     "vad_resize_u8_f": (_i, [_vp, _ll, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
+    # frame bank -> batch (csrc/frame_gather.hip)
+    "vad_gather_frames_u8": (_i, [_vp, _ll, _vp, _ll, _i, _i, _i, _vp, _vp]),
     "vad_graph_begin": (_i, [_vp]),
     "vad_graph_end": (_i, [_vp, C.POINTER(_vp)]),
     "vad_graph_launch": (_i, [_vp, _vp]),

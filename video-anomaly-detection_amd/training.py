@@ -210,6 +210,22 @@ class _FlatTrainer:
         self.optimizer_step(1.0 / world)
         return loss
 
+    def train_epoch(self, batches) -> float:
+        """The reference's `train_one_epoch` (train_video.py:44-65, train.py:27-52) over any iterable of dict batches
+        ({'frames': ...} clips or {'image': ...} images - a `FrameBank` loader, a `DataLoader`): one `step` per batch, and the
+        average step loss as a Python float.  The step losses are added on the device in float64, in step order, and read
+        back ONCE at the end: the same sum, in the same order, as the reference's `total_loss += loss.item()` (a Python
+        float is a double), so the value is bit-equal to it without a host round trip per step."""
+        total = torch.zeros((), dtype=torch.float64, device=self.device)
+        count = 0
+        for batch in batches:
+            x = batch["frames"] if "frames" in batch else batch["image"]
+            total += self.step(x.to(self.device)).double()
+            count += 1
+        if count == 0:
+            raise ValueError("train_epoch needs at least one batch")
+        return float(total.item()) / count
+
 
 class VideoTrainer(_FlatTrainer):
     """Native training steps for a `VideoAutoencoder` living on a GPU (reference train_video.py:44-65): Adam on `loss` = 'mse'
