@@ -696,6 +696,40 @@ int vad_resize_u8_f(const void* src, long long n, int in_h, int in_w, int pixel_
 int vad_gather_frames_u8(const unsigned char* bank, long long bank_frames, const long long* index, long long n, int h, int w,
                          int out_format, void* out, void* stream);
 
+/* ------------------------------------------------------------------ Score histogram (csrc/score_hist.hip)
+ * The joint distribution of (score, label) as integer counters: everything a ranking metric needs - pixel-level AUROC of an
+ * error map / SSIM map against the ground-truth mask the reference only plots (evaluate.py:142-171), frame-level AUROC
+ * (evaluate_video.py:171-176) - accumulated batch by batch on the device; only the counters are ever read by the host.
+ *
+ * Quantiser, one parameter m = mantissa_bits in [VAD_HIST_MIN_M, VAD_HIST_MAX_M]: a finite v >= 0 (-0.0 counts as 0) falls into
+ * bin key(v) = float_bits(v) >> (23 - m), of (255 << m) bins; a <= b implies key(a) <= key(b).  A negative value, a NaN or an
+ * infinity is not binned: it increments rejected[class].
+ *
+ * State blob (caller-owned device memory, 16-byte aligned, vad_hist_state_bytes(m) bytes; 0 for an m out of range):
+ *     uint32 header[4] = {magic "VADH", abi << 16 | m, m, 0};  uint64 counts[2][nbins];  uint64 rejected[2]     (class 0, 1)
+ * vad_hist_reset writes the header and zeroes the counters.  The host checks every argument it can see and returns VAD_ERR_ARG;
+ * the header lives in device memory, so - as for the model and resize blobs - every kernel compares it with the call's m ON THE
+ * DEVICE: with a state made for another m (or not a state) the call changes nothing, and no offset of that blob is followed.
+ * Integer atomics only: the counters are exact, and identical for any batching, launch order or sharding.  All calls are
+ * asynchronous on `stream`, allocate nothing and can be captured into a graph.
+ *
+ * vad_hist_accumulate: values = n_groups * group_elems contiguous fp32 (4-byte aligned; any count), labels in label_format:
+ *   VAD_LBL_U8_ELEM   one byte per element, positive iff >= 128
+ *   VAD_LBL_F32_ELEM  one float per element, positive iff > 0.5   (what ToTensor makes of a mask: b / 255 > 0.5 iff b >= 128)
+ *   VAD_LBL_U8_GROUP  one byte per group, positive iff non-zero, applied to the group's group_elems elements (a frame's label for
+ *                     its pixels; group_elems = 1: a vector of frame scores)
+ * vad_hist_merge: dst += src, counts and rejected (two streams, or the states of several ranks after a gather). */
+#define VAD_HIST_MIN_M 4
+#define VAD_HIST_MAX_M 15
+#define VAD_LBL_U8_ELEM 0
+#define VAD_LBL_F32_ELEM 1
+#define VAD_LBL_U8_GROUP 2
+size_t vad_hist_state_bytes(int m);
+int vad_hist_reset(void* state, int m, void* stream);
+int vad_hist_accumulate(const float* values, long long n_groups, long long group_elems, const void* labels, int label_format,
+                        void* state, int m, void* stream);
+int vad_hist_merge(void* dst, const void* src, int m, void* stream);
+
 /* ------------------------------------------------------------------ hipGraph capture / replay of a scoring call
  * vad_graph_begin(stream); <one vad_img_score* / vad_vid_score* call on `stream`>; vad_graph_end(stream, &exec) captures
  * the call's launch sequence (kernels, and the fork / join with the library's helper streams) into an instantiated

@@ -14,5 +14,7 @@ from . import training                                                 # noqa: F
 from .training import ImageTrainer, VideoTrainer                                    # noqa: F401
 from . import scoring                                                 # noqa: F401
 from .scoring import FrameResizer                                    # noqa: F401
+from . import metrics                                                 # noqa: F401
+from .metrics import ScoreHistogram                                  # noqa: F401
 from . import frame_bank                                              # noqa: F401
 from .frame_bank import FrameBank                                    # noqa: F401

@@ -340,3 +340,51 @@ def score_stream(model, seed: int, n_frames: int, chunk: int = 512, h: int = 256
         return out
 
     return sharded_scores(score_block, n_frames, 1, rank, world, dev, group, force_collective)
+
+
+# ------------------------------------------------------------------------------ ranking metrics on the device
+def pixel_auroc(model, loader: Iterable[dict], device, map: str = "mse", mantissa_bits: int = 11, hist=None):
+    """Pixel-level AUROC of an image model's anomaly map against the ground-truth masks - the localisation metric of MVTec-style
+    datasets; the reference loads `sample['mask']` and only plots it beside the map (evaluate.py:142-171).  Batches are
+    {'image', 'mask', ...} as `MVTecDataset` yields them (utils/dataset.py:150-156): mask float `[B,1,H,W]` (ToTensor: a pixel is
+    anomalous iff > 0.5; `resize_masks` makes these on the device) or uint8 (iff >= 128 - the same pixels).
+    `map`: "mse" = the channel-mean squared error map of `score_all`; "ssim" = `score_criteria(ssim_map=True)['ssim_map']`, which
+    already holds 1 - SSIM per pixel (channel mean, `losses.ssim_per_frame`), so it is scored as it stands: higher = more
+    anomalous, like the error map.  It can be slightly negative where SSIM exceeds 1 by rounding; such pixels are counted in
+    `hist.rejected()`, not binned.
+    Each batch is ONE scoring call and ONE `accumulate`; no map is copied to the host - the only host read is the counters, once,
+    at the end.  Returns (auroc, tie_bound, hist) (`metrics.auroc_from_counts`); pass `hist` to continue an earlier evaluation or
+    to all-reduce before reading (`hist.all_reduce()`), in which case its own mantissa_bits applies."""
+    from . import metrics
+    if map not in ("mse", "ssim"):
+        raise hip.VadError(f"pixel_auroc: map must be 'mse' or 'ssim', got {map!r}")
+    if hist is None:
+        hist = metrics.ScoreHistogram(mantissa_bits, device)
+    with torch.no_grad():
+        for batch in loader:
+            images = batch["image"].to(device)
+            masks = torch.as_tensor(batch["mask"]).to(device)
+            if map == "mse":
+                values = model.score_all(images)["errmap"]
+            else:
+                values = model.score_criteria(images, ssim_map=True)["ssim_map"]
+            hist.accumulate(values, masks)
+    auroc, tie_bound = hist.auroc()
+    return auroc, tie_bound, hist
+
+
+def frame_auroc(model, loader: Iterable[dict], device, hist=None, mantissa_bits: int = 11):
+    """Frame-level AUROC of a video model (evaluate_video.py:171-176) without gathering the scores: the clip loop of
+    `score_clips(per_frame=True)` - batches {'frames' [B,T,C,H,W], 'frame_labels' [B,T], ...} -, each batch's frame scores and
+    labels going into a histogram on the device.  Returns (auroc, tie_bound, hist); ranks of a sharded evaluation call
+    `hist.all_reduce()` on a histogram they pass in instead of gathering score vectors."""
+    from . import metrics
+    if hist is None:
+        hist = metrics.ScoreHistogram(mantissa_bits, device)
+    with torch.no_grad():
+        for batch in loader:
+            frames = batch["frames"].to(device)
+            labels = torch.as_tensor(np.asarray(batch["frame_labels"])).to(device)
+            hist.accumulate(model.score_seq_and_frames(frames)["frame"], labels)
+    auroc, tie_bound = hist.auroc()
+    return auroc, tie_bound, hist
