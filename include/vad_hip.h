@@ -518,6 +518,38 @@ int vad_debug_set_tail_group(int frames);
 int vad_debug_set_dec4_fused(int on);
 /* rows of the dec3.3 map per work-group band of the fused kernel (0 = chosen from the batch size); results do not depend on it */
 int vad_debug_set_dec4_band(int rows);
+/* The CU count that every launch-planning decision sees: the choice between latency and throughput tilings, the small-grid
+ * ConvLSTM and transposed-convolution forms, the band height of the fused tail and the grid of every persistent kernel
+ * (CUs x resident work-groups).  0 (default) = the device's count; a value above it is refused (VAD_ERR_ARG).  With 1 a
+ * handful of small frames runs the throughput tilings, and the persistent kernels walk many frames / items per work-group -
+ * what the layer tests of tests/test_hip_persistent.py rely on.  Results never depend on it, except for the grouping of the
+ * BatchNorm partial sums of the training forward.  Size bounds (vad_*_workspace_bytes, statistics rows) ignore it. */
+int vad_debug_set_plan_cus(int cus);
+/* This thread's latest persistent layer launch: out[0] grid work-groups, [1] work items (frame walkers: frames x tiles x column
+ * blocks; item walkers: their item count), [2] independent walks (= the grid; 4 x the grid for the wave-persistent transposed
+ * convolution / bf16 1x1 kernel), [3] kernel family (1 conv3x3 / ConvLSTM step, 2 fused first layer, 3 first layer, 4
+ * convt2x2, 5 conv1x1 bf16, 6 fused dec4 tail, 7 Winograd), [4..7] the tiling MT, NT, WM, WN (conv families; dec4: band rows
+ * and strips in [4], [5]), [8] the kernel mode (conv3x3: 0 plain, 1 pool, 2 ConvLSTM; convt2x2 / conv1x1: the VAD_PREC_* of
+ * the instantiation; dec4: the input format; Winograd: 0 plain, 1 pool, 2 fused cell).  Grid 0: that launch was not persistent.
+ * The record belongs to the entry points that have a persistent form - vad_conv3x3, vad_conv3x3_c3 (_fused, _bf16, _bf16op),
+ * vad_convlstm_step, vad_convt2x2, vad_conv1x1_p, which clear it on entry, and vad_conv3x3_wino, vad_convlstm_step_wino,
+ * vad_dec4_score, which always launch a persistent kernel; every other entry point (vad_conv1x1, the *_to3_score tails, the
+ * BatchNorm / pooling passes, ...) leaves it as it was.
+ * out[9..17]: the same nine values of the thread's latest PERSISTENT launch, whatever was launched behind it (the x halves of
+ * a ConvLSTM sequence are followed by its steps).  Writes min(cap, 18) values and returns 18. */
+int vad_debug_last_plan(int out[], int cap);
+/* The statistics launches of the training forward, one layer at a time (the training steps call them internally): the
+ * un-activated, un-pooled vad_conv3x3 / vad_convt2x2 / first-layer launch (cout 32; out16: 0 fp32 output, 1 bf16 output, 2 bf16
+ * output and operands) that also writes its BatchNorm partial sums, stats[rows][2][cout] = per row the sums of (y - bias) and of
+ * (y - bias)^2 over the outputs that row's work-group (convt2x2: wave) produced, and *rows = their count (0: this launch could
+ * not provide them).  Room: vad_debug_stats_floats(kind, cout, n, h, w) floats, kind 0 conv3x3, 1 convt2x2, 2 first layer. */
+size_t vad_debug_stats_floats(int kind, int cout, int n, int h, int w);
+int vad_debug_conv3x3_stats(const float* in, long long in_fs, const float* w_packed, const float* bias, float* out, long long out_fs,
+                            int n, int h, int w, int cin, int cout, int precision, float* stats, int* rows, void* stream);
+int vad_debug_convt2x2_stats(const float* in, long long in_fs, const float* w_packed, const float* bias, float* out, long long out_fs,
+                             int n, int h, int w, int cin, int cout, int precision, float* stats, int* rows, void* stream);
+int vad_debug_conv3x3_c3_stats(const float* x_nchw, const float* w_packed, const float* bias, void* out, int out16, int n, int h, int w,
+                               float* stats, int* rows, void* stream);
 
 /* Row f-3 — raw-frame ingest.  The *_x forms take the original frames in either format:
  *   VAD_X_F32_NCHW (0): float32 [N,3,H,W] already normalised to [-1,1] (same as the plain entry points);

@@ -100,7 +100,15 @@ def _batchnorm_passes_on_bf16_tensors(vad, n, h, w, c, act, pool):
                                             (2, 3, 3, 64, 128), (4, 7, 7, 128, 64), (2, 20, 36, 64, 128), (5, 9, 70, 128, 64), (7, 5, 16, 32, 128)])
 def test_conv3x3_on_bf16_tensors_equals_the_bf16_operand_kernels(vad, n, h, w, cin, cout):
     """forward + BatchNorm partial sums, data gradient and weight gradient of a 3x3 convolution"""
+    check_conv3x3_on_bf16_tensors(vad, n, h, w, cin, cout)
+
+
+def check_conv3x3_on_bf16_tensors(vad, n, h, w, cin, cout, launched=None, ws=None):
+    """The body of the test above; `launched(what)` is called behind every forward-kernel launch (tests/test_hip_persistent.py
+    reads the launch plan back there); `ws(n)` hands out scratch of n floats (default: this module's guarded arenas)."""
     import hip_helpers as H
+    launched = launched or (lambda what: None)
+    _ws = ws or globals()["_ws"]
     l, rng = vad.hip.lib(), _rng(cin + cout + h)
     a16, a32 = _rep(rng.standard_normal((n, h, w, cin)))
     g16, g32 = _rep(rng.standard_normal((n, h, w, cout)))
@@ -113,12 +121,16 @@ def test_conv3x3_on_bf16_tensors_equals_the_bf16_operand_kernels(vad, n, h, w, c
     assert torch.equal(fwd, fwd3) and torch.equal(dgr, dgr3)                 # one operand layout for both bf16 modes
     o32, o16 = _nan32(n, h, w, cout), _nan16(n, h, w, cout)
     vad.hip.check(l.vad_conv3x3(a32.data_ptr(), 0, fwd.data_ptr(), bias.data_ptr(), o32.data_ptr(), 0, n, h, w, cin, cout, 0, 0, BF16, H.stream()))
+    launched("conv3x3 forward, bf16 operands")
     vad.hip.check(l.vad_conv3x3(a16.data_ptr(), 0, fwd.data_ptr(), bias.data_ptr(), o16.data_ptr(), 0, n, h, w, cin, cout, 0, 0, BF16S, H.stream()))
+    launched("conv3x3 forward, bf16 tensors")
     assert torch.equal(o16, o32.to(torch.bfloat16))
     zero = torch.zeros(max(cin, cout), device="cuda")
     d32, d16 = _nan32(n, h, w, cin), _nan16(n, h, w, cin)
     vad.hip.check(l.vad_conv3x3(g32.data_ptr(), 0, dgr.data_ptr(), zero.data_ptr(), d32.data_ptr(), 0, n, h, w, cout, cin, 0, 0, BF16, H.stream()))
+    launched("conv3x3 data gradient, bf16 operands")
     vad.hip.check(l.vad_conv3x3(g16.data_ptr(), 0, dgr.data_ptr(), zero.data_ptr(), d16.data_ptr(), 0, n, h, w, cout, cin, 0, 0, BF16S, H.stream()))
+    launched("conv3x3 data gradient, bf16 tensors")
     assert torch.equal(d16, d32.to(torch.bfloat16))
     ws = _ws(l.vad_conv_wgrad_ws_floats(n, h, 9, cin, cout))
     w32, w16 = _nan32(cout, cin, 3, 3), _nan32(cout, cin, 3, 3)
@@ -145,7 +157,14 @@ def test_conv3x3_on_bf16_tensors_equals_the_bf16_operand_kernels(vad, n, h, w, c
 @pytest.mark.parametrize("n,h,w,cin,cout", [(2, 4, 4, 128, 128), (3, 8, 6, 128, 64), (2, 16, 16, 64, 32), (4, 7, 7, 32, 128), (2, 5, 3, 128, 64)])
 def test_convt2x2_on_bf16_tensors(vad, n, h, w, cin, cout):
     """forward (+ statistics path), weight gradient from the space-to-depth gradient, 1x1 data gradient on bf16 operands"""
+    check_convt2x2_on_bf16_tensors(vad, n, h, w, cin, cout)
+
+
+def check_convt2x2_on_bf16_tensors(vad, n, h, w, cin, cout, launched=None, ws=None):
+    """The body of the test above; `launched(what)` as in check_conv3x3_on_bf16_tensors."""
     import hip_helpers as H
+    launched = launched or (lambda what: None)
+    _ws = ws or globals()["_ws"]
     l, rng = vad.hip.lib(), _rng(cin * 3 + cout + h)
     a16, a32 = _rep(rng.standard_normal((n, h, w, cin)))
     g16, g32 = _rep(rng.standard_normal((n, h, w, 4 * cout)))               # space-to-depth gradient
@@ -155,7 +174,9 @@ def test_convt2x2_on_bf16_tensors(vad, n, h, w, cin, cout):
     vad.hip.check(l.vad_train_pack_convt2x2(wt.data_ptr(), cin, cout, fwd.data_ptr(), dgr3.data_ptr(), BF16S, H.stream()))
     o32, o16 = _nan32(n, 2 * h, 2 * w, cout), _nan16(n, 2 * h, 2 * w, cout)
     vad.hip.check(l.vad_convt2x2(a32.data_ptr(), 0, fwd.data_ptr(), bias.data_ptr(), o32.data_ptr(), 0, n, h, w, cin, cout, 0, BF16, H.stream()))
+    launched("convt2x2 forward, bf16 operands")
     vad.hip.check(l.vad_convt2x2(a16.data_ptr(), 0, fwd.data_ptr(), bias.data_ptr(), o16.data_ptr(), 0, n, h, w, cin, cout, 0, BF16S, H.stream()))
+    launched("convt2x2 forward, bf16 tensors")
     assert torch.equal(o16, o32.to(torch.bfloat16))
     ws = _ws(l.vad_conv_wgrad_ws_floats(n, h, 1, cin, 4 * cout))
     w32, w16 = _nan32(cin, cout, 2, 2), _nan32(cin, cout, 2, 2)
@@ -178,6 +199,7 @@ def test_convt2x2_on_bf16_tensors(vad, n, h, w, cin, cout):
     guard = torch.full((n * h * w + 32, cin), 7.0, dtype=torch.bfloat16, device="cuda")       # room behind the tensor: must stay untouched
     da = guard[:n * h * w]
     vad.hip.check(l.vad_conv1x1_p(g16.data_ptr(), dgr3.data_ptr(), zero.data_ptr(), da.data_ptr(), n * h * w, 4 * cout, cin, BF16S, H.stream()))
+    launched("conv1x1 data gradient, bf16 tensors")
     wq = wt.to(torch.bfloat16).double().permute(2, 3, 1, 0).reshape(4 * cout, cin)          # [q*cout + co][ci]
     ref = g32.double().reshape(-1, 4 * cout) @ wq
     err = (da.double().reshape(-1, cin) - ref).abs()
@@ -188,7 +210,14 @@ def test_convt2x2_on_bf16_tensors(vad, n, h, w, cin, cout):
 @pytest.mark.parametrize("npix,cin,cout", [(512, 64, 128), (256, 128, 32), (1024, 32, 96), (24, 64, 64), (1000, 32, 64)])
 def test_conv1x1_on_bf16_tensors(vad, npix, cin, cout):
     """VideoAutoencoder.proj (models/video_autoencoder.py:311) forward and data gradient in the bf16-tensor mode"""
+    check_conv1x1_on_bf16_tensors(vad, npix, cin, cout)
+
+
+def check_conv1x1_on_bf16_tensors(vad, npix, cin, cout, launched=None, ws=None):
+    """The body of the test above; `launched(what)` as in check_conv3x3_on_bf16_tensors."""
     import hip_helpers as H
+    launched = launched or (lambda what: None)
+    _ws = ws or globals()["_ws"]
     l, rng = vad.hip.lib(), _rng(npix + cin)
     a16, a32 = _rep(rng.standard_normal((npix, cin)))
     wt = H.dev(rng.standard_normal((cout, cin)) / np.sqrt(cin))
@@ -197,6 +226,7 @@ def test_conv1x1_on_bf16_tensors(vad, npix, cin, cout):
     vad.hip.check(l.vad_train_pack_conv1x1_p(wt.data_ptr(), cout, cin, fwd.data_ptr(), dgr.data_ptr(), BF16S, H.stream()))
     out = _nan16(npix, cout)
     vad.hip.check(l.vad_conv1x1_p(a16.data_ptr(), fwd.data_ptr(), bias.data_ptr(), out.data_ptr(), npix, cin, cout, BF16S, H.stream()))
+    launched("conv1x1 forward, bf16 tensors")
     ref = a32.double() @ wt.to(torch.bfloat16).double().t() + bias.double()
     err = (out.double() - ref).abs()
     assert bool((err <= 2.0 ** -8 * ref.abs() + 1e-5).all()), float(err.max())
@@ -204,6 +234,7 @@ def test_conv1x1_on_bf16_tensors(vad, npix, cin, cout):
     zero = torch.zeros(cin, device="cuda")
     da = _nan16(npix, cin)
     vad.hip.check(l.vad_conv1x1_p(g16.data_ptr(), dgr.data_ptr(), zero.data_ptr(), da.data_ptr(), npix, cout, cin, BF16S, H.stream()))
+    launched("conv1x1 data gradient, bf16 tensors")
     ref = g32.double() @ wt.to(torch.bfloat16).double()
     err = (da.double() - ref).abs()
     assert bool((err <= 2.0 ** -8 * ref.abs() + 1e-5).all()), float(err.max())

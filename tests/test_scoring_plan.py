@@ -6,6 +6,7 @@ own argument checks.  No GPU needed: the library loads without one, and tests/sc
 `VAD_LIB=<libvad_hip.so of the commit to record from> python tests/test_scoring_plan.py <that commit>` rewrites the fixtures."""
 import itertools
 import json
+import re
 import shutil
 import subprocess
 import sys
@@ -94,12 +95,19 @@ def launch_script():
     return "\n".join(out) + "\n"
 
 
-def launch_digests(lib_path, workdir):
-    exe, syms, script = (Path(workdir) / n for n in ("score_launch_trace", "kernels.txt", "script.txt"))
+def build_tracer(lib_path, workdir):
+    """tests/score_launch_trace.cpp compiled, and the library's kernel symbols in the file it reads -> (program, symbol file)"""
+    exe, syms = (Path(workdir) / n for n in ("score_launch_trace", "kernels.txt"))
     src = Path(__file__).with_name("score_launch_trace.cpp")
     subprocess.run([shutil.which("g++") or shutil.which("c++"), "-O1", "-std=c++17", "-rdynamic", "-o", str(exe), str(src), "-ldl"], check=True)
     table = [line.split() for line in subprocess.run(["nm", str(lib_path)], check=True, capture_output=True, text=True).stdout.splitlines()]
     syms.write_text("".join(f"{t[0]} {t[2]}\n" for t in table if len(t) == 3 and "kernel" in t[2]))
+    return exe, syms
+
+
+def launch_digests(lib_path, workdir):
+    exe, syms = build_tracer(lib_path, workdir)
+    script = Path(workdir) / "script.txt"
     script.write_text(launch_script())
     out = subprocess.run([str(exe), str(lib_path), str(syms), str(script)], check=True, capture_output=True, text=True).stdout.split()
     return dict(zip(out[0::3], out[2::3])), sum(map(int, out[1::3]))
@@ -112,6 +120,77 @@ def test_launches_are_the_recorded_ones(vad, tmp_path):
     got, calls = launch_digests(vad.hip.LIB_PATH, tmp_path)
     assert calls == want["calls"] > 3000
     assert len(got) == 9 * 5 + 12 and got == want["fnv1a64"]
+
+
+# ------------------------------------------------------------------------------ B2. the planning override
+PLAN_CALLS = ("img 0 0 3 1 64 64 256 1 15", "vid 0 0 3 1 4 64 64 128 128 2 1 15")      # one 64 x 64 frame; one clip of four
+
+
+def traced_launches(exe, lib_path, syms, workdir, plan_cus):
+    """The tracer's `dump` text of PLAN_CALLS under vad_debug_set_plan_cus(plan_cus) -> per call a list of (kernel name, its
+    integer template arguments, grid.x), and the group's digest."""
+    script = Path(workdir) / f"plan{plan_cus}.txt"
+    script.write_text(f"set vad_debug_set_plan_cus {plan_cus}\ngroup plan\n" + "\n".join(PLAN_CALLS) + "\n")
+    run = subprocess.run([str(exe), str(lib_path), str(syms), str(script), "dump"], check=True, capture_output=True, text=True)
+    calls = []
+    for line in run.stderr.splitlines():
+        if line in PLAN_CALLS:
+            calls.append([])
+        elif line.startswith(" L "):
+            _, sym, grid = line.split()[:3]
+            name = re.match(r"_Z(?:N\d+_GLOBAL__N_1)?(\d+)", sym)         # (the fused tail's kernel lives in an unnamed namespace)
+            start = name.end()
+            calls[-1].append((sym[start:start + int(name.group(1))], tuple(int(v) for v in re.findall(r"Li(\d+)E", sym)), int(grid.split(",")[0])))
+        elif line.startswith(" ws "):
+            assert " rc 0" in line, line
+    assert len(calls) == len(PLAN_CALLS)
+    return calls, run.stdout.split()[2]
+
+
+def is_persistent(name):
+    return "pkernel" in name or name == "dec4_score_kernel"
+
+
+def test_plan_cus_override_reaches_every_planner(vad, tmp_path):
+    """vad_debug_set_plan_cus(1) under the tracer (256 CUs assumed, occupancy 2): a one-frame image call and a one-clip video call
+    take the throughput tilings of every convolution - conv3x3 (2,2,2,2), (1,2,2,2), (2,2,4,1), convt2x2 (2,4) - instead of the
+    latency tilings and the gate-split kernel, and every persistent grid shrinks; with the switch at 0 the launches are the ones
+    recorded without it."""
+    exe, syms = build_tracer(vad.hip.LIB_PATH, tmp_path)
+    (img0, vid0), digest0 = traced_launches(exe, vad.hip.LIB_PATH, syms, tmp_path, 0)
+    (img1, vid1), digest1 = traced_launches(exe, vad.hip.LIB_PATH, syms, tmp_path, 1)
+    assert digest0 != digest1
+    tiling = lambda launch: launch[1][1:5]                                   # conv3x3_mfma_pkernel<CK, MT, NT, WM, WN, ...>
+    conv = lambda call: {tiling(k) for k in call if k[0] == "conv3x3_mfma_pkernel"}
+    convt = lambda call: {k[1][:2] for k in call if k[0] == "convt2x2_pkernel"}
+    latency = {(1, 1, 2, 2)}
+    for dflt, one in ((img0, img1), (vid0, vid1)):
+        assert conv(dflt) & latency and not conv(one) & latency
+        assert any(k[0] == "convlstm_gate_kernel" for k in dflt) and not any(k[0] == "convlstm_gate_kernel" for k in one)
+        assert {(2, 2, 2, 2), (1, 2, 2, 2), (2, 2, 4, 1)} <= conv(one)
+        assert convt(dflt) == {(1, 1)} and convt(one) == {(2, 4)}
+    # the image call launches one kernel per layer either way: launch by launch, a persistent grid under the one-CU plan is
+    # smaller - or, where both plans launch the same frame-walking instantiation on the call's one frame, the same: that grid is
+    # the work-group positions of one frame whatever the cap (the fused first layer and the cout-32 convolution of dec4)
+    assert len(img0) == len(img1) and sum(is_persistent(k[0]) for k in img1) >= 14
+    same = 0
+    for k0, k1 in zip(img0, img1):
+        if not is_persistent(k1[0]):
+            assert k0 == k1
+        elif k0[:2] == k1[:2] and k1[0] == "conv3x3_mfma_pkernel":
+            assert k1[2] == k0[2]
+            same += 1
+        else:
+            assert k1[2] < k0[2], (k0, k1)
+    assert same == 2
+    # the video call launches another sequence (x halves per step); per kernel family every grid is smaller than any of the default's
+    for family in ("conv3x3_c3_pkernel", "conv3x3_mfma_pkernel", "convt2x2_pkernel"):
+        g0, g1 = [k[2] for k in vid0 if k[0] == family], [k[2] for k in vid1 if k[0] == family]
+        assert g0 and g1 and max(g1) < min(g0), family
+    # occupancy 2 x one CU: item walkers launch two work-groups, frame walkers the positions of one frame
+    assert all(k[2] <= 2 for call in (img1, vid1) for k in call if k[0] in ("conv3x3_c3_pkernel", "convt2x2_pkernel", "dec4_score_kernel"))
+    # and back at 0 the recorded digests hold (test_launches_are_the_recorded_ones runs the whole script; here: the same two calls)
+    assert traced_launches(exe, vad.hip.LIB_PATH, syms, tmp_path, 0)[1] == digest0
 
 
 # ------------------------------------------------------------------------------ C. refusals

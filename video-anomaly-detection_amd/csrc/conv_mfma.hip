@@ -295,7 +295,7 @@ struct ConvKnobs {
 };
 #define VAD_REQUIRE_PREC(who) VAD_REQUIRE(precision >= VAD_PREC_FP32 && precision <= VAD_PREC_BF16S, who ": precision=%d must be VAD_PREC_FP32 (0), VAD_PREC_SPLIT (1), VAD_PREC_BF16 (2) or VAD_PREC_BF16S (3)", precision)
 
-static int vad_num_cus() {
+static int vad_device_cus() {     // the device's own count: what every size bound (statistics rows, workspaces) is computed from
     static std::atomic<int> ncu_cached{0};
     int ncu = ncu_cached.load(std::memory_order_relaxed);
     if (!ncu) {
@@ -306,6 +306,34 @@ static int vad_num_cus() {
         ncu_cached = ncu;
     }
     return ncu;
+}
+// debug: the CU count every launch-planning decision sees (tilings, small-grid forms, persistent grids); 0 = the device's.  A
+// test sets 1 to run the throughput tilings and multi-iteration walks of the persistent kernels on a handful of small frames.
+static std::atomic<int> g_vad_plan_cus{0};
+extern "C" int vad_debug_set_plan_cus(int cus) {
+    // (never above the device's own count: the statistics rows and workspaces are sized from it)
+    VAD_REQUIRE(cus >= 0 && cus <= vad_device_cus(), "debug_set_plan_cus: %d CUs asked for, the device has %d (0 = the device's count)", cus, vad_device_cus());
+    g_vad_plan_cus = cus;
+    return VAD_OK;
+}
+int vad_plan_cus_override(void) { return g_vad_plan_cus.load(std::memory_order_relaxed); }
+static int vad_num_cus() {
+    const int forced = vad_plan_cus_override(), ncu = vad_device_cus();
+    return forced > 0 && forced < ncu ? forced : ncu;       // (never above the device's: the size bounds are computed from it)
+}
+
+// this thread's latest persistent launch, for vad_debug_last_plan (grid 0: the latest launch was not persistent)
+thread_local VadLastPlan t_vad_last_plan = {};
+thread_local VadLastPlan t_vad_last_walk = {};
+extern "C" int vad_debug_last_plan(int out[], int cap) {
+    VAD_REQUIRE(out && cap >= 0, "debug_last_plan: bad arguments");
+    const VadLastPlan* both[2] = {&t_vad_last_plan, &t_vad_last_walk};
+    for (int r = 0; r < 2; ++r) {
+        const VadLastPlan& l = *both[r];
+        const int v[VAD_PLAN_FIELDS] = {(int)l.grid, (int)l.items, (int)l.walkers, l.family, l.mt, l.nt, l.wm, l.wn, l.mode};
+        for (int i = 0; i < VAD_PLAN_FIELDS && r * VAD_PLAN_FIELDS + i < cap; ++i) out[r * VAD_PLAN_FIELDS + i] = v[i];
+    }
+    return 2 * VAD_PLAN_FIELDS;
 }
 
 // does the gate-split kernel (conv_small.h) serve n frames best?  cq = output columns / 4 (hid for a ConvLSTM step).  Measured
@@ -323,16 +351,23 @@ static int vad_gate_kernel_wins(int n, int h, int wd, int cq, const ConvKnobs& k
 }
 
 
+// The grid cap of a persistent kernel: CUs x resident work-groups per CU.  Use EVERY resident slot the hardware offers: with
+// fewer work-groups than slots the dispatcher packs some CUs to their limit and leaves others with one group, and a
+// persistent grid then runs at the pace of the fullest CU.  `occ` caches the instantiation's occupancy (written once with the
+// same value by whichever thread gets there first); the CU count is read per launch, so vad_debug_set_plan_cus reaches
+// instantiations that have launched before.
 template <typename K>
-static unsigned persistent_grid(K kernel, unsigned nblocks, int max_per_cu = 2) {
-    int per_cu = 0;
-    const int ncu = vad_num_cus();
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-    // Use EVERY resident slot the hardware offers: with fewer work-groups than slots the dispatcher packs some CUs
-    // to their limit and leaves others with one group, and a persistent grid then runs at the pace of the fullest CU.
-    (void)max_per_cu;
-    const unsigned g = (unsigned)ncu * (unsigned)per_cu;
-    return nblocks < g ? nblocks : g;
+static unsigned persistent_cap(K kernel, std::atomic<unsigned>& occ) {
+    unsigned per_cu = occ.load(std::memory_order_relaxed);
+    if (!per_cu) {
+        int q = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, kernel, 256, 0) != hipSuccess || q < 1) q = 1;
+        occ = per_cu = (unsigned)q;
+    }
+    return (unsigned)vad_num_cus() * per_cu;
+}
+static void vad_note_plan(unsigned grid, unsigned items, unsigned walkers, int family, int mt, int nt, int wm, int wn, int mode) {
+    vad_note_launch_plan(VadLastPlan{grid, items, walkers, family, mt, nt, wm, wn, mode});
 }
 
 // Persistent grid: (tiles per frame x cout blocks) work-group positions, replicated over `fgroups` frame groups
@@ -346,15 +381,15 @@ static unsigned persistent_grid_for(const Conv3P& p, unsigned cap) {
     return t_vad_last_pgrid = per_frame * fgroups;
 }
 
-// `variant`: 1 = persistent kernel, 0 = one tile per work-group (exact fp32 only); grid caps are per instantiation and
-// written once with the same value by whichever thread gets there first.
+// `variant`: 1 = persistent kernel, 0 = one tile per work-group (exact fp32 only); occupancies are cached per instantiation
+// (persistent_cap).
 // one persistent launch; ST = 1: the instantiation that also writes the BatchNorm partial sums (p.stats)
 template <int CK, int MT, int NT, int WM, int WN, int MODE, int ACT, int PREC, int ST, int IO16 = 0>
 static void launch_conv3_persistent(const Conv3P& p, const Conv3P& q, hipStream_t s) {
-    static std::atomic<unsigned> grid_cap{0};
-    unsigned cap = grid_cap.load(std::memory_order_relaxed);
-    if (!cap) grid_cap = cap = persistent_grid(conv3x3_mfma_pkernel<CK, MT, NT, WM, WN, MODE, ACT, 0, PREC, ST, IO16>, ~0u);
-    hipLaunchKernelGGL((conv3x3_mfma_pkernel<CK, MT, NT, WM, WN, MODE, ACT, 0, PREC, ST, IO16>), dim3(persistent_grid_for(p, cap)), dim3(256), 0, s, q);
+    static std::atomic<unsigned> occ{0};
+    const unsigned grid = persistent_grid_for(p, persistent_cap(conv3x3_mfma_pkernel<CK, MT, NT, WM, WN, MODE, ACT, 0, PREC, ST, IO16>, occ));
+    vad_note_plan(grid, p.nblocks, grid, VAD_PLAN_CONV3, MT, NT, WM, WN, MODE);
+    hipLaunchKernelGGL((conv3x3_mfma_pkernel<CK, MT, NT, WM, WN, MODE, ACT, 0, PREC, ST, IO16>), dim3(grid), dim3(256), 0, s, q);
 }
 template <int CK, int MT, int NT, int WM, int WN, int MODE, int ACT, int PREC, int IO16 = 0>
 static void launch_conv3_p(const Conv3P& p, const Conv3P& q, hipStream_t s) {
@@ -422,7 +457,7 @@ static int launch_conv3(Conv3P& p, int n, int act, hipStream_t s, int precision,
 }
 
 // upper bound of the partial-sum rows x 2 x cout floats a stats launch writes (persistent grid <= 4 work-groups per CU)
-size_t vad_conv3x3_stats_floats(int cout) { return (size_t)vad_num_cus() * 4 * 2 * (size_t)cout; }
+size_t vad_conv3x3_stats_floats(int cout) { return (size_t)vad_device_cus() * 4 * 2 * (size_t)cout; }
 
 static int conv3_stats_rows(int rc, const Conv3P& p, bool with_stats, int* stats_rows) {
     if (rc == VAD_OK && with_stats && t_vad_last_pgrid) *stats_rows = (int)(t_vad_last_pgrid / (unsigned)p.cblocks);
@@ -473,6 +508,7 @@ int vad_conv3x3_kpart(const float* in, long long in_fs, const float* w, const fl
     const bool with_stats = stats && !pool && act == VAD_ACT_NONE && kn.variant != 0;
     p.stats = with_stats ? stats : nullptr;
     t_vad_last_pgrid = 0;
+    t_vad_last_plan = {};
     // (every return below goes through L3; the row count is read back from the launch's grid)
 #define L3(CK, MT, NT, WM, WN, MODE) conv3_stats_rows(launch_conv3<CK, MT, NT, WM, WN, MODE>(p, n, act, s, precision, kn.variant, kn), p, with_stats, stats_rows)
     if (precision != VAD_PREC_FP32) {
@@ -567,22 +603,23 @@ int vad_conv3x3_c3_fused_fmt(const void* x, int fmt, const float* w0, const floa
     VAD_REQUIRE(nb < (1ll << 31), "conv3x3_c3_fused: grid too large");
     p.nblocks = (unsigned)nb;
     p.n = n;
+    t_vad_last_plan = {};
     if (precision == VAD_PREC_SPLIT) {
-        static std::atomic<unsigned> grid_cap1{0};
-        unsigned cap = grid_cap1.load(std::memory_order_relaxed);
-        if (!cap) grid_cap1 = cap = persistent_grid(conv3x3_mfma_pkernel<32, 2, 1, 4, 1, MODE_POOL, VAD_ACT_LEAKY, 1, 1>, ~0u);
+        static std::atomic<unsigned> occ1{0};
+        const unsigned grid = persistent_grid_for(p, persistent_cap(conv3x3_mfma_pkernel<32, 2, 1, 4, 1, MODE_POOL, VAD_ACT_LEAKY, 1, 1>, occ1));
+        vad_note_plan(grid, p.nblocks, grid, VAD_PLAN_C3FUSED, 2, 1, 4, 1, MODE_POOL);
         p.dbg = g_vad_dbg;
-        hipLaunchKernelGGL((conv3x3_mfma_pkernel<32, 2, 1, 4, 1, MODE_POOL, VAD_ACT_LEAKY, 1, 1>), dim3(persistent_grid_for(p, cap)), dim3(256), 0,
+        hipLaunchKernelGGL((conv3x3_mfma_pkernel<32, 2, 1, 4, 1, MODE_POOL, VAD_ACT_LEAKY, 1, 1>), dim3(grid), dim3(256), 0,
                            (hipStream_t)stream, p);
     } else if (kn.variant == 0) {
         hipLaunchKernelGGL((conv3x3_mfma_kernel<32, 2, 1, 4, 1, MODE_POOL, VAD_ACT_LEAKY, 1>), dim3((unsigned)nb), dim3(256), 0,
                            (hipStream_t)stream, p);
     } else {
-        static std::atomic<unsigned> grid_cap{0};
-        unsigned cap = grid_cap.load(std::memory_order_relaxed);
-        if (!cap) grid_cap = cap = persistent_grid(conv3x3_mfma_pkernel<32, 2, 1, 4, 1, MODE_POOL, VAD_ACT_LEAKY, 1>, ~0u);
+        static std::atomic<unsigned> occ{0};
+        const unsigned grid = persistent_grid_for(p, persistent_cap(conv3x3_mfma_pkernel<32, 2, 1, 4, 1, MODE_POOL, VAD_ACT_LEAKY, 1>, occ));
+        vad_note_plan(grid, p.nblocks, grid, VAD_PLAN_C3FUSED, 2, 1, 4, 1, MODE_POOL);
         p.dbg = g_vad_dbg;
-        hipLaunchKernelGGL((conv3x3_mfma_pkernel<32, 2, 1, 4, 1, MODE_POOL, VAD_ACT_LEAKY, 1>), dim3(persistent_grid_for(p, cap)), dim3(256), 0,
+        hipLaunchKernelGGL((conv3x3_mfma_pkernel<32, 2, 1, 4, 1, MODE_POOL, VAD_ACT_LEAKY, 1>), dim3(grid), dim3(256), 0,
                            (hipStream_t)stream, p);
     }
     VAD_LAUNCH_CHECK();
@@ -631,6 +668,7 @@ int vad_convlstm_step_zx(const float* x, long long x_fs, const float* zx, long l
     // the persistent kernel shares one set of staging offsets between x and h: needs cin_x == hid
     VAD_REQUIRE(!(precision == VAD_PREC_SPLIT && cin_x != hid), "convlstm_step: split precision needs cin_x == hid (got %d, %d)", cin_x, hid);
     const ConvKnobs kn;
+    t_vad_last_plan = {};
     // Small grids (the reference's own batch sizes: 4 clips, or 1 window): the 32x32x2 tiling yields 8 work-groups per clip of
     // a 16x16 map, each a 123 us serial K loop; below one work-group per CU the 16x16x4 form (4x the waves, a quarter of the
     // latency, bit-identical results: conv_small.h) wins - 133 -> ~35 us per step at B <= 8.
@@ -1071,6 +1109,7 @@ int vad_conv3x3_c3_stats_t(const void* x, int fmt, const float* w, const float* 
     VAD_REQUIRE(act == VAD_ACT_LEAKY || act == VAD_ACT_RELU || act == VAD_ACT_NONE, "conv3x3_c3: bad act");
     hipStream_t s = (hipStream_t)stream;
     const ConvKnobs kn;
+    t_vad_last_plan = {};
     VAD_REQUIRE(!out16 || (kn.variant != 0 && !pool && act == VAD_ACT_NONE), "conv3x3_c3: bf16 output is offered by the persistent un-pooled un-activated kernel only");
     // persistent kernel (tiles of 32 rows x 16 columns) for both forms.  The un-pooled one (training forward) writes 8.4 MB per
     // 256x256 frame: 2.6 us/frame = 3.5 TB/s with the scalar-offset buffer stores (the one-tile-per-work-group kernel, with a
@@ -1084,14 +1123,15 @@ int vad_conv3x3_c3_stats_t(const void* x, int fmt, const float* w, const float* 
         p.nblocks = (unsigned)nb;
         const bool with_stats = stats && !pool && act == VAD_ACT_NONE && cout == 32;
         if (with_stats) p.stats = stats;
-#define C3P_LAUNCH(POOL, ACT)                                                                              \
+#define C3P_LAUNCH_K(...)                                                                                  \
     {                                                                                                      \
-        static std::atomic<unsigned> cap_{0};                                                              \
-        unsigned cap = cap_.load(std::memory_order_relaxed);                                               \
-        if (!cap) cap_ = cap = persistent_grid(conv3x3_c3_pkernel<POOL, ACT>, ~0u);                        \
-        hipLaunchKernelGGL((conv3x3_c3_pkernel<POOL, ACT>), dim3(p.nblocks < cap ? p.nblocks : cap), dim3(256), 0, s, p); \
-        if (with_stats) *stats_blocks = (int)(p.nblocks < cap ? p.nblocks : cap);                          \
+        static std::atomic<unsigned> occ_{0};                                                              \
+        const unsigned cap = persistent_cap(__VA_ARGS__, occ_), grid = p.nblocks < cap ? p.nblocks : cap;  \
+        vad_note_plan(grid, p.nblocks, grid, VAD_PLAN_C3, 4, cout / 32, 4, 1, pool ? MODE_POOL : MODE_PLAIN); \
+        hipLaunchKernelGGL((__VA_ARGS__), dim3(grid), dim3(256), 0, s, p);                                 \
+        if (with_stats) *stats_blocks = (int)grid;                                                         \
     }
+#define C3P_LAUNCH(POOL, ACT) C3P_LAUNCH_K(conv3x3_c3_pkernel<POOL, ACT>)
         if (pool) {
             if (act == VAD_ACT_LEAKY) C3P_LAUNCH(1, VAD_ACT_LEAKY)
             else if (act == VAD_ACT_RELU) C3P_LAUNCH(1, VAD_ACT_RELU)
@@ -1101,22 +1141,13 @@ int vad_conv3x3_c3_stats_t(const void* x, int fmt, const float* w, const float* 
             else if (act == VAD_ACT_RELU) C3P_LAUNCH(0, VAD_ACT_RELU)
             else if (out16 == 2) {       // bf16 output AND bf16 MFMA operands (float input only)
                 VAD_REQUIRE(fmt == VAD_X_F32_NCHW, "conv3x3_c3: the bf16-operand form takes float frames");
-                static std::atomic<unsigned> cap_{0};
-                unsigned cap = cap_.load(std::memory_order_relaxed);
-                if (!cap) cap_ = cap = persistent_grid(conv3x3_c3_pkernel<0, VAD_ACT_NONE, 1, 1>, ~0u);
-                hipLaunchKernelGGL((conv3x3_c3_pkernel<0, VAD_ACT_NONE, 1, 1>), dim3(p.nblocks < cap ? p.nblocks : cap), dim3(256), 0, s, p);
-                if (with_stats) *stats_blocks = (int)(p.nblocks < cap ? p.nblocks : cap);
+                C3P_LAUNCH_K(conv3x3_c3_pkernel<0, VAD_ACT_NONE, 1, 1>)
             }
-            else if (out16) {
-                static std::atomic<unsigned> cap_{0};
-                unsigned cap = cap_.load(std::memory_order_relaxed);
-                if (!cap) cap_ = cap = persistent_grid(conv3x3_c3_pkernel<0, VAD_ACT_NONE, 1>, ~0u);
-                hipLaunchKernelGGL((conv3x3_c3_pkernel<0, VAD_ACT_NONE, 1>), dim3(p.nblocks < cap ? p.nblocks : cap), dim3(256), 0, s, p);
-                if (with_stats) *stats_blocks = (int)(p.nblocks < cap ? p.nblocks : cap);
-            }
+            else if (out16) C3P_LAUNCH_K(conv3x3_c3_pkernel<0, VAD_ACT_NONE, 1>)
             else C3P_LAUNCH(0, VAD_ACT_NONE)
         }
 #undef C3P_LAUNCH
+#undef C3P_LAUNCH_K
         VAD_LAUNCH_CHECK();
         return VAD_OK;
     }
@@ -1285,7 +1316,7 @@ extern "C" int vad_convt2x2(const float* in, long long in_fs, const float* w, co
 }
 
 // upper bound of the rows x 2 x cout floats a stats launch writes (one row per wave of a persistent grid, <= 4 work-groups per CU)
-size_t vad_convt2x2_stats_floats(int cout) { return (size_t)vad_num_cus() * 4 * 4 * 2 * (size_t)cout; }
+size_t vad_convt2x2_stats_floats(int cout) { return (size_t)vad_device_cus() * 4 * 4 * 2 * (size_t)cout; }
 
 // stats / stats_rows as in vad_conv3x3_stats (un-activated launches, cout <= 128): [rows][2][cout], shifted by the bias
 int vad_convt2x2_stats(const float* in, long long in_fs, const float* w, const float* bias,
@@ -1306,6 +1337,7 @@ int vad_convt2x2_stats(const float* in, long long in_fs, const float* w, const f
     p.w = w; p.bias = bias; p.out = out;
     p.out_fs = out_fs ? out_fs : (long long)4 * h * wd * cout;
     p.h = h; p.w_ = wd; p.cin = cin; p.cout = cout; p.npix = (long long)n * h * wd;
+    t_vad_last_plan = {};
     if (kn.variant == 0 && precision == VAD_PREC_FP32) return launch_convt<1>(p, act, (hipStream_t)stream);
     // wave-persistent LDS-free kernel (convt_pkernel.h): 32-bit offsets inside one frame
     VAD_REQUIRE(4ll * h * wd * cout * 4 < (1ll << 31) && (long long)h * wd * cin * 4 < (1ll << 31) && 4ll * cin * cout * 4 < (1ll << 31),
@@ -1331,16 +1363,16 @@ int vad_convt2x2_stats(const float* in, long long in_fs, const float* w, const f
         const bool st16 = stats && cout <= 128;
         q.stats = st16 ? stats : nullptr;
         if (st16) {
-            static std::atomic<unsigned> cap_{0};
-            unsigned cap = cap_.load(std::memory_order_relaxed);
-            if (!cap) cap_ = cap = persistent_grid(convt2x2_pkernel<2, 2, VAD_ACT_NONE, 2, 1, 1, 1>, ~0u);
-            hipLaunchKernelGGL((convt2x2_pkernel<2, 2, VAD_ACT_NONE, 2, 1, 1, 1>), dim3(want16 < cap ? want16 : cap), dim3(256), 0, (hipStream_t)stream, q);
-            *stats_rows = (int)((want16 < cap ? want16 : cap) * 4);
+            static std::atomic<unsigned> occ_{0};
+            const unsigned cap = persistent_cap(convt2x2_pkernel<2, 2, VAD_ACT_NONE, 2, 1, 1, 1>, occ_), grid = want16 < cap ? want16 : cap;
+            vad_note_plan(grid, q.nitems, 4 * grid, VAD_PLAN_CONVT, mt, nt, 0, 0, prec);
+            hipLaunchKernelGGL((convt2x2_pkernel<2, 2, VAD_ACT_NONE, 2, 1, 1, 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, q);
+            *stats_rows = (int)(grid * 4);
         } else {
-            static std::atomic<unsigned> cap_{0};
-            unsigned cap = cap_.load(std::memory_order_relaxed);
-            if (!cap) cap_ = cap = persistent_grid(convt2x2_pkernel<2, 2, VAD_ACT_NONE, 2, 0, 1, 1>, ~0u);
-            hipLaunchKernelGGL((convt2x2_pkernel<2, 2, VAD_ACT_NONE, 2, 0, 1, 1>), dim3(want16 < cap ? want16 : cap), dim3(256), 0, (hipStream_t)stream, q);
+            static std::atomic<unsigned> occ_{0};
+            const unsigned cap = persistent_cap(convt2x2_pkernel<2, 2, VAD_ACT_NONE, 2, 0, 1, 1>, occ_), grid = want16 < cap ? want16 : cap;
+            vad_note_plan(grid, q.nitems, 4 * grid, VAD_PLAN_CONVT, mt, nt, 0, 0, prec);
+            hipLaunchKernelGGL((convt2x2_pkernel<2, 2, VAD_ACT_NONE, 2, 0, 1, 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, q);
         }
         VAD_LAUNCH_CHECK();
         return VAD_OK;
@@ -1353,11 +1385,11 @@ int vad_convt2x2_stats(const float* in, long long in_fs, const float* w, const f
     q.stats = with_stats ? stats : nullptr;
 #define CT_LAUNCH_ST(A, MT_, NT_, P, ST)                                                                     \
     {                                                                                                        \
-        static std::atomic<unsigned> cap_{0};                                                                \
-        unsigned cap = cap_.load(std::memory_order_relaxed);                                                 \
-        if (!cap) cap_ = cap = persistent_grid(convt2x2_pkernel<MT_, NT_, A, P, ST>, ~0u);                   \
-        hipLaunchKernelGGL((convt2x2_pkernel<MT_, NT_, A, P, ST>), dim3(want < cap ? want : cap), dim3(256), 0, (hipStream_t)stream, q); \
-        if (ST) *stats_rows = (int)((want < cap ? want : cap) * 4);                                          \
+        static std::atomic<unsigned> occ_{0};                                                                \
+        const unsigned cap = persistent_cap(convt2x2_pkernel<MT_, NT_, A, P, ST>, occ_), grid = want < cap ? want : cap; \
+        vad_note_plan(grid, q.nitems, 4 * grid, VAD_PLAN_CONVT, MT_, NT_, 0, 0, P);                          \
+        hipLaunchKernelGGL((convt2x2_pkernel<MT_, NT_, A, P, ST>), dim3(grid), dim3(256), 0, (hipStream_t)stream, q); \
+        if (ST) *stats_rows = (int)(grid * 4);                                                               \
     }
 #define CT_LAUNCH_(A, MT_, NT_, P) CT_LAUNCH_ST(A, MT_, NT_, P, 0)
 #define CT_LAUNCH(A)                                                                                         \
@@ -1385,6 +1417,7 @@ int vad_convt2x2_stats(const float* in, long long in_fs, const float* w, const f
 // of the wave-persistent transposed-convolution kernel.  The pixel list is presented as frames of h x w pixels (w a
 // multiple of 16) so that its 2-row x 16-column M-tiles are full.  Any other precision: the fp32 kernel below.
 int vad_conv1x1_p(const void* in, const float* w, const float* bias, void* out, long long npix, int cin, int cout, int precision, void* stream) {
+    t_vad_last_plan = {};
     if (precision != VAD_PREC_BF16S) return vad_conv1x1((const float*)in, w, bias, (float*)out, npix, cin, cout, stream);
     VAD_REQUIRE(in && w && bias && out, "conv1x1: null pointer");
     VAD_REQUIRE(npix > 0 && cin % 32 == 0 && cout % 32 == 0 && cin > 0 && cout > 0, "conv1x1 (bf16): channels must be multiples of 32");
@@ -1416,15 +1449,15 @@ int vad_conv1x1_p(const void* in, const float* w, const float* bias, void* out, 
     q.nitems = (unsigned)items;
     const unsigned want = (unsigned)((items + 3) / 4);
     if (narrow) {
-        static std::atomic<unsigned> cap_{0};
-        unsigned cap = cap_.load(std::memory_order_relaxed);
-        if (!cap) cap_ = cap = persistent_grid(convt2x2_pkernel<2, 1, VAD_ACT_NONE, 2, 0, 1, 0>, ~0u);
-        hipLaunchKernelGGL((convt2x2_pkernel<2, 1, VAD_ACT_NONE, 2, 0, 1, 0>), dim3(want < cap ? want : cap), dim3(256), 0, (hipStream_t)stream, q);
+        static std::atomic<unsigned> occ_{0};
+        const unsigned cap = persistent_cap(convt2x2_pkernel<2, 1, VAD_ACT_NONE, 2, 0, 1, 0>, occ_), grid = want < cap ? want : cap;
+        vad_note_plan(grid, q.nitems, 4 * grid, VAD_PLAN_CONV1X1, 2, 1, 0, 0, VAD_PREC_BF16S);
+        hipLaunchKernelGGL((convt2x2_pkernel<2, 1, VAD_ACT_NONE, 2, 0, 1, 0>), dim3(grid), dim3(256), 0, (hipStream_t)stream, q);
     } else {
-        static std::atomic<unsigned> cap_{0};
-        unsigned cap = cap_.load(std::memory_order_relaxed);
-        if (!cap) cap_ = cap = persistent_grid(convt2x2_pkernel<2, 2, VAD_ACT_NONE, 2, 0, 1, 0>, ~0u);
-        hipLaunchKernelGGL((convt2x2_pkernel<2, 2, VAD_ACT_NONE, 2, 0, 1, 0>), dim3(want < cap ? want : cap), dim3(256), 0, (hipStream_t)stream, q);
+        static std::atomic<unsigned> occ_{0};
+        const unsigned cap = persistent_cap(convt2x2_pkernel<2, 2, VAD_ACT_NONE, 2, 0, 1, 0>, occ_), grid = want < cap ? want : cap;
+        vad_note_plan(grid, q.nitems, 4 * grid, VAD_PLAN_CONV1X1, 2, 2, 0, 0, VAD_PREC_BF16S);
+        hipLaunchKernelGGL((convt2x2_pkernel<2, 2, VAD_ACT_NONE, 2, 0, 1, 0>), dim3(grid), dim3(256), 0, (hipStream_t)stream, q);
     }
     VAD_LAUNCH_CHECK();
     return VAD_OK;
@@ -1440,4 +1473,25 @@ extern "C" int vad_conv1x1(const float* in, const float* w, const float* bias, f
     p.h = 1; p.w_ = (int)((npix < (1ll << 30)) ? npix : 0); p.cin = cin; p.cout = cout; p.npix = npix;
     VAD_REQUIRE(p.w_ > 0, "conv1x1: npix too large");
     return launch_convt<0>(p, VAD_ACT_NONE, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Layer-level access to the statistics launches of the training forward (include/vad_hip.h: debug entry points for
+// tests/test_hip_persistent.py; the training steps call the internal forms directly).
+extern "C" size_t vad_debug_stats_floats(int kind, int cout, int n, int h, int w) {
+    if (kind == 0) return vad_conv3x3_stats_floats(cout);
+    if (kind == 1) return vad_convt2x2_stats_floats(cout);
+    return (size_t)n * (size_t)((w + 15) / 16) * (size_t)((h + 31) / 32) * 2 * (size_t)cout;     // first layer: one row per 32 x 16 tile at most
+}
+extern "C" int vad_debug_conv3x3_stats(const float* in, long long in_fs, const float* w, const float* bias, float* out, long long out_fs,
+                                       int n, int h, int wd, int cin, int cout, int precision, float* stats, int* stats_rows, void* stream) {
+    return vad_conv3x3_stats(in, in_fs, w, bias, out, out_fs, n, h, wd, cin, cout, VAD_ACT_NONE, 0, precision, stats, stats_rows, stream);
+}
+extern "C" int vad_debug_convt2x2_stats(const float* in, long long in_fs, const float* w, const float* bias, float* out, long long out_fs,
+                                        int n, int h, int wd, int cin, int cout, int precision, float* stats, int* stats_rows, void* stream) {
+    return vad_convt2x2_stats(in, in_fs, w, bias, out, out_fs, n, h, wd, cin, cout, VAD_ACT_NONE, precision, stats, stats_rows, stream);
+}
+extern "C" int vad_debug_conv3x3_c3_stats(const float* x, const float* w, const float* bias, void* out, int out16, int n, int h, int wd,
+                                          float* stats, int* stats_blocks, void* stream) {
+    return vad_conv3x3_c3_stats_t(x, VAD_X_F32_NCHW, w, bias, out, out16, n, h, wd, 32, VAD_ACT_NONE, 0, stats, stats_blocks, stream);
 }

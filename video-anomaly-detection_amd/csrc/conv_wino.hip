@@ -322,22 +322,25 @@ static int wino_num_cus() {
         if (ncu <= 0) ncu = 256;
         cached = ncu;
     }
-    return ncu;
+    const int forced = vad_plan_cus_override();            // debug (vad_debug_set_plan_cus): the count the planning below sees
+    return forced > 0 && forced < ncu ? forced : ncu;
 }
 
 template <int NT, int POOL, int ACT>
 static void launch_wino(const ConvWP& p, hipStream_t s) {
-    static std::atomic<unsigned> cap_{0};
-    unsigned cap = cap_.load(std::memory_order_relaxed);
-    if (!cap) {
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, conv3x3_wino_pkernel<NT, POOL, ACT>, 256, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-        cap_ = cap = (unsigned)wino_num_cus() * (unsigned)per_cu;
+    static std::atomic<unsigned> occ_{0};                  // the instantiation's occupancy; the CU count is read per launch
+    unsigned per_cu = occ_.load(std::memory_order_relaxed);
+    if (!per_cu) {
+        int q = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, conv3x3_wino_pkernel<NT, POOL, ACT>, 256, 0) != hipSuccess || q < 1) q = 1;
+        occ_ = per_cu = (unsigned)q;
     }
+    const unsigned cap = (unsigned)wino_num_cus() * per_cu;
     const unsigned per_frame = (unsigned)(p.tiles_x * p.tiles_y * p.cblocks);
     unsigned fgroups = cap / per_frame;
     if (fgroups < 1) fgroups = 1;
     if (fgroups > (unsigned)p.n) fgroups = (unsigned)p.n;
+    vad_note_launch_plan(VadLastPlan{per_frame * fgroups, per_frame * (unsigned)p.n, per_frame * fgroups, VAD_PLAN_WINO, 0, NT, 0, 0, POOL});
     hipLaunchKernelGGL((conv3x3_wino_pkernel<NT, POOL, ACT>), dim3(per_frame * fgroups), dim3(256), 0, s, p);
 }
 

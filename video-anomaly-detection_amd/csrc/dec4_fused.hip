@@ -421,7 +421,8 @@ int d4_num_cus() {
         if (ncu <= 0) ncu = 256;
         cached = ncu;
     }
-    return ncu;
+    const int forced = vad_plan_cus_override();            // debug (vad_debug_set_plan_cus): the count the planning below sees
+    return forced > 0 && forced < ncu ? forced : ncu;
 }
 }  // namespace
 
@@ -487,6 +488,7 @@ int vad_dec4_score_fmt(const float* in, const float* wt_packed, const float* bt,
     VAD_REQUIRE(items < (1ll << 31), "dec4_score: %lld work items out of range", items);
     p.nitems = (unsigned)items;
     const unsigned grid = (unsigned)(items < slots ? items : slots);
+    vad_note_launch_plan(VadLastPlan{grid, p.nitems, grid, VAD_PLAN_DEC4, R, p.nstrips, 0, 0, fmt});
     if (fmt == VAD_X_U8_NHWC) hipLaunchKernelGGL(dec4_score_kernel<true>, dim3(grid), dim3(256), D4_LDS_BYTES, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(dec4_score_kernel<false>, dim3(grid), dim3(256), D4_LDS_BYTES, (hipStream_t)stream, p);
     VAD_LAUNCH_CHECK();

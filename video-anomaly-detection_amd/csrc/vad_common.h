@@ -31,6 +31,21 @@ static inline bool vad_is_pow2f(float v) {
     return v > 0.f && (u & 0x007fffffu) == 0u && (u >> 23) != 0u && (u >> 23) != 0xffu;
 }
 
+// Launch planning under vad_debug_set_plan_cus (conv_mfma.hip): the CU count the planners use instead of the device's, 0 = none.
+int vad_plan_cus_override(void);
+// What vad_debug_last_plan reports: this thread's latest persistent launch.  grid work-groups walk `items` units of work (frame
+// walkers: frames x tiles x column blocks; item walkers: their item count) with `walkers` independent loops (one per work-group,
+// one per wave in the transposed-convolution kernel); grid 0 = the latest layer launch was not a persistent one.
+enum { VAD_PLAN_CONV3 = 1, VAD_PLAN_C3FUSED = 2, VAD_PLAN_C3 = 3, VAD_PLAN_CONVT = 4, VAD_PLAN_CONV1X1 = 5, VAD_PLAN_DEC4 = 6, VAD_PLAN_WINO = 7 };
+enum { VAD_PLAN_FIELDS = 9 };                       // per record; vad_debug_last_plan reports two records
+struct VadLastPlan { unsigned grid, items, walkers; int family, mt, nt, wm, wn, mode; };
+// cleared on entry by the layer entry points that have both persistent and other forms (vad_conv3x3*, vad_conv3x3_c3*,
+// vad_convlstm_step*, vad_convt2x2*, vad_conv1x1_p), written by every persistent launch (the Winograd entry points and the fused
+// tail always launch one); no other entry point touches it
+extern thread_local VadLastPlan t_vad_last_plan;
+extern thread_local VadLastPlan t_vad_last_walk;     // never cleared: the latest PERSISTENT launch (a sequence's last launch may be another)
+static inline void vad_note_launch_plan(const VadLastPlan& p) { t_vad_last_plan = p; t_vad_last_walk = p; }
+
 // Launch check: kernel launches report configuration errors through hipGetLastError.
 #define VAD_LAUNCH_CHECK() VAD_HIP_TRY(hipGetLastError())
 

@@ -227,6 +227,12 @@ SIGNATURES = {
     "vad_debug_set_tail_group": (_i, [_i]),
     "vad_debug_set_dec4_fused": (_i, [_i]),
     "vad_debug_set_dec4_band": (_i, [_i]),
+    "vad_debug_set_plan_cus": (_i, [_i]),
+    "vad_debug_last_plan": (_i, [C.POINTER(_i), _i]),
+    "vad_debug_stats_floats": (_sz, [_i, _i, _i, _i, _i]),
+    "vad_debug_conv3x3_stats": (_i, [_vp, _ll, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _vp, C.POINTER(_i), _vp]),
+    "vad_debug_convt2x2_stats": (_i, [_vp, _ll, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _vp, C.POINTER(_i), _vp]),
+    "vad_debug_conv3x3_c3_stats": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, C.POINTER(_i), _vp]),
     "vad_dec4_score_partials": (_i, [_i, _i]),
     "vad_dec4_score": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "vad_debug_set_lstm_wavefront": (_i, [_i]),
