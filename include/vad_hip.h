@@ -13,6 +13,7 @@
 #ifndef VAD_HIP_H
 #define VAD_HIP_H
 #include <stddef.h>
+#include <stdint.h>
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -761,6 +762,42 @@ int vad_hist_reset(void* state, int m, void* stream);
 int vad_hist_accumulate(const float* values, long long n_groups, long long group_elems, const void* labels, int label_format,
                         void* state, int m, void* stream);
 int vad_hist_merge(void* dst, const void* src, int m, void* stream);
+
+/* ------------------------------------------------------------------ Per-region overlap (csrc/region_overlap.hip)
+ * The localisation metric of MVTec-style data: PRO(t) = the mean, over all connected anomalous regions r of the ground-truth
+ * masks, of |{p in r : v_p >= t}| / |r|, against FPR(t) over all normal pixels; AUPRO integrates the curve up to a false-positive
+ * rate (0.3) on the host, from counters.  The device labels the masks and accumulates the counters; maps, masks, labels and
+ * region sizes never leave it.
+ *
+ * vad_label_regions: masks = n images of h x w (any h, w >= 1 with h * w < 2^31 - 1; n * h * w <= 2^38), a pixel anomalous under
+ * VAD_LBL_U8_ELEM (>= 128) or VAD_LBL_F32_ELEM (> 0.5); connectivity 8 (the 3 x 3 structure of the MVTec evaluation) or 4.  Every
+ * image is labelled on its own.  labels int32 [n, h, w]: 0 = normal, otherwise 1 + (the smallest y * w + x of the pixel's region) -
+ * canonical, so two labellings compare element by element.  sizes_or_null uint32 [n, h, w]: the region's pixel count at the
+ * region's root pixel (the one whose label is its own index + 1), 0 elsewhere.  ws: caller-provided, 16-byte aligned,
+ * vad_pro_workspace_bytes(n, h, w) bytes (0 for dimensions out of range); its first uint32 is a flag word the call clears and the
+ * kernels set: every walk of the union-find is bounded by a step count known at launch (2 * h * w), and a walk that exhausts it
+ * sets bit 0 and leaves - a defect gives a wrong labelling and a set flag, never a hang.  n == 0 clears the flag word only.
+ *
+ * State blob (caller-owned, 16-byte aligned, vad_pro_state_bytes(m) bytes; 0 for an m out of range; m and the quantiser as above):
+ *     uint32 header[4] = {magic "VADP", abi << 16 | m, m, 0};  uint64 wpos[nbins], pos[nbins], neg[nbins];
+ *     uint64 regions, max_region, rejected[2], flags
+ * vad_pro_accumulate labels the masks into ws and adds the batch: a normal pixel 1 to neg[key(v)]; an anomalous pixel of region r
+ * 1 to pos[key(v)] and W(r) = (2^VAD_PRO_WEIGHT_BITS + |r| / 2) / |r| (integer division) to wpos[key(v)]; a negative, NaN or
+ * infinite value 1 to rejected[class] (it still counts towards |r|); the number of regions to `regions`; the largest |r| into
+ * max_region; the workspace's flag word into flags.  One region adds at most 2^44 + |r| / 2 to a bin, so a bin cannot wrap below
+ * 2^19 regions: the reader of the counters checks `regions` (accumulating cannot).  pos / neg are what vad_hist_accumulate counts.
+ * Integer atomics only: exact, and identical for any batching, launch order or sharding.  The header is compared with m ON THE
+ * DEVICE: with a foreign blob the call changes nothing and follows no offset of it.  vad_pro_merge: dst += src; the maximum for
+ * max_region, the union for flags.  All calls are asynchronous on `stream`, allocate nothing and can be captured into a graph. */
+#define VAD_PRO_WEIGHT_BITS 44
+size_t vad_pro_state_bytes(int m);
+int vad_pro_reset(void* state, int m, void* stream);
+int vad_pro_merge(void* dst, const void* src, int m, void* stream);
+size_t vad_pro_workspace_bytes(long long n, int h, int w);
+int vad_label_regions(const void* masks, int label_format, long long n, int h, int w, int connectivity, int32_t* labels,
+                      uint32_t* sizes_or_null, void* ws, size_t ws_bytes, void* stream);
+int vad_pro_accumulate(const float* values, const void* masks, int label_format, long long n, int h, int w, int connectivity,
+                       void* state, int m, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------ hipGraph capture / replay of a scoring call
  * vad_graph_begin(stream); <one vad_img_score* / vad_vid_score* call on `stream`>; vad_graph_end(stream, &exec) captures

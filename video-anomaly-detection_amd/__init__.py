@@ -15,6 +15,6 @@ from .training import ImageTrainer, VideoTrainer                                
 from . import scoring                                                 # noqa: F401
 from .scoring import FrameResizer                                    # noqa: F401
 from . import metrics                                                 # noqa: F401
-from .metrics import ScoreHistogram                                  # noqa: F401
+from .metrics import ProHistogram, ScoreHistogram                    # noqa: F401
 from . import frame_bank                                              # noqa: F401
 from .frame_bank import FrameBank                                    # noqa: F401

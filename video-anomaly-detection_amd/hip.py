@@ -16,7 +16,7 @@ PKG_DIR = Path(__file__).resolve().parent
 REPO_DIR = PKG_DIR.parent
 CSRC = PKG_DIR / "csrc"
 LIB_PATH = Path(os.environ.get("VAD_LIB", PKG_DIR / "libvad_hip.so"))
-SOURCES = ["conv_mfma.hip", "conv_wino.hip", "dec4_fused.hip", "tail.hip", "wide_io.hip", "state_io.hip", "resize_u8.hip", "frame_gather.hip", "score_hist.hip", "ssim.hip", "train_ops.hip", "wgrad.hip", "train_step.hip", "train_step_img.hip", "vad_api.hip", "pack.cpp"]
+SOURCES = ["conv_mfma.hip", "conv_wino.hip", "dec4_fused.hip", "tail.hip", "wide_io.hip", "state_io.hip", "resize_u8.hip", "frame_gather.hip", "score_hist.hip", "region_overlap.hip", "ssim.hip", "train_ops.hip", "wgrad.hip", "train_step.hip", "train_step_img.hip", "vad_api.hip", "pack.cpp"]
 
 VAD_OK = 0
 ABI_VERSION = 3
@@ -46,6 +46,7 @@ ACT_NONE, ACT_LEAKY, ACT_RELU = 0, 1, 2
 X_F32_NCHW, X_U8_NHWC = 0, 1
 LBL_U8_ELEM, LBL_F32_ELEM, LBL_U8_GROUP = 0, 1, 2      # include/vad_hip.h VAD_LBL_*: label formats of vad_hist_accumulate
 HIST_MIN_M, HIST_MAX_M = 4, 15
+PRO_WEIGHT_BITS = 44     # VAD_PRO_WEIGHT_BITS: a region adds (2^44 + |r| / 2) // |r| per pixel to the weighted histogram
 PROF_SLOTS = 32
 MAX_WIDTH = 4096          # VAD_MAX_WIDTH: largest latent_dim / lstm_hidden_dim
 
@@ -278,6 +279,13 @@ SIGNATURES = {
     "vad_hist_reset": (_i, [_vp, _i, _vp]),
     "vad_hist_accumulate": (_i, [_vp, _ll, _ll, _vp, _i, _vp, _i, _vp]),
     "vad_hist_merge": (_i, [_vp, _vp, _i, _vp]),
+    # per-region overlap: mask labelling and the region-weighted histogram (csrc/region_overlap.hip)
+    "vad_pro_state_bytes": (_sz, [_i]),
+    "vad_pro_reset": (_i, [_vp, _i, _vp]),
+    "vad_pro_merge": (_i, [_vp, _vp, _i, _vp]),
+    "vad_pro_workspace_bytes": (_sz, [_ll, _i, _i]),
+    "vad_label_regions": (_i, [_vp, _i, _ll, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "vad_pro_accumulate": (_i, [_vp, _vp, _i, _ll, _i, _i, _i, _vp, _i, _vp, _sz, _vp]),
     "vad_graph_begin": (_i, [_vp]),
     "vad_graph_end": (_i, [_vp, C.POINTER(_vp)]),
     "vad_graph_launch": (_i, [_vp, _vp]),

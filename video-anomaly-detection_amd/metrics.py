@@ -14,6 +14,9 @@ top m mantissa bits; -0.0 counts as 0), of `255 << m` bins; the bin's lower edge
 The map is monotone, so quantising can only create ties, never swap a pair: `auroc_from_counts` returns the AUROC of the quantised
 scores together with a rigorous bound on its distance from the AUROC of the unquantised ones.  Negative values, NaNs and
 infinities are not binned; they are counted per class in `rejected`.
+
+The second half of the file is the per-region overlap (AUPRO): `label_regions`, `ProHistogram` (csrc/region_overlap.hip) and
+`aupro_from_counts` / `pro_curve_from_counts`, built on the same quantiser.
 """
 from __future__ import annotations
 
@@ -333,3 +336,372 @@ def class_stats_from_counts(counts) -> dict:
         mean = float(np.sum(w * e))
         out[name] = {"count": n, "mean": mean, "std": float(np.sqrt(np.sum(w * (e - mean) ** 2)))}
     return out
+
+
+# ====================================================================== per-region overlap (AUPRO)
+# Per-region overlap, the localisation metric of MVTec-style data.  Thresholds are the bins' lower edges;
+# FPR(t) = the share of all normal pixels with v >= t; PRO(t) = the mean over all connected anomalous regions r of the evaluation
+# of |{p in r : v_p >= t}| / |r|.  PRO(t) = sum over anomalous pixels of [v_p >= t] / (R |r(p)|) is a histogram in which a pixel
+# adds a weight; the device adds the integer W(r) = (2^44 + |r| / 2) // |r| (`vad_pro_accumulate`, csrc/region_overlap.hip), so
+# the counters stay exact integer sums.
+PRO_WEIGHT_BITS = hip.PRO_WEIGHT_BITS
+PRO_MAX_REGIONS = 1 << 19      # a region adds at most 2^44 + |r| / 2 to a bin: beyond 2^19 regions a uint64 bin could wrap
+_PRO_MAGIC = 0x50444156        # "VADP", csrc/region_overlap.hip
+_PRO_TAIL = 5                  # regions, max_region, rejected[2], flags
+
+
+def pro_state_bytes(mantissa_bits: int) -> int:
+    """Size of the device blob: 16-byte header, uint64 wpos / pos / neg [nbins], uint64 regions, max_region, rejected[2], flags."""
+    return _HEADER_BYTES + 8 * (3 * num_bins(mantissa_bits) + _PRO_TAIL)
+
+
+def region_weight(size: int) -> int:
+    """W(r) for a region of `size` pixels: 2^44 / size rounded to the nearest integer."""
+    return ((1 << PRO_WEIGHT_BITS) + size // 2) // size
+
+
+def _pro_points(wpos, neg, regions, what: str):
+    """-> (keys descending, fpr float64 [K + 1], pro float64 [K + 1], m): the curve's vertices after (0, 0), one per populated bin
+    from the highest key down."""
+    w = np.asarray(wpos.detach().cpu().numpy() if isinstance(wpos, torch.Tensor) else wpos)
+    q = np.asarray(neg.detach().cpu().numpy() if isinstance(neg, torch.Tensor) else neg)
+    if w.ndim != 1 or q.shape != w.shape or not np.issubdtype(w.dtype, np.integer) or not np.issubdtype(q.dtype, np.integer):
+        raise ValueError(f"{what}: wpos and neg must be integer arrays [nbins] of one length, got {w.dtype} {w.shape} and {q.dtype} {q.shape}")
+    m = next((k for k in range(MIN_MANTISSA_BITS, MAX_MANTISSA_BITS + 1) if 255 << k == w.shape[0]), None)
+    if m is None:
+        raise ValueError(f"{what}: {w.shape[0]} bins are not 255 << m for a mantissa_bits m in {MIN_MANTISSA_BITS}..{MAX_MANTISSA_BITS}")
+    if w.dtype == np.int64:
+        w = w.view(np.uint64)                                          # the device's uint64 sums, read through an int64 view
+    if (q < 0).any() or (w.dtype != np.uint64 and (w < 0).any()):
+        raise ValueError(f"{what}: counters must be non-negative")
+    regions = int(regions)
+    if regions <= 0:
+        raise ValueError(f"{what}: no region (the masks hold no anomalous pixel)")
+    if regions > PRO_MAX_REGIONS:
+        raise ValueError(f"{what}: {regions} regions are more than 2^19 = {PRO_MAX_REGIONS}: a weighted bin may have wrapped")
+    keys = np.flatnonzero((w != 0) | (q != 0))[::-1]
+    w, q = w[keys], q[keys].astype(np.int64)
+    n_neg = _total(q)
+    if n_neg == 0:
+        raise ValueError(f"{what}: no normal pixel")
+    if len(w) and float(w.max()) * len(w) < 2.0 ** 62:
+        cw = np.cumsum(w.astype(np.int64)).astype(np.float64)
+    else:                                                              # near 2^63: Python integers, each rounded once
+        cw, run = [], 0
+        for v in w.tolist():
+            run += v
+            cw.append(run)
+        cw = np.array([float(v) for v in cw], np.float64)
+    denom = float(regions << PRO_WEIGHT_BITS)
+    if float(q.max()) * len(q) < 2.0 ** 62:
+        cq = np.cumsum(q).astype(np.float64)
+    else:
+        cq, run = [], 0
+        for v in q.tolist():
+            run += v
+            cq.append(run)
+        cq = np.array([float(v) for v in cq], np.float64)
+    fpr = np.concatenate([[0.0], cq / float(n_neg)])
+    pro = np.concatenate([[0.0], cw / denom])
+    return keys, fpr, pro, m
+
+
+def pro_curve_from_counts(wpos, neg, regions) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(fpr, pro, thresholds) at the populated bins, as `roc_curve_from_counts`: point k >= 1 flags `score >= thresholds[k]`
+    (bin lower edges, float32, descending - they apply to unquantised scores as they stand); point 0 is (0, 0) at +inf."""
+    keys, fpr, pro, m = _pro_points(wpos, neg, regions, "pro_curve_from_counts")
+    return fpr, pro, np.concatenate([np.array([np.inf], np.float32), bin_lower_edges(keys, m)])
+
+
+def aupro_from_counts(wpos, neg, regions, max_region, fpr_limit: float = 0.3) -> Tuple[float, float, float]:
+    """(aupro, quant_bound, weight_bound) from the weighted histogram `wpos` [nbins], the normal pixels' histogram `neg` [nbins],
+    the number of regions and the largest region's size.
+
+    aupro: the curve (fpr, pro) of `pro_curve_from_counts`, joined by straight lines, integrated up to `fpr_limit` (in (0, 1]) with
+    one linear interpolation on the segment the limit cuts, divided by `fpr_limit` - the integration of the MVTec evaluation.
+    weight_bound = max_region / 2^45: a weight is 2^44 / |r| rounded to an integer, so the overlap of one region is off by at most
+    |r| / 2^45 at every threshold, and so are their mean and the normalised area: |aupro - AUPRO of the quantised scores| <= it.
+    quant_bound: a threshold at a bin edge selects the same pixels on raw and on quantised scores, so every vertex of this curve is
+    a vertex of the exact curve, which is monotone between two of them: the areas differ by at most 0.5 * dFPR * dPRO per whole
+    segment and (fpr_limit - FPR_0) * dPRO on the cut one, all divided by `fpr_limit`.
+    |aupro - AUPRO of the unquantised scores| <= quant_bound + weight_bound."""
+    if isinstance(fpr_limit, bool) or not isinstance(fpr_limit, (int, float, np.floating, np.integer)) or not 0.0 < float(fpr_limit) <= 1.0:
+        raise ValueError(f"aupro_from_counts: fpr_limit must be in (0, 1], got {fpr_limit!r}")
+    limit = float(fpr_limit)
+    _, fpr, pro, _ = _pro_points(wpos, neg, regions, "aupro_from_counts")
+    max_region = int(max_region)
+    if max_region <= 0:
+        raise ValueError(f"aupro_from_counts: max_region must be positive with {int(regions)} regions, got {max_region}")
+    whole = int(np.flatnonzero(fpr <= limit)[-1])                      # vertices 0..whole lie inside the limit
+    df, dp = np.diff(fpr[:whole + 1]), np.diff(pro[:whole + 1])
+    area = float(np.sum(df * (pro[1:whole + 1] + pro[:whole]) * 0.5))
+    bound = float(np.sum(0.5 * df * dp))
+    if fpr[whole] < limit:                                             # the limit cuts segment whole -> whole + 1 (fpr ends at 1)
+        f0, f1, p0, p1 = fpr[whole], fpr[whole + 1], pro[whole], pro[whole + 1]
+        p_cut = p0 + (p1 - p0) * (limit - f0) / (f1 - f0)
+        area += float((limit - f0) * (p0 + p_cut) * 0.5)
+        bound += float((limit - f0) * (p1 - p0))
+    return area / limit, bound / limit, max_region / float(1 << (PRO_WEIGHT_BITS + 1))
+
+
+def _check_connectivity(c, what: str) -> int:
+    if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or int(c) not in (4, 8):
+        raise hip.VadError(f"{what}: connectivity must be 4 or 8, got {c!r}")
+    return int(c)
+
+
+def _mask_planes(masks: torch.Tensor, what: str):
+    """-> (contiguous mask tensor, label format, B, H, W) for a mask batch [B,H,W] or [B,1,H,W]: float masks (anomalous iff > 0.5)
+    as float32, uint8 bytes (iff >= 128) as they are, bool / other integers (iff non-zero) as bytes 0 / 255."""
+    if masks.dim() == 4 and masks.shape[1] == 1:
+        masks = masks[:, 0]
+    if masks.dim() != 3 or masks.shape[1] < 1 or masks.shape[2] < 1:
+        raise hip.VadError(f"{what}: masks must be [B,H,W] or [B,1,H,W], got {tuple(masks.shape)}")
+    if masks.is_floating_point():
+        m, fmt = (masks if masks.dtype == torch.float32 else masks.float()).contiguous(), hip.LBL_F32_ELEM
+    else:
+        m, fmt = (masks if masks.dtype == torch.uint8 else (masks != 0).to(torch.uint8) * 255).contiguous(), hip.LBL_U8_ELEM
+    return m, fmt, m.shape[0], m.shape[1], m.shape[2]
+
+
+def _pro_workspace(n: int, h: int, w: int, device, what: str) -> torch.Tensor:
+    size = hip.lib().vad_pro_workspace_bytes(n, h, w)
+    if size == 0:
+        raise hip.VadError(f"{what}: {n} masks of {h} x {w} are out of range (h * w < 2^31 - 1, n * h * w <= 2^38)")
+    return torch.empty(size, dtype=torch.uint8, device=device)
+
+
+def _raise_on_flags(flags: int, what: str) -> None:
+    if flags:
+        raise hip.VadError(f"{what}: flags {flags:#x} are set - a walk of the labelling kernels ran out of its step bound (bit 0) or a "
+                           "region has no size (bit 1); the labels and counters of this evaluation are not to be trusted")
+
+
+def label_regions(masks: torch.Tensor, connectivity: int = 8) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Connected anomalous regions of a batch of masks on the GPU (`vad_label_regions`): -> (labels int32 [B,H,W], sizes uint32
+    [B,H,W]).  labels: 0 = normal, otherwise 1 + (the smallest y * W + x of the pixel's region); every image is labelled on its own.
+    sizes: the region's pixel count at its root pixel (label == own index + 1), 0 elsewhere.  connectivity 8 is
+    `scipy.ndimage.label(mask, structure=ones((3, 3)))`, 4 its default structure.  Reads the kernels' flag word (one 4-byte copy,
+    which waits for the labelling) and raises VadError if it is set."""
+    connectivity = _check_connectivity(connectivity, "label_regions")
+    if not isinstance(masks, torch.Tensor):
+        raise hip.VadError("label_regions: masks must be a torch tensor")
+    if not masks.is_cuda:
+        raise hip.VadError(f"label_regions: masks ({masks.device}) must be on the GPU (regions are labelled on the device; there is no CPU fallback)")
+    m, fmt, b, h, w = _mask_planes(masks, "label_regions")
+    labels = torch.empty((b, h, w), dtype=torch.int32, device=m.device)
+    sizes = torch.empty((b, h, w), dtype=torch.uint32, device=m.device)
+    with torch.cuda.device(m.device):
+        ws = _pro_workspace(b, h, w, m.device, "label_regions")
+        hip.check(hip.lib().vad_label_regions(m.data_ptr(), fmt, b, h, w, connectivity, labels.data_ptr(), sizes.data_ptr(),
+                                              ws.data_ptr(), ws.numel(), hip.current_stream()), "vad_label_regions")
+    hip.calls["label_regions"] = hip.calls.get("label_regions", 0) + 1
+    _raise_on_flags(int(ws[:4].view(torch.int32).item()), "label_regions")
+    return labels, sizes
+
+
+class ProHistogram:
+    """The counters of the per-region overlap in one device blob (include/vad_hip.h `vad_pro_*`): the weighted histogram `wpos`
+    of the anomalous pixels, their plain histogram `pos` and the normal pixels' `neg` - `counts()` is what a `ScoreHistogram` of
+    the same batches would hold, so `auroc()` comes with it -, the number of regions, the largest region, rejected values per
+    class and the labelling kernels' flag word.
+
+    `accumulate(values, masks)` labels the masks and adds the batch on the GPU, asynchronously; `aupro()` is the one host read
+    (24 * (255 << m) bytes: 12 MB at the default m = 11).  With `device="cpu"` the object is a container for counters (load,
+    merge, all-reduce, read): accumulating runs on the GPU only and there is no CPU fallback."""
+
+    def __init__(self, mantissa_bits: int = 11, device="cuda", connectivity: int = 8):
+        self.mantissa_bits = _check_m(mantissa_bits, "ProHistogram")
+        self.connectivity = _check_connectivity(connectivity, "ProHistogram")
+        self.nbins = 255 << self.mantissa_bits
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._state = torch.empty(pro_state_bytes(self.mantissa_bits), dtype=torch.uint8, device=self.device)
+        self._ws = None
+        if self.device.type == "cuda":
+            assert hip.lib().vad_pro_state_bytes(self.mantissa_bits) == self._state.numel()
+        self.reset()
+
+    # ------------------------------------------------------------------ state
+    def _words(self) -> torch.Tensor:
+        """wpos, pos, neg [nbins] each, then regions, max_region, rejected[2], flags: one int64 view of the blob."""
+        return self._state[_HEADER_BYTES:].view(torch.int64)
+
+    def _header(self) -> np.ndarray:
+        m = self.mantissa_bits
+        return np.array([_PRO_MAGIC, (hip.ABI_VERSION << 16) | m, m, 0], np.uint32)
+
+    def reset(self) -> "ProHistogram":
+        if self.device.type == "cuda":
+            with torch.cuda.device(self.device):
+                hip.check(hip.lib().vad_pro_reset(self._state.data_ptr(), self.mantissa_bits, hip.current_stream()), "vad_pro_reset")
+        else:
+            self._state.zero_()
+            self._state[:_HEADER_BYTES] = torch.from_numpy(self._header().view(np.uint8).copy())
+        return self
+
+    def weighted(self) -> torch.Tensor:
+        """int64 [nbins] on the histogram's device (a copy): the bits of the uint64 sums of W(r) per bin."""
+        return self._words()[:self.nbins].clone()
+
+    def counts(self) -> torch.Tensor:
+        """int64 [2, nbins] (a copy): row 0 = normal, row 1 = anomalous - the counts of `ScoreHistogram`."""
+        w = self._words()
+        return torch.stack([w[2 * self.nbins:3 * self.nbins], w[self.nbins:2 * self.nbins]])
+
+    def _tail(self) -> list:
+        """[regions, max_region, rejected normal, rejected anomalous, flags] on the host; raises on a set flag word."""
+        tail = self._words()[3 * self.nbins:].tolist()
+        _raise_on_flags(tail[4], "ProHistogram")
+        return tail
+
+    def regions(self) -> int:
+        return self._tail()[0]
+
+    def max_region(self) -> int:
+        return self._tail()[1]
+
+    def rejected(self) -> torch.Tensor:
+        """int64 [2]: negative, NaN and infinite values seen per class (in no bin; an anomalous one still counts towards |r|)."""
+        return self._words()[3 * self.nbins + 2:3 * self.nbins + 4].clone()
+
+    def flags(self) -> int:
+        return int(self._words()[3 * self.nbins + 4].item())
+
+    def _host(self):
+        """(wpos uint64 [nbins], pos, neg int64 [nbins], tail): the one device -> host read; header and flags are checked."""
+        blob = self._state.cpu().numpy()
+        if not np.array_equal(blob[:_HEADER_BYTES].view(np.uint32), self._header()):
+            raise hip.VadError("ProHistogram: the state's header is not that of a per-region histogram with mantissa_bits "
+                               f"{self.mantissa_bits} (the blob was overwritten)")
+        words = blob[_HEADER_BYTES:].view(np.int64)
+        tail = words[3 * self.nbins:].tolist()
+        _raise_on_flags(tail[4], "ProHistogram")
+        nb = self.nbins
+        return words[:nb].view(np.uint64).copy(), words[nb:2 * nb].copy(), words[2 * nb:3 * nb].copy(), tail
+
+    def state_dict(self) -> dict:
+        """Host copies of every counter, with mantissa_bits and connectivity: resume a long evaluation later."""
+        w = self._words().cpu()
+        nb = self.nbins
+        return {"mantissa_bits": self.mantissa_bits, "connectivity": self.connectivity, "weighted": w[:nb].clone(),
+                "counts": torch.stack([w[2 * nb:3 * nb], w[nb:2 * nb]]), "regions": int(w[3 * nb]), "max_region": int(w[3 * nb + 1]),
+                "rejected": w[3 * nb + 2:3 * nb + 4].clone(), "flags": int(w[3 * nb + 4])}
+
+    def load_state_dict(self, state: dict) -> "ProHistogram":
+        if state.get("mantissa_bits") != self.mantissa_bits:
+            raise hip.VadError(f"ProHistogram.load_state_dict: mantissa_bits {state.get('mantissa_bits')!r} of the saved state differs "
+                               f"from this histogram's {self.mantissa_bits}")
+        if state.get("connectivity") != self.connectivity:
+            raise hip.VadError(f"ProHistogram.load_state_dict: connectivity {state.get('connectivity')!r} of the saved state differs "
+                               f"from this histogram's {self.connectivity}")
+        weighted = torch.as_tensor(np.asarray(state["weighted"]))
+        counts = torch.as_tensor(np.asarray(state["counts"]))
+        rejected = torch.as_tensor(np.asarray(state["rejected"]))
+        nb = self.nbins
+        if (tuple(weighted.shape) != (nb,) or tuple(counts.shape) != (2, nb) or tuple(rejected.shape) != (2,)
+                or any(t.dtype != torch.int64 for t in (weighted, counts, rejected))):
+            raise hip.VadError(f"ProHistogram.load_state_dict: weighted must be int64 [{nb}], counts int64 [2, {nb}] and rejected int64 "
+                               f"[2], got {weighted.dtype} {tuple(weighted.shape)}, {counts.dtype} {tuple(counts.shape)} and "
+                               f"{rejected.dtype} {tuple(rejected.shape)}")
+        words = self._words()
+        words[:nb].copy_(weighted)
+        words[nb:2 * nb].copy_(counts[1])
+        words[2 * nb:3 * nb].copy_(counts[0])
+        words[3 * nb:].copy_(torch.tensor([int(state["regions"]), int(state["max_region"]), int(rejected[0]), int(rejected[1]),
+                                           int(state.get("flags", 0))], dtype=torch.int64))
+        return self
+
+    # ------------------------------------------------------------------ accumulate
+    def accumulate(self, values: torch.Tensor, masks: torch.Tensor) -> "ProHistogram":
+        """Add a batch.  `values`: float32 GPU tensor [B,1,H,W] or [B,H,W] (an error map, an SSIM map).  `masks`: the ground truth
+        at the same resolution, [B,1,H,W] or [B,H,W]: float (anomalous iff > 0.5), uint8 (iff >= 128 - the same pixels), bool /
+        other integers (iff non-zero).  Labels the masks and adds the counters in one `vad_pro_accumulate` call, asynchronous on
+        the current stream; the workspace is kept and grown as needed."""
+        what = "ProHistogram.accumulate"
+        if not isinstance(values, torch.Tensor) or not isinstance(masks, torch.Tensor):
+            raise hip.VadError(f"{what}: values and masks must be torch tensors")
+        if self.device.type != "cuda" or not values.is_cuda or not masks.is_cuda:
+            raise hip.VadError(f"{what}: values ({values.device}), masks ({masks.device}) and the histogram ({self.device}) must be "
+                               "on the GPU (regions are labelled on the device; there is no CPU fallback)")
+        if values.device != self.device or masks.device != self.device:
+            raise hip.VadError(f"{what}: values ({values.device}) and masks ({masks.device}) must be on the histogram's device {self.device}")
+        if values.dtype != torch.float32:
+            raise hip.VadError(f"{what}: values must be float32, got {values.dtype}")
+        if values.dim() == 4 and values.shape[1] == 1:
+            values = values[:, 0]
+        if values.dim() != 3:
+            raise hip.VadError(f"{what}: values must be [B,1,H,W] or [B,H,W], got {tuple(values.shape)}")
+        m, fmt, b, h, w = _mask_planes(masks, what)
+        if tuple(values.shape) != (b, h, w):
+            raise hip.VadError(f"{what}: masks {tuple(masks.shape)} must have the batch and resolution of values {tuple(values.shape)}")
+        if b == 0:
+            return self
+        values = values.contiguous()
+        with torch.cuda.device(self.device):
+            need = hip.lib().vad_pro_workspace_bytes(b, h, w)
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = _pro_workspace(b, h, w, self.device, what)
+            hip.check(hip.lib().vad_pro_accumulate(values.data_ptr(), m.data_ptr(), fmt, b, h, w, self.connectivity,
+                                                   self._state.data_ptr(), self.mantissa_bits, self._ws.data_ptr(), self._ws.numel(),
+                                                   hip.current_stream()), "vad_pro_accumulate")
+        hip.calls["pro_accumulate"] = hip.calls.get("pro_accumulate", 0) + 1
+        return self
+
+    # ------------------------------------------------------------------ combine
+    def merge(self, other: "ProHistogram") -> "ProHistogram":
+        """self += other: sums of the counters, the larger max_region, the union of the flags."""
+        if not isinstance(other, ProHistogram):
+            raise hip.VadError(f"ProHistogram.merge: other must be a ProHistogram, got {type(other).__name__}")
+        if other.mantissa_bits != self.mantissa_bits:
+            raise hip.VadError(f"ProHistogram.merge: mantissa_bits differ ({self.mantissa_bits} and {other.mantissa_bits}); bins of "
+                               "different widths cannot be added")
+        if other.connectivity != self.connectivity:
+            raise hip.VadError(f"ProHistogram.merge: connectivity differs ({self.connectivity} and {other.connectivity}); regions "
+                               "of different definitions cannot be averaged")
+        if other is self:
+            raise hip.VadError("ProHistogram.merge: other is this histogram")
+        if self.device.type == "cuda" and other.device == self.device:
+            with torch.cuda.device(self.device):
+                hip.check(hip.lib().vad_pro_merge(self._state.data_ptr(), other._state.data_ptr(), self.mantissa_bits,
+                                                  hip.current_stream()), "vad_pro_merge")
+        else:
+            mine, theirs = self._words(), other._words().to(self.device)
+            k = 3 * self.nbins
+            biggest, flags = torch.maximum(mine[k + 1], theirs[k + 1]), mine[k + 4] | theirs[k + 4]
+            mine.add_(theirs)
+            mine[k + 1], mine[k + 4] = biggest, flags
+        return self
+
+    def all_reduce(self, group=None, force_collective: bool = False) -> int:
+        """Combine the ranks of `group`: ONE all_reduce(SUM) of the counters (a summed flag word is non-zero exactly when a rank's
+        is) and ONE all_reduce(MAX) of the max_region word.  Returns the world size."""
+        import torch.distributed as dist
+        words = self._words()
+        k = 3 * self.nbins + 1
+        biggest = words[k:k + 1].clone()
+        words[k] = 0
+        world = allreduce_counters_(words, group, force_collective)
+        if world > 1 or (force_collective and dist.is_available() and dist.is_initialized()):
+            if biggest.is_cuda and dist.get_backend(group) == "gloo":
+                host = biggest.cpu()
+                dist.all_reduce(host, op=dist.ReduceOp.MAX, group=group)
+                biggest.copy_(host)
+            else:
+                dist.all_reduce(biggest, op=dist.ReduceOp.MAX, group=group)
+        words[k] = biggest[0]
+        return world
+
+    # ------------------------------------------------------------------ metrics (one host read)
+    def aupro(self, fpr_limit: float = 0.3) -> Tuple[float, float, float]:
+        wpos, _, neg, tail = self._host()
+        return aupro_from_counts(wpos, neg, tail[0], tail[1], fpr_limit)
+
+    def pro_curve(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        wpos, _, neg, tail = self._host()
+        return pro_curve_from_counts(wpos, neg, tail[0])
+
+    def auroc(self) -> Tuple[float, float]:
+        _, pos, neg, _ = self._host()
+        return auroc_from_counts(np.stack([neg, pos]))

@@ -373,6 +373,33 @@ def pixel_auroc(model, loader: Iterable[dict], device, map: str = "mse", mantiss
     return auroc, tie_bound, hist
 
 
+def pixel_aupro(model, loader: Iterable[dict], device, map: str = "mse", fpr_limit: float = 0.3, mantissa_bits: int = 11, hist=None,
+                connectivity: int = 8):
+    """Per-region overlap (AUPRO) of an image model's anomaly map against the ground-truth masks: every connected anomalous region
+    of the masks weighs the same, and the curve is integrated up to a false-positive rate of `fpr_limit` - the localisation metric
+    of the MVTec evaluation, where pixel AUROC is dominated by the large defects.  The loop of `pixel_auroc` (same batches, same
+    `map`): each batch is ONE scoring call and ONE `ProHistogram.accumulate`, which labels the masks' regions and adds the counters
+    on the device; the only host read is the counters, once, at the end.  Returns (aupro, quant_bound, weight_bound, hist)
+    (`metrics.aupro_from_counts`); pass `hist` to continue an earlier evaluation or to all-reduce before reading, in which case
+    its own mantissa_bits and connectivity apply.  `hist.auroc()` is the pixel AUROC of the same evaluation."""
+    from . import metrics
+    if map not in ("mse", "ssim"):
+        raise hip.VadError(f"pixel_aupro: map must be 'mse' or 'ssim', got {map!r}")
+    if hist is None:
+        hist = metrics.ProHistogram(mantissa_bits, device, connectivity)
+    with torch.no_grad():
+        for batch in loader:
+            images = batch["image"].to(device)
+            masks = torch.as_tensor(batch["mask"]).to(device)
+            if map == "mse":
+                values = model.score_all(images)["errmap"]
+            else:
+                values = model.score_criteria(images, ssim_map=True)["ssim_map"]
+            hist.accumulate(values, masks)
+    aupro, quant_bound, weight_bound = hist.aupro(fpr_limit)
+    return aupro, quant_bound, weight_bound, hist
+
+
 def frame_auroc(model, loader: Iterable[dict], device, hist=None, mantissa_bits: int = 11):
     """Frame-level AUROC of a video model (evaluate_video.py:171-176) without gathering the scores: the clip loop of
     `score_clips(per_frame=True)` - batches {'frames' [B,T,C,H,W], 'frame_labels' [B,T], ...} -, each batch's frame scores and
