@@ -470,6 +470,12 @@ int vad_synth_frames(float* out_nchw, unsigned long long seed, long long first_f
  * bias in, zero weights out: a padded channel stays exactly 0 through every layer, results are those of the unpadded
  * network).  Every entry point takes the REAL dimensions. */
 #define VAD_MAX_WIDTH 4096
+/* Frame sizes: H and W positive multiples of 16 (four 2x2 poolings) with H * W <= VAD_MAX_FRAME_PIXELS = 2^23 - 1.  The kernels
+ * multiply pixel indices as 24-bit operands (4K UHD, 8,294,400 pixels, fits).  Every scoring and training entry point refuses a
+ * larger frame with VAD_ERR_ARG before anything is launched and every *_workspace_bytes query answers 0 for it; the layer entry
+ * points (vad_conv3x3*, vad_convlstm_step*, vad_convt2x2, vad_dec4_score) hold the same limit for their own h x w maps, next to
+ * the byte limit of 2^31 bytes per frame of any of their tensors. */
+#define VAD_MAX_FRAME_PIXELS 8388607
 /* The packed blob starts with a 16-byte header {magic "VADB", tag = abi<<16 | precision<<8 | model kind, dims}; the
  * layers follow.  Pack with the precision the blob will be launched with: the kernel that finalises the scores compares
  * the tag with the launch's `precision` on the device and returns NaN scores on a mismatch (never a silent wrong number).

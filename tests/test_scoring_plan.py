@@ -3,7 +3,9 @@ workspace each launch points, and what a call with one bad argument answers - al
 it was when every workspace layout was written twice (a size formula and a pointer walk) and every entry point spelled out its
 own argument checks.  No GPU needed: the library loads without one, and tests/score_launch_trace.cpp stands in for HIP.
 
-`VAD_LIB=<libvad_hip.so of the commit to record from> python tests/test_scoring_plan.py <that commit>` rewrites the fixtures."""
+`VAD_LIB=<libvad_hip.so of the commit to record from> python tests/test_scoring_plan.py <that commit>` rewrites the fixtures;
+with `add-refusals` behind the commit it only ADDS the refusal cases that scoring_refusals.json does not hold yet: every recorded
+entry must come out as recorded, and the file's source line gains the commit the new ones were recorded from."""
 import itertools
 import json
 import re
@@ -216,17 +218,20 @@ def refusal_cases(vad):
     seq = dict(x=X, precision=0, b=2, t=3, gh=3, gw=5, cin_p=32, hid_p=64, layers=2, packed=PACKED, ws=WS, ws_bytes=0, hseq_out=OUT, all_layers=0,
                state_in=STATE, state_out=STATE + 0x100000, stream=STREAM)
     misaligned_state = [("misaligned state_in", dict(state_in=STATE + 4)), ("misaligned state_out", dict(state_out=STATE + 4))]
+    # one pixel more than the kernels' 24-bit pixel indices hold (VAD_MAX_FRAME_PIXELS = 2^23 - 1); recorded behind the older cases
+    too_large = [("frame of 2^23 pixels", dict(h=4096, w=2048))]
     return {
         "vad_img_score_c": (img, "vad_img_workspace_bytes_c", ("chunk", "h", "w", "latent", "in_ch"),
-                            nulls("x", "packed", "ws") + common + none_of("scores", "errmap", "recon", "latent_out")),
+                            nulls("x", "packed", "ws") + common + none_of("scores", "errmap", "recon", "latent_out") + too_large),
         "vad_vid_score_s": (vid, "vad_vid_workspace_bytes_c", ("chunk", "t", "h", "w", "latent", "hid", "layers", "in_ch"),
-                            nulls("x", "packed", "ws") + common + none_of("seq_scores", "frame_scores", "errmap", "recon", "state_out") + misaligned_state),
+                            nulls("x", "packed", "ws") + common + none_of("seq_scores", "frame_scores", "errmap", "recon", "state_out") + misaligned_state + too_large),
         "vad_vid_score_windows_c": (win, "vad_vid_windows_workspace_bytes_c", ("chunk", "t", "stride", "h", "w", "latent", "hid", "layers", "in_ch"),
                                     nulls("x", "packed", "ws") + common + none_of("seq_scores", "frame_scores", "errmap", "recon")
-                                    + [("stride > T", dict(stride=5)), ("frames < T", dict(nframes=3))]),
+                                    + [("stride > T", dict(stride=5)), ("frames < T", dict(nframes=3))] + too_large),
         "vad_convlstm_seq": (seq, "vad_convlstm_seq_workspace_bytes", ("b", "t", "gh", "gw", "cin_p", "hid_p", "layers", "all_layers"),
                              nulls("x", "packed", "ws", "hseq_out") + [c for c in common if c[0] in ("bad precision", "workspace one byte short", "misaligned workspace", "misaligned weights")]
-                             + misaligned_state + [("misaligned x", dict(x=X + 4)), ("cin_p != hid_p in split mode", dict(precision=1))]),
+                             + misaligned_state + [("misaligned x", dict(x=X + 4)), ("cin_p != hid_p in split mode", dict(precision=1)),
+                                                   ("grid of 2^23 positions", dict(gh=4096, gw=2048))]),
     }
 
 
@@ -247,8 +252,80 @@ def test_refusals_are_the_recorded_ones(vad, lib):
     """Return code and vad_last_error() text of calls with ONE bad argument.  Every check runs before the first HIP call."""
     want = json.loads((GOLDEN / "scoring_refusals.json").read_text())["refusals"]
     got = refusals(vad, lib)
-    assert len(got) == 16 + 18 + 18 + 12 and all(rc < 0 and text for rc, text in got.values())
+    assert len(got) == 17 + 19 + 19 + 13 and all(rc < 0 and text for rc, text in got.values())
     assert got == want
+    over = {k: v for k, v in got.items() if "2^23" in k}
+    assert len(over) == 4 and all(rc == -1 and str(PIXEL_LIMIT) in text for rc, text in over.values()), over
+
+
+PIXEL_LIMIT = 2 ** 23 - 1                      # VAD_MAX_FRAME_PIXELS: the largest frame whose pixel indices fit a 24-bit multiply operand
+OVER = [(4096, 2048), (2048, 4096), (16, 2 ** 19), (4112, 2048)]          # 2^23 pixels three ways, and the next multiple of 16 rows
+UNDER = (4096, 2032)                           # 8,323,072 pixels: the largest 4096-row frame of 16-pixel steps below the limit
+
+
+def test_size_queries_refuse_frames_over_the_pixel_limit(vad, lib):
+    """Every workspace query answers 0 for a frame of 2^23 pixels or more - the scoring ones, the ConvLSTM roll-out's and the
+    trainers' - and a size for the largest frame below."""
+    queries = {
+        "vad_img_workspace_bytes": lambda h, w: (1, h, w, 32),
+        "vad_img_workspace_bytes_c": lambda h, w: (1, h, w, 32, 3),
+        "vad_vid_workspace_bytes": lambda h, w: (1, 1, h, w, 32, 32, 1),
+        "vad_vid_workspace_bytes_c": lambda h, w: (1, 1, h, w, 32, 32, 1, 3),
+        "vad_vid_windows_workspace_bytes": lambda h, w: (1, 2, 1, h, w, 32, 32, 1),
+        "vad_vid_windows_workspace_bytes_c": lambda h, w: (1, 2, 1, h, w, 32, 32, 1, 3),
+        "vad_convlstm_seq_workspace_bytes": lambda h, w: (1, 1, h, w, 32, 64, 1, 0),
+        "vad_img_train_workspace_bytes": lambda h, w: (1, h, w, 32),
+        "vad_vid_train_workspace_bytes": lambda h, w: (1, 1, h, w, 32, 32, 1),
+        "vad_vid_train_workspace_bytes_l": lambda h, w: (1, 1, h, w, 32, 32, 1, 2),
+    }
+    for name, args in queries.items():
+        fn = getattr(lib, name)
+        assert fn(*args(*UNDER)) > 0, name
+        for h, w in OVER:
+            assert fn(*args(h, w)) == 0, (name, h, w)
+
+
+def layer_refusal_cases(l):
+    """Layer entry point -> a call of it on one h x w frame with dummy, never-dereferenced pointers."""
+    P = X                                      # any non-null, 16-B aligned address
+    return {
+        "conv3x3": lambda h, w: l.vad_conv3x3(P, 0, P, P, P, 0, 1, h, w, 32, 32, 1, 0, 0, None),
+        "conv3x3 pooled, split": lambda h, w: l.vad_conv3x3(P, 0, P, P, P, 0, 1, h, w, 32, 32, 1, 1, 1, None),
+        "conv3x3_wino": lambda h, w: l.vad_conv3x3_wino(P, 0, P, P, P, 0, 1, h, w, 32, 32, 1, 0, None),
+        "convlstm_step": lambda h, w: l.vad_convlstm_step(P, 0, None, 0, None, P, P, P, 0, P, 1, h, w, 32, 64, 0, None),
+        "convlstm_step_wino": lambda h, w: l.vad_convlstm_step_wino(P, 0, None, 0, None, P, P, P, 0, P, P, 1, h, w, 32, 32, None),
+        "conv3x3_c3": lambda h, w: l.vad_conv3x3_c3(P, P, P, P, 1, h, w, 32, 1, 0, None),
+        "conv3x3_c3 pooled": lambda h, w: l.vad_conv3x3_c3(P, P, P, P, 1, h, w, 32, 1, 1, None),
+        "conv3x3_c3_fused": lambda h, w: l.vad_conv3x3_c3_fused(P, P, P, P, P, P, 1, h, w, 0, None),
+        "conv3x3_c3_fused split": lambda h, w: l.vad_conv3x3_c3_fused(P, P, P, P, P, P, 1, h, w, 1, None),
+        "convt2x2": lambda h, w: l.vad_convt2x2(P, 0, P, P, P, 0, 1, h, w, 32, 32, 2, 0, None),
+        "dec4_score": lambda h, w: l.vad_dec4_score(P, P, P, P, P, P, P, P, P, 1, h, w, None),
+    }
+
+
+def test_layer_entry_points_refuse_frames_over_the_pixel_limit(lib):
+    """One bad argument - a frame of 2^23 pixels or more - at every layer entry point whose kernel multiplies a pixel index as a
+    24-bit operand (and at vad_conv3x3_c3, the first layer in front of them): VAD_ERR_ARG before the first HIP call, and the
+    message names the limit.  The un-pooled first layer also counts its output in BYTES: 128 channels of a 4096 x 1024 frame are
+    2^29 elements but 2^31 bytes, the limit of every other layer's offsets inside one frame."""
+    for name, call in layer_refusal_cases(lib).items():
+        for h, w in OVER:
+            assert call(h, w) == -1, (name, h, w)
+            text = lib.vad_last_error().decode()
+            assert name.split()[0] + ":" in text and str(PIXEL_LIMIT) in text and f"{h}x{w}" in text, (name, text)
+    assert lib.vad_conv3x3_c3(X, X, X, X, 1, 4096, 1024, 128, 0, 0, None) == -1
+    assert "2^31 bytes" in lib.vad_last_error().decode()
+    # the bf16 1x1 convolution runs a pixel count that is no multiple of 16 as ONE ragged frame of 16-pixel rows: the same limit
+    # (VAD_PREC_BF16S = 3)
+    assert lib.vad_conv1x1_p(X, X, X, X, 2 ** 23 + 1, 32, 32, 3, None) == -1
+    text = lib.vad_last_error().decode()
+    assert "conv1x1 (bf16):" in text and str(PIXEL_LIMIT) in text, text
+    # the trainers refuse the same frames before anything is launched (their plans; dummy pointers, a workspace of any size)
+    for h, w in OVER:
+        assert lib.vad_img_train_fwd_bwd(X, 1, h, w, 32, X, X, X, X, 1 << 40, 0, 0.0, 11, 0, X, None, None) == -1
+        assert str(PIXEL_LIMIT) in lib.vad_last_error().decode()
+        assert lib.vad_vid_train_fwd_bwd(X, 1, 1, h, w, 32, 32, 1, X, X, X, X, 1 << 40, 0, X, None, None) == -1
+        assert str(PIXEL_LIMIT) in lib.vad_last_error().decode()
 
 
 if __name__ == "__main__":                     # record the fixtures from the library VAD_LIB names
@@ -258,6 +335,15 @@ if __name__ == "__main__":                     # record the fixtures from the li
     pkg = importlib.import_module("video-anomaly-detection_amd")
     source, l = f"recorded from commit {sys.argv[1]}", pkg.hip.lib()
     dump = lambda name, obj: (GOLDEN / name).write_text(json.dumps(dict(source=source, **obj), separators=(",", ":")) + "\n")
+    if sys.argv[2:] == ["add-refusals"]:
+        old, now = json.loads((GOLDEN / "scoring_refusals.json").read_text()), refusals(pkg, l)
+        changed = [k for k, v in old["refusals"].items() if now.get(k) != v]
+        assert not changed, f"recorded refusals came out differently: {changed}"
+        added = [k for k in now if k not in old["refusals"]]
+        source = f"{old['source']}; new cases recorded from commit {sys.argv[1]}"
+        dump("scoring_refusals.json", dict(refusals=now))
+        print(source, pkg.hip.LIB_PATH, "added", added)
+        sys.exit(0)
     dump("scoring_ws_bytes.json", {name: dict(axes=axes, bytes=sizes(l, name, axes)) for name, axes in size_grids(pkg).items()})
     dump("scoring_refusals.json", dict(refusals=refusals(pkg, l)))
     with tempfile.TemporaryDirectory() as tmp:

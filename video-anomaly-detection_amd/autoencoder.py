@@ -291,7 +291,7 @@ class ConvAutoencoder(nn.Module):
         chunk = max(1, min(int(self.chunk), b))
         nbytes = l.vad_img_workspace_bytes_c(chunk, h, w, self.latent_dim, kc)
         if nbytes == 0:
-            raise hip.VadError(f"unsupported frame size {h}x{w}: H and W must be multiples of 16")
+            raise hip.VadError(f"unsupported frame size {h}x{w}: {hip.FRAME_RULE}")
         ws = self._hip.workspace(nbytes, dev)
         if out is None:                                   # (a captured call hands in its own output tensors)
             out = {}

@@ -490,6 +490,7 @@ int vad_conv3x3_kpart(const float* in, long long in_fs, const float* w, const fl
     VAD_REQUIRE_PREC("conv3x3");
     const ConvKnobs kn;
     VAD_REQUIRE(n > 0 && h > 0 && wd > 0, "conv3x3: bad shape n=%d h=%d w=%d", n, h, wd);
+    VAD_REQUIRE_PIXELS("conv3x3", h, wd);
     VAD_REQUIRE(cin % 32 == 0 && cout % 32 == 0 && cin > 0 && cout > 0,
                 "conv3x3: cin=%d cout=%d must be positive multiples of 32", cin, cout);
     VAD_REQUIRE(!pool || (h % 2 == 0 && wd % 2 == 0), "conv3x3: pooling needs even H,W (got %dx%d)", h, wd);
@@ -592,6 +593,8 @@ int vad_conv3x3_c3_fused_fmt(const void* x, int fmt, const float* w0, const floa
     VAD_REQUIRE(fmt == VAD_X_F32_NCHW || (fmt == VAD_X_U8_NHWC && (kn.variant != 0 || precision == VAD_PREC_SPLIT)),
                 "conv3x3_c3_fused: input format %d unsupported (uint8 input needs the persistent kernel)", fmt);
     VAD_REQUIRE(n > 0 && h > 0 && wd > 0 && h % 2 == 0 && wd % 2 == 0, "conv3x3_c3_fused: bad shape %dx%d", h, wd);
+    // the plane stride H*W is itself a 24-bit operand; 12 H W input bytes and 32 H W output bytes per frame then stay far below 2^31
+    VAD_REQUIRE_PIXELS("conv3x3_c3_fused", h, wd);
     Conv3P p{};
     p.in = (const float*)x; p.in_fs = (long long)3 * h * wd; p.cin_a = 32;   // frame stride in ELEMENTS of the input type
     p.w = w1; p.bias = b1; p.out = out; p.out_fs = (long long)(h / 2) * (wd / 2) * 32;
@@ -655,6 +658,7 @@ int vad_convlstm_step_zx(const float* x, long long x_fs, const float* zx, long l
     VAD_REQUIRE(precision == VAD_PREC_FP32 || precision == VAD_PREC_SPLIT, "convlstm_step: precision=%d must be VAD_PREC_FP32 (0) or VAD_PREC_SPLIT (1)", precision);
     VAD_REQUIRE((h_prev == nullptr) == (c_prev == nullptr), "convlstm_step: h_prev and c_prev must both be given or both NULL");
     VAD_REQUIRE(n > 0 && h > 0 && wd > 0, "convlstm_step: bad shape");
+    VAD_REQUIRE_PIXELS("convlstm_step", h, wd);
     VAD_REQUIRE(cin_x % 32 == 0 && hid % 64 == 0 && cin_x > 0 && hid > 0,
                 "convlstm_step: cin_x=%d must be a multiple of 32 and hid=%d a multiple of 64", cin_x, hid);
     Conv3P p{};
@@ -1105,6 +1109,7 @@ int vad_conv3x3_c3_stats_t(const void* x, int fmt, const float* w, const float* 
     VAD_REQUIRE(x && w && bias && out, "conv3x3_c3: null pointer");
     VAD_REQUIRE(fmt == VAD_X_F32_NCHW || fmt == VAD_X_U8_NHWC, "conv3x3_c3: bad input format %d", fmt);
     VAD_REQUIRE(n > 0 && h > 0 && wd > 0 && cout > 0 && cout % 32 == 0, "conv3x3_c3: bad shape");
+    VAD_REQUIRE_PIXELS("conv3x3_c3", h, wd);   // (the frame limit of every layer behind it; this kernel's own offsets are plain 32-bit products)
     VAD_REQUIRE(!pool || (h % 2 == 0 && wd % 2 == 0), "conv3x3_c3: pooling needs even H,W");
     VAD_REQUIRE(act == VAD_ACT_LEAKY || act == VAD_ACT_RELU || act == VAD_ACT_NONE, "conv3x3_c3: bad act");
     hipStream_t s = (hipStream_t)stream;
@@ -1115,8 +1120,10 @@ int vad_conv3x3_c3_stats_t(const void* x, int fmt, const float* w, const float* 
     // 256x256 frame: 2.6 us/frame = 3.5 TB/s with the scalar-offset buffer stores (the one-tile-per-work-group kernel, with a
     // 64-bit address computed per store, needs 3.8 us; an earlier persistent form with the same address arithmetic 6.5 us).
     if (kn.variant != 0) {
-        VAD_REQUIRE(12ll * h * wd < (1ll << 31) && (long long)h * wd * cout < (1ll << 31),
-                    "conv3x3_c3: frame %dx%d (cout %d) too large for the 32-bit offsets inside one frame", h, wd, cout);
+        // byte offsets inside one frame: the input planes and the output map (4 bytes per element, 2 as bf16), pooled or not
+        const long long out_bytes = (long long)(pool ? h / 2 : h) * (pool ? wd / 2 : wd) * cout * (out16 ? 2 : 4);
+        VAD_REQUIRE(12ll * h * wd < (1ll << 31) && out_bytes < (1ll << 31),
+                    "conv3x3_c3: frame %dx%d (cout %d: %lld output bytes) too large for the 32-bit offsets inside one frame (2^31 bytes)", h, wd, cout, out_bytes);
         ConvC3P p{(const float*)x, w, bias, out, h, wd, cout, (wd + 15) / 16, (h + 31) / 32, 0, fmt == VAD_X_U8_NHWC, nullptr};
         const long long nb = (long long)n * p.tiles_x * p.tiles_y;
         VAD_REQUIRE(nb < (1ll << 31), "conv3x3_c3: grid too large");
@@ -1328,6 +1335,9 @@ int vad_convt2x2_stats(const float* in, long long in_fs, const float* w, const f
     VAD_REQUIRE_PREC("convt2x2");
     const ConvKnobs kn;
     VAD_REQUIRE(n > 0 && h > 0 && wd > 0, "convt2x2: bad shape");
+    // the persistent kernel's INPUT pixel index is the 24-bit operand (its output offsets are 32-bit products); the one-tile
+    // debug variant below addresses in 64 bits and carries the limit by policy, not by need: one frame limit for every form
+    VAD_REQUIRE_PIXELS("convt2x2", h, wd);
     VAD_REQUIRE(cin % 32 == 0 && cout % 32 == 0 && cin > 0 && cout > 0,
                 "convt2x2: cin=%d cout=%d must be positive multiples of 32", cin, cout);
     VAD_REQUIRE(act >= 0 && act <= 2, "convt2x2: bad act");
@@ -1431,7 +1441,9 @@ int vad_conv1x1_p(const void* in, const float* w, const float* bias, void* out, 
         n = rows / h;
     } else {                                   // ragged: one frame of ceil(npix / 16) rows whose last row is partly valid
         const long long rows = (npix + 15) / 16;
-        VAD_REQUIRE(rows < (1 << 24), "conv1x1 (bf16): %lld pixels (not a multiple of 16) are too many for one ragged frame", npix);
+        // the kernel's 24-bit pixel index (convt_pkernel.h) over the frame's rows x 16 positions
+        VAD_REQUIRE(rows * 16 <= VAD_MAX_FRAME_PIXELS, "conv1x1 (bf16): %lld pixels (not a multiple of 16) are too many for one ragged frame: the limit is %d "
+                    "(2^23 - 1: pixel indices are 24-bit multiply operands inside the kernels)", npix, VAD_MAX_FRAME_PIXELS);
         h = (int)rows;
         frame_pix = (int)npix;
     }

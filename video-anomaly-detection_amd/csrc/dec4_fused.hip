@@ -444,6 +444,7 @@ int vad_dec4_score_fmt(const float* in, const float* wt_packed, const float* bt,
     VAD_REQUIRE(in && wt_packed && bt && w2_gemm && bias3 && x && partials, "dec4_score: null pointer");
     VAD_REQUIRE(fmt == VAD_X_F32_NCHW || fmt == VAD_X_U8_NHWC, "dec4_score: bad input format %d", fmt);
     VAD_REQUIRE(n > 0 && h > 0 && w > 0 && w % 8 == 0, "dec4_score: bad shape n=%d %dx%d (W must be a positive multiple of 8)", n, h, w);
+    VAD_REQUIRE_PIXELS("dec4_score", h, w);      // the input map's pixel index; 128 H W input and 48 H W original-frame bytes stay below 2^31
     VAD_REQUIRE((long long)h * w * 32 * 4 < (1ll << 31), "dec4_score: frame %dx%d too large for 32-bit offsets", h, w);
     VAD_REQUIRE(((uintptr_t)wt_packed & 15) == 0 && ((uintptr_t)in & 15) == 0, "dec4_score: weights and activations must be 16-B aligned");
     Dec4P p{};

@@ -109,7 +109,7 @@ extern "C" size_t vad_convlstm_state_floats(int b, int gh, int gw, int hid_p, in
     return (size_t)2 * layers * b * gh * gw * hid_p;
 }
 extern "C" size_t vad_vid_state_floats(int b, int h, int w, int hid, int layers) {
-    if (h <= 0 || w <= 0 || h % 16 || w % 16 || hid <= 0 || hid > VAD_MAX_WIDTH) return 0;
+    if (h <= 0 || w <= 0 || h % 16 || w % 16 || !vad_frame_pixels_ok(h, w) || hid <= 0 || hid > VAD_MAX_WIDTH) return 0;   // (no model scores such frames)
     return vad_convlstm_state_floats(b, h / 16, w / 16, vad_pad_up(hid, 64), layers);
 }
 

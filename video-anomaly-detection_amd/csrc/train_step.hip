@@ -56,7 +56,7 @@ size_t align64(size_t v) { return (v + 63) & ~(size_t)63; }
 bool make_plan(Plan& p, int B, int T, int H, int W, int L, int Hd, int NL, int kind = 0) {
     if (kind < 0 || kind > 2) return false;
     p.kind = kind;
-    if (B <= 0 || T <= 0 || H <= 0 || W <= 0 || H % 16 || W % 16 || L <= 0 || L % 32 || Hd <= 0 || Hd % 32 || Hd > 256 || NL < 1 || NL > 8) return false;
+    if (B <= 0 || T <= 0 || H <= 0 || W <= 0 || H % 16 || W % 16 || !vad_frame_pixels_ok(H, W) || L <= 0 || L % 32 || Hd <= 0 || Hd % 32 || Hd > 256 || NL < 1 || NL > 8) return false;
     if ((long long)B * T > (1 << 20)) return false;
     p.B = B; p.T = T; p.H = H; p.W = W; p.L = L; p.Hd = Hd; p.NL = NL; p.N = B * T;
     p.proj = Hd != L;
@@ -326,8 +326,8 @@ extern "C" int vad_vid_train_fwd_bwd_l(const float* x, int b, int t, int h, int 
     // data gradients and the first layer's forward on bf16 operands too.
     Plan p;
     VAD_REQUIRE(make_plan(p, b, t, h, w, latent, hid, layers, loss_kind),
-                "vid_train_fwd_bwd: unsupported configuration (B=%d T=%d %dx%d latent=%d hid=%d layers=%d): H, W multiples of 16, "
-                "latent and hidden multiples of 32, hidden <= 256, 1..8 layers", b, t, h, w, latent, hid, layers);
+                "vid_train_fwd_bwd: unsupported configuration (B=%d T=%d %dx%d latent=%d hid=%d layers=%d): H, W multiples of 16 with H*W <= %d pixels, "
+                "latent and hidden multiples of 32, hidden <= 256, 1..8 layers", b, t, h, w, latent, hid, layers, VAD_MAX_FRAME_PIXELS);
     if (workspace_bytes < p.ws_floats * sizeof(float))
         return vad_fail(VAD_ERR_WS, "vid_train_fwd_bwd: workspace %zu bytes < %zu needed", workspace_bytes, p.ws_floats * sizeof(float));
     // bf16 tensors: the BatchNorm statistics come from the convolutions' accumulators and from nowhere else (there is no

@@ -33,7 +33,7 @@ struct ImgPlan {
 size_t align64(size_t v) { return (v + 63) & ~(size_t)63; }
 
 bool make_plan(ImgPlan& p, int N, int H, int W, int L) {
-    if (N <= 0 || H <= 0 || W <= 0 || H % 16 || W % 16 || L <= 0 || L % 32 || L > 1024 || N > (1 << 20)) return false;
+    if (N <= 0 || H <= 0 || W <= 0 || H % 16 || W % 16 || !vad_frame_pixels_ok(H, W) || L <= 0 || L % 32 || L > 1024 || N > (1 << 20)) return false;
     p.N = N; p.H = H; p.W = W; p.L = L;
     const int c[5] = {3, 32, 64, 128, L}, d[5] = {L, 128, 64, 32, 32};
     for (int i = 0; i < 5; ++i) { p.c[i] = c[i]; p.d[i] = d[i]; }
@@ -162,7 +162,7 @@ extern "C" int vad_img_train_fwd_bwd(const float* x, int n, int h, int w, int la
     VAD_REQUIRE(loss_kind >= 0 && loss_kind <= 2, "img_train_fwd_bwd: loss_kind must be 0 (mse), 1 (ssim) or 2 (combined)");
     ImgPlan p;
     VAD_REQUIRE(make_plan(p, n, h, w, latent), "img_train_fwd_bwd: unsupported configuration (N=%d %dx%d latent=%d): H, W multiples "
-                "of 16, latent a multiple of 32", n, h, w, latent);
+                "of 16 with H*W <= %d pixels, latent a multiple of 32", n, h, w, latent, VAD_MAX_FRAME_PIXELS);
     if (workspace_bytes < p.ws_floats * sizeof(float))
         return vad_fail(VAD_ERR_WS, "img_train_fwd_bwd: workspace %zu bytes < %zu needed", workspace_bytes, p.ws_floats * sizeof(float));
     hipStream_t s = (hipStream_t)stream;

@@ -123,12 +123,15 @@ extern "C" int vad_debug_set_tail_group(int frames) { g_vad_tail_group = frames;
 
 // ------------------------------------------------------------------------------ argument checks of the scoring entry points
 // `who` is the entry point's name in the message.  The size functions use the predicates and return 0 silently.
-static bool frame_shape_ok(int h, int w) { return h > 0 && w > 0 && h % 16 == 0 && w % 16 == 0; }
+// (frames of more than VAD_MAX_FRAME_PIXELS pixels do not fit the kernels' 24-bit pixel indices, vad_common.h)
+static bool frame_shape_ok(int h, int w) { return h > 0 && w > 0 && h % 16 == 0 && w % 16 == 0 && vad_frame_pixels_ok(h, w); }
 static bool in_ch_ok(int in_ch) { return in_ch >= 3 && in_ch <= VAD_MAX_IN_CH; }
 static bool aligned(const void* p, uintptr_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
 
 static int req_frame_shape(const char* who, int h, int w, const char* why) {
-    VAD_REQUIRE(frame_shape_ok(h, w), "%s: H=%d W=%d must be positive multiples of 16%s", who, h, w, why);
+    VAD_REQUIRE(h > 0 && w > 0 && h % 16 == 0 && w % 16 == 0, "%s: H=%d W=%d must be positive multiples of 16%s", who, h, w, why);
+    VAD_REQUIRE(vad_frame_pixels_ok(h, w), "%s: H=%d W=%d is a frame of %lld pixels, the limit is %d (2^23 - 1: pixel indices are 24-bit multiply operands inside the kernels)",
+                who, h, w, (long long)h * w, VAD_MAX_FRAME_PIXELS);
     return VAD_OK;
 }
 static int req_precision(const char* who, int p) {
@@ -662,6 +665,8 @@ size_t seq_carve(void* ws, LstmRun& R, int b, int t, int gh, int gw, int hid_p, 
 }
 int seq_dims_ok(const char* who, long long b, int t, int gh, int gw, int cin_p, int hid_p, int layers) {
     VAD_REQUIRE(b > 0 && b < (1ll << 24) && t > 0 && gh > 0 && gw > 0, "%s: bad shape b=%lld T=%d grid=%dx%d", who, b, t, gh, gw);
+    VAD_REQUIRE(vad_frame_pixels_ok(gh, gw), "%s: grid=%dx%d has %lld positions, the limit is %d (2^23 - 1: pixel indices are 24-bit multiply operands inside the kernels)",
+                who, gh, gw, (long long)gh * gw, VAD_MAX_FRAME_PIXELS);
     VAD_REQUIRE(vad_convlstm_packed_floats(cin_p, hid_p, layers) != 0,
                 "%s: cin_p=%d must be a positive multiple of 32, hid_p=%d of 64, layers=%d in [1,8]", who, cin_p, hid_p, layers);
     return VAD_OK;
@@ -669,7 +674,7 @@ int seq_dims_ok(const char* who, long long b, int t, int gh, int gw, int cin_p, 
 }  // namespace
 
 extern "C" size_t vad_convlstm_seq_workspace_bytes(int b, int t, int gh, int gw, int cin_p, int hid_p, int layers, int all_layers) {
-    if (b <= 0 || t <= 0 || gh <= 0 || gw <= 0 || vad_convlstm_packed_floats(cin_p, hid_p, layers) == 0) return 0;
+    if (b <= 0 || t <= 0 || gh <= 0 || gw <= 0 || !vad_frame_pixels_ok(gh, gw) || vad_convlstm_packed_floats(cin_p, hid_p, layers) == 0) return 0;
     LstmRun R{};
     const size_t n = seq_carve(nullptr, R, b, t, gh, gw, hid_p, layers, all_layers);
     return n ? n : 256;

@@ -23,6 +23,17 @@ int vad_fail(int code, const char* fmt, ...);
         if (!(cond)) return vad_fail(VAD_ERR_ARG, __VA_ARGS__); \
     } while (0)
 
+// Frame-size limit of every entry point that takes H x W frames or maps.  The persistent kernels form in-frame offsets as
+// __mul24(__mul24(y, W) + x, channels) (conv_pkernel.h, conv_small.h, conv_wino.hip, convt_pkernel.h, dec4_fused.hip), and the
+// fused first layer multiplies the plane index by __mul24(H, W): v_mul_i32_i24 sign-extends its operands from bit 23, so a
+// pixel index - and H*W itself - of 2^23 or more turns negative, the offset falls outside the buffer descriptor, loads return 0
+// and stores are dropped without any error.  The byte limits (one frame of a tensor below 2^31 bytes) come on top.
+// (VAD_MAX_FRAME_PIXELS = 2^23 - 1: include/vad_hip.h)
+static inline bool vad_frame_pixels_ok(int h, int w) { return (long long)h * w <= VAD_MAX_FRAME_PIXELS; }
+#define VAD_REQUIRE_PIXELS(who, h, w)                                                                                              \
+    VAD_REQUIRE(vad_frame_pixels_ok(h, w), who ": %dx%d = %lld pixels per frame exceed the limit of %d (2^23 - 1: pixel indices are " \
+                "24-bit multiply operands inside the kernels)", h, w, (long long)(h) * (w), VAD_MAX_FRAME_PIXELS)
+
 // A positive, finite power of two: multiplying by it is exact (up to overflow / underflow), which is what the gradient
 // rescaling of the split-fp16 training mode relies on.
 static inline bool vad_is_pow2f(float v) {

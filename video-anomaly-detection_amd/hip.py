@@ -49,6 +49,8 @@ HIST_MIN_M, HIST_MAX_M = 4, 15
 PRO_WEIGHT_BITS = 44     # VAD_PRO_WEIGHT_BITS: a region adds (2^44 + |r| / 2) // |r| per pixel to the weighted histogram
 PROF_SLOTS = 32
 MAX_WIDTH = 4096          # VAD_MAX_WIDTH: largest latent_dim / lstm_hidden_dim
+MAX_FRAME_PIXELS = 2 ** 23 - 1    # VAD_MAX_FRAME_PIXELS: largest H * W (pixel indices are 24-bit multiply operands inside the kernels)
+FRAME_RULE = f"H and W must be multiples of 16 with H * W <= {MAX_FRAME_PIXELS}"
 
 _lock = threading.Lock()
 _lib = None

@@ -254,7 +254,7 @@ class VideoTrainer(_FlatTrainer):
     def _workspace(self, b, t, h, w) -> torch.Tensor:
         nbytes = hip.lib().vad_vid_train_workspace_bytes_l(b, t, h, w, *self.cfg, self._KINDS[self.loss])
         if nbytes == 0:
-            raise hip.VadError(f"unsupported training shape B={b} T={t} {h}x{w}: H and W must be multiples of 16")
+            raise hip.VadError(f"unsupported training shape B={b} T={t} {h}x{w}: {hip.FRAME_RULE}")
         return self._ensure_ws(nbytes)
 
     def forward_backward(self, clips: torch.Tensor, recon: bool = False):
@@ -303,7 +303,7 @@ class ImageTrainer(_FlatTrainer):
         l = hip.lib()
         nbytes = l.vad_img_train_workspace_bytes(b, h, w, self.latent)
         if nbytes == 0:
-            raise hip.VadError(f"unsupported training shape B={b} {h}x{w}: H and W must be multiples of 16")
+            raise hip.VadError(f"unsupported training shape B={b} {h}x{w}: {hip.FRAME_RULE}")
         ws = self._ensure_ws(nbytes)
         out = torch.empty_like(x) if recon else None
         with torch.cuda.device(self.device):

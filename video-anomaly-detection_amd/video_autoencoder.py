@@ -248,7 +248,7 @@ class VideoState:
         """The state of `b` fresh streams of h x w frames."""
         n = hip.lib().vad_vid_state_floats(b, h, w, model.lstm_hidden_dim, model.lstm_num_layers)
         if n == 0:
-            raise hip.VadError(f"no state exists for {b} streams of {h}x{w} (H and W must be multiples of 16)")
+            raise hip.VadError(f"no state exists for {b} streams of {h}x{w} ({hip.FRAME_RULE})")
         return cls(torch.zeros(n, dtype=torch.float32, device=device), b, h, w, model.lstm_hidden_dim, model.lstm_num_layers)
 
     @classmethod
@@ -410,7 +410,7 @@ class VideoAutoencoder(nn.Module):
         dims = (self.latent_dim, self.lstm_hidden_dim, self.lstm_num_layers)
         nbytes = l.vad_vid_workspace_bytes_c(chunk, t, h, w, *dims, kc)
         if nbytes == 0:
-            raise hip.VadError(f"unsupported frame size {h}x{w}: H and W must be multiples of 16")
+            raise hip.VadError(f"unsupported frame size {h}x{w}: {hip.FRAME_RULE}")
         ws = self._hip.workspace(nbytes, dev)
         if out is None:                                   # (a captured call hands in its own output tensors)
             out = {}
@@ -523,7 +523,7 @@ class VideoAutoencoder(nn.Module):
         kc = _HipScorer.kernel_channels(cin)
         nbytes = l.vad_vid_windows_workspace_bytes_c(chunk, t, int(stride), h, w, *dims, kc)
         if nbytes == 0:
-            raise hip.VadError(f"unsupported frame size {h}x{w}: H and W must be multiples of 16")
+            raise hip.VadError(f"unsupported frame size {h}x{w}: {hip.FRAME_RULE}")
         ws = self._hip.workspace(nbytes, dev)
         out = {"seq": torch.empty(nw, dtype=torch.float32, device=dev),
                "frame": torch.empty(nw, t, dtype=torch.float32, device=dev)}
@@ -562,7 +562,7 @@ class VideoAutoencoder(nn.Module):
         if state is None or not inplace:
             n = hip.lib().vad_vid_state_floats(b, h, w, self.lstm_hidden_dim, self.lstm_num_layers)
             if n == 0:
-                raise hip.VadError(f"unsupported frame size {h}x{w}: H and W must be multiples of 16")
+                raise hip.VadError(f"unsupported frame size {h}x{w}: {hip.FRAME_RULE}")
             new = VideoState(torch.empty(n, dtype=torch.float32, device=frames.device), b, h, w, self.lstm_hidden_dim,
                              self.lstm_num_layers)
         else:
