@@ -8,6 +8,10 @@
  * Every `workspace` / `ws` argument is caller-owned device scratch of the size the matching size function reports: its contents
  * on entry are irrelevant, and no byte outside [ws, ws + size) is read or written.
  *
+ * Non-finite data: a NaN (either sign bit) in an input, a state, a weight, a bias or a BatchNorm parameter is never erased - every
+ * output whose receptive field holds it is NaN, no other frame's output changes a bit, and scores / losses are non-finite
+ * whenever the reference's are (never a silent wrong number).
+ *
  * Return value: VAD_OK or a negative VAD_ERR_*; vad_last_error() gives the text.
  */
 #ifndef VAD_HIP_H

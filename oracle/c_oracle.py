@@ -120,6 +120,12 @@ def maxpool2(x):
     return y
 
 
+def relu(x):
+    y = np.array(x, dtype=np.float32, order="C")
+    lib().vo_relu(_p(y), C.c_size_t(y.size))
+    return y
+
+
 def convlstm_cell(x, h, c, w, b):
     """-> (h', c') for one step; inputs are not modified."""
     x = np.ascontiguousarray(x, np.float32)

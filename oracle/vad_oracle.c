@@ -81,13 +81,17 @@ void vo_leaky_relu(float* x, size_t n, float slope) {
 #pragma omp parallel for schedule(static)
     for (size_t i = 0; i < n; ++i) x[i] = x[i] > 0.f ? x[i] : slope * x[i];
 }
-void vo_relu(float* x, size_t n) { vo_leaky_relu(x, n, 0.f); }
+/* relu(NaN) = NaN, relu(-Inf) = 0 like torch's (0 * x would make -Inf a NaN) */
+void vo_relu(float* x, size_t n) {
+#pragma omp parallel for schedule(static)
+    for (size_t i = 0; i < n; ++i) x[i] = (x[i] > 0.f || x[i] != x[i]) ? x[i] : 0.f;
+}
 void vo_tanh(float* x, size_t n) {
 #pragma omp parallel for schedule(static)
     for (size_t i = 0; i < n; ++i) x[i] = (float)tanh((double)x[i]);
 }
 
-/* nn.MaxPool2d(2, 2) */
+/* nn.MaxPool2d(2, 2): a NaN anywhere in the window is the result, as in torch (m stays NaN: no later v > m holds) */
 void vo_maxpool2(const float* x, float* y, int N, int C, int H, int W) {
     const int Ho = H / 2, Wo = W / 2;
 #pragma omp parallel for schedule(static)
@@ -95,10 +99,10 @@ void vo_maxpool2(const float* x, float* y, int N, int C, int H, int W) {
         for (int oy = 0; oy < Ho; ++oy)
             for (int ox = 0; ox < Wo; ++ox) {
                 const float* p = x + ((size_t)nc * H + 2 * oy) * W + 2 * ox;
+                const float v[3] = {p[1], p[W], p[W + 1]};
                 float m = p[0];
-                if (p[1] > m) m = p[1];
-                if (p[W] > m) m = p[W];
-                if (p[W + 1] > m) m = p[W + 1];
+                for (int k = 0; k < 3; ++k)
+                    if (v[k] > m || v[k] != v[k]) m = v[k];
                 y[((size_t)nc * Ho + oy) * Wo + ox] = m;
             }
 }

@@ -98,6 +98,44 @@ def test_convlstm_unit(vad, golden):
     assert max_abs(h, g["h_last"]) < 1e-5 and max_abs(c, g["c_last"]) < 1e-5
 
 
+def _f32_bits(bits):
+    return np.array([bits], np.uint32).view(np.float32)[0]
+
+
+NONFINITE = {"+nan": _f32_bits(0x7FC00000), "-nan": _f32_bits(0xFFC00000), "+inf": np.float32(np.inf), "-inf": np.float32(-np.inf)}
+
+
+@pytest.mark.parametrize("poison", list(NONFINITE))
+def test_maxpool_relu_nonfinite_like_torch(poison):
+    """vo_maxpool2 / vo_relu against torch.nn.MaxPool2d / relu in float64 with one non-finite element at every position of a
+    2x2 window (and two of them in one window, every pair of positions): the same elements are NaN, the others are equal
+    bit for bit (a maximum selects, it does not round).  NaN of either sign bit; max(-Inf, x) = x and relu(-Inf) = 0 stay."""
+    bad = NONFINITE[poison]
+    rng = np.random.default_rng(17)
+    base = rng.standard_normal((2, 3, 6, 8)).astype(np.float32)
+    base[0, 0, 0, 0:2] = [-0.0, 0.0]                       # a window that holds both zeros
+    cases = [[(dy, dx)] for dy in range(2) for dx in range(2)]
+    cases += [[a[0], b[0]] for i, a in enumerate(cases) for b in cases[i + 1:]]
+    cases += [[(0, 0), (0, 1), (1, 0), (1, 1)]]
+    for pos in cases:
+        x = base.copy()
+        for (dy, dx) in pos:
+            x[1, 2, 2 + dy, 4 + dx] = bad                  # window (1, 2) of plane (1, 2): interior
+            x[0, 0, 4 + dy, 6 + dx] = bad                  # the last window of plane (0, 0)
+        with np.errstate(invalid="ignore"):
+            want = torch.nn.MaxPool2d(2, 2)(torch.from_numpy(x).double()).numpy()
+            got = c_oracle.maxpool2(x)
+            assert np.array_equal(np.isnan(got), np.isnan(want)), (poison, pos)
+            ok = ~np.isnan(want)
+            assert np.array_equal(got[ok].astype(np.float64), want[ok]), (poison, pos)
+            if "nan" in poison:
+                assert np.isnan(got[1, 2, 1, 2]) and np.isnan(got[0, 0, 2, 3]) and np.isnan(got).sum() == 2
+            wr = torch.relu(torch.from_numpy(x).double()).numpy()
+            gr = c_oracle.relu(x)
+            assert np.array_equal(np.isnan(gr), np.isnan(wr)) and np.array_equal(gr[~np.isnan(wr)].astype(np.float64), wr[~np.isnan(wr)])
+            assert np.isnan(wr).sum() == (2 * len(pos) if "nan" in poison else 0)
+
+
 def test_score_semantics(vad, golden):
     """Properties the survey measured on the reference: score == spatial mean of the
     per-pixel map; clip score == mean of frame scores; frame score == mean of its map."""

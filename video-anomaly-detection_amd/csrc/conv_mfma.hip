@@ -244,7 +244,7 @@ __global__ __launch_bounds__(256) void conv3x3_mfma_kernel(Conv3P p) {
 #pragma unroll
                     for (int pos = 0; pos < 4; ++pos) v[pos] = vad_act(acc[mt][nt][4 * q + pos], ACT);
                     if (MODE == MODE_POOL) {
-                        const float m = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+                        const float m = vad_vmax4(v[0], v[1], v[2], v[3]);
                         const int oy = (y0 >> 1) + (wm * MT + mt), ox = (x0 >> 1) + wq;
                         if (oy < (p.h >> 1) && ox < (p.w_ >> 1))
                             p.out[(size_t)n * p.out_fs + ((size_t)oy * (p.w_ >> 1) + ox) * p.cout + co] = m;
@@ -771,7 +771,7 @@ __global__ __launch_bounds__(256) void conv3x3_c3_kernel(ConvC3P p) {
 #pragma unroll
                 for (int pos = 0; pos < 4; ++pos) v[pos] = vad_act(acc[4 * q + pos], ACT);
                 if (POOL) {
-                    const float m = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+                    const float m = vad_vmax4(v[0], v[1], v[2], v[3]);
                     const int oy = (y0 >> 1) + (wave * MT + mt), ox = (x0 >> 1) + wq;
                     if (oy < (p.h >> 1) && ox < (p.w_ >> 1))
                         p.out[(((size_t)n * (p.h >> 1) + oy) * (p.w_ >> 1) + ox) * p.cout + co] = m;
@@ -1014,8 +1014,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c3_pkernel(ConvC3P p) {
                     for (int q = 0; q < 4; ++q) {
                         if constexpr (POOL) {
                             // MaxPool2d(act(.)) == act(MaxPool2d(.)) bit for bit (ReLU / LeakyReLU are non-decreasing): one activation
-                            // per window instead of four; vad_vmax = one v_max_f32 (fmaxf adds a canonicalising max per operand)
-                            const float m = vad_act(vad_vmax(vad_vmax(acc[mt][4 * q], acc[mt][4 * q + 1]), vad_vmax(acc[mt][4 * q + 2], acc[mt][4 * q + 3])), ACT);
+                            // per window instead of four; vad_vmax = the NaN-propagating maximum (vad_common.h)
+                            const float m = vad_act(vad_vmax4(acc[mt][4 * q], acc[mt][4 * q + 1], acc[mt][4 * q + 2], acc[mt][4 * q + 3]), ACT);
                             // lane part (column half, channel) + scalar part (row, column pair); a window outside the pooled image
                             // (partial tiles only) gets the out-of-range offset and the store is dropped
                             unsigned vo = lanepart;

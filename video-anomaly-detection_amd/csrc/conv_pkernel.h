@@ -731,7 +731,7 @@ __global__ __launch_bounds__(256, (FUSE_C3 && !PREC) ? 3 : 2) void conv3x3_mfma_
                         for (int nt = 0; nt < NT; ++nt) {
                             // MaxPool2d(act(.)) == act(MaxPool2d(.)) bit for bit (ReLU / LeakyReLU are non-decreasing): one
                             // activation per window instead of four (VALU work shares the pipe with the exact-fp32 MFMAs)
-                            const float m = fmaxf(fmaxf(acc[mt][nt][4 * q], acc[mt][nt][4 * q + 1]), fmaxf(acc[mt][nt][4 * q + 2], acc[mt][nt][4 * q + 3]));
+                            const float m = vad_vmax4(acc[mt][nt][4 * q], acc[mt][nt][4 * q + 1], acc[mt][nt][4 * q + 2], acc[mt][nt][4 * q + 3]);
                             vad_bstore1(vad_act(m, ACT), ro, ok ? eoff[nt] : VAD_OOB, so);
                         }
                     }

@@ -315,16 +315,14 @@ __global__ __launch_bounds__(256 * MTW) void convlstm_gate_kernel(Conv3P p) {
         float* zo = p.out + (size_t)n * p.out_fs;
         if (POOL) {       // the lane's four registers are one 2x2 window (H, W even: host-checked); activation is monotonic: act(max) == max(act)
             const int y = y0, x = x0 + 8 * wm + 2 * kq;
-            const float m = vad_act(fmaxf(fmaxf(acc[0], acc[1]), fmaxf(acc[2], acc[3])), ACT);
+            const float m = vad_act(vad_vmax4(acc[0], acc[1], acc[2], acc[3]), ACT);
             if (y < H && x < W) zo[((size_t)(y >> 1) * (W >> 1) + (x >> 1)) * p.cout + g * hid + hc] = m;
         } else {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int y = y0 + (r >> 1), x = x0 + 8 * wm + 2 * kq + (r & 1);
-                // plain fmaxf, not vad_act's inline-asm v_max: hipcc's hazard recogniser puts no wait states between an MFMA and an
-                // asm statement that reads its result (same values: maxNum of two non-NaN floats)
-                const float v = acc[r];
-                const float a_ = ACT == VAD_ACT_LEAKY ? fmaxf(v, 0.2f * v) : (ACT == VAD_ACT_RELU ? fmaxf(v, 0.f) : v);
+                // (vad_act is a compiler builtin, no asm statement: hipcc's hazard recogniser pads the MFMA -> VALU read itself)
+                const float a_ = vad_act(acc[r], ACT);
                 if (y < H && x < W) zo[((size_t)y * W + x) * p.cout + g * hid + hc] = a_;
             }
         }

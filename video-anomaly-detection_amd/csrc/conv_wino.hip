@@ -284,7 +284,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_pkernel(ConvWP p) {
 #pragma unroll
                     for (int kk = 0; kk < 4; ++kk) {
                         const bool ok = full_tile || (ey0 < oh && (ex0 + kk) < ow);
-                        const float m = fmaxf(fmaxf(yy[nt][0][0][kk], yy[nt][0][1][kk]), fmaxf(yy[nt][1][0][kk], yy[nt][1][1][kk]));
+                        const float m = vad_vmax4(yy[nt][0][0][kk], yy[nt][0][1][kk], yy[nt][1][0][kk], yy[nt][1][1][kk]);
                         vad_bstore1(vad_act(m + bv[nt], ACT), ro, ok ? eoff : VAD_OOB, kk * ecol + nt * 128u);
                     }
                 } else {

@@ -352,16 +352,16 @@ __global__ __launch_bounds__(256, 2) void dec4_score_kernel(Dec4P p) {
                 else if (iy == r1) load_row(fr, have_next, nn, nstrip, nr0 - 1);   // band end: the next item's first row
                 store_partial(prev, o.ws);
                 __builtin_amdgcn_sched_barrier(0);
-                // ReLU as an INTEGER max with 0 (negative floats are negative integers): one instruction, where fmaxf costs a
-                // canonicalising v_max as well - and, unlike an inline-asm v_max_f32, one whose MFMA hazards hipcc handles
+                // ReLU as the NaN-propagating maximum with 0 (vad_vmax: one v_maximum3_f32, no canonicalising v_max, and a builtin
+                // whose MFMA hazards hipcc handles).  An integer max with 0 is one instruction too, but it erases every NaN
+                // whose sign bit is set - the default NaN of an x86 host among them.
                 // All 32 first, then the 32 MFMAs back to back: interleaved, every MFMA waits two states for the VALU result it reads.
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
 #pragma unroll
                     for (int b = 0; b < 2; ++b) {
-                        const float t = acc1[b][r];                      // (not __builtin_bit_cast on the element: hipcc then reads element 0)
-                        const int bits = __float_as_int(t);
-                        acc1[b][r] = __int_as_float(bits > 0 ? bits : 0);
+                        const float t = acc1[b][r];                      // (read the element into a scalar first, as the integer form had to)
+                        acc1[b][r] = vad_vmax(t, 0.f);
                     }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll

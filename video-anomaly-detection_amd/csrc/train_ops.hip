@@ -170,7 +170,7 @@ __global__ __launch_bounds__(256) void bn_act_pool_fwd_kernel(BnFwdP p) {
             const f32x4 v2 = bn_apply(io::ld(&src[o + (size_t)p.w * p.c]), mean, invstd, gamma, beta, ACT);
             const f32x4 v3 = bn_apply(io::ld(&src[o + (size_t)p.w * p.c + p.c]), mean, invstd, gamma, beta, ACT);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = fmaxf(fmaxf(v[e], v1[e]), fmaxf(v2[e], v3[e]));
+            for (int e = 0; e < 4; ++e) v[e] = vad_vmax4(v[e], v1[e], v2[e], v3[e]);
         } else {
             v = bn_apply(io::ld(&src[((size_t)y * p.w + x) * p.c]), mean, invstd, gamma, beta, ACT);
         }
@@ -220,7 +220,7 @@ __global__ __launch_bounds__(256) void bn_act_pool_fwd8_kernel(BnFwdP p) {
                 const f32x4 v2 = bn_apply(w2[hf], mean[hf], invstd[hf], gamma[hf], beta[hf], ACT);
                 const f32x4 v3 = bn_apply(w3[hf], mean[hf], invstd[hf], gamma[hf], beta[hf], ACT);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[hf][e] = fmaxf(fmaxf(v[hf][e], v1[e]), fmaxf(v2[e], v3[e]));
+                for (int e = 0; e < 4; ++e) v[hf][e] = vad_vmax4(v[hf][e], v1[e], v2[e], v3[e]);
             }
         } else {
             f32x4 w0[2];

@@ -71,12 +71,14 @@ __device__ __forceinline__ unsigned vad_xcd_remap(unsigned b, unsigned nb) {
 
 // LeakyReLU(0.2) as max(v, 0.2 v): the same value as the select for every input (0.2 v < v exactly when v > 0), in two
 // VALU instructions instead of v_mul + v_cmp + v_cndmask plus the VCC wait states - these epilogues run on the pipe the
-// exact-fp32 MFMAs use.  One plain v_max_f32 each (fmaxf adds a canonicalising v_max(v, v) per operand under IEEE mode).
-__device__ __forceinline__ float vad_vmax(float a, float b) {
-    float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
+// exact-fp32 MFMAs use.
+// Every maximum of an activation or a pooling window is the IEEE-754-2019 `maximum`: NaN if either operand is NaN (either sign
+// bit), -0 < +0, what torch's relu / LeakyReLU / MaxPool2d give.  v_max_f32 / fmaxf are `maxNum`, which returns the non-NaN
+// operand: ReLU(NaN) = 0, and a pooling window kept its NaN only when every element was one ("Non-finite values").
+// The builtin lowers to v_maximum3_f32 - a max with 0 behind a pair folds into one instruction, no canonicalising v_max(v, v) -
+// and, being no asm statement, gets its MFMA wait states from hipcc.  Same bits as maxNum for operands that are not NaN.
+__device__ __forceinline__ float vad_vmax(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+__device__ __forceinline__ float vad_vmax4(float a, float b, float c, float d) { return vad_vmax(vad_vmax(a, b), vad_vmax(c, d)); }
 __device__ __forceinline__ float vad_act(float v, int act) {
     if (act == VAD_ACT_LEAKY) return vad_vmax(v, 0.2f * v);
     if (act == VAD_ACT_RELU) return vad_vmax(v, 0.f);
