@@ -809,6 +809,30 @@ int vad_label_regions(const void* masks, int label_format, long long n, int h, i
 int vad_pro_accumulate(const float* values, const void* masks, int label_format, long long n, int h, int w, int connectivity,
                        void* state, int m, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ Smoothed anomaly maps (csrc/map_smooth.hip)
+ * The two steps an MVTec-style evaluation takes between the error map and the ranking metrics: the map is smoothed with a Gaussian
+ * (scipy.ndimage.gaussian_filter, conventionally sigma = 4) and the image is scored by the maximum of the smoothed map.
+ *
+ * vad_smooth_maps: maps = n frames of h x w fp32, contiguous (any h, w >= 1 with h * w <= VAD_MAX_FRAME_PIXELS; 4-byte aligned).
+ * taps_dev: device fp32 [2 * radius + 1], made on the host (scipy's: w[k] = exp(-0.5 / sigma^2 * (k - radius)^2) in float64,
+ * divided by their float64 sum, rounded once to fp32; every tap must be > 0).  Borders: scipy's mode="reflect" (index -k -> k - 1,
+ * index n - 1 + k -> n - k), one reflection, so radius <= min(h, w).  First along h, then along w; each pass is
+ * acc = fl(w[0] x[0]), acc = fl(acc + fl(w[k] x[k])) for k = 1 .. 2 radius ascending, every product and sum rounded to fp32 on its
+ * own (no fused multiply-add), the intermediate fp32: numpy float32 restates it bit for bit.  A NaN makes exactly the pixels whose
+ * reflected window holds it NaN; +Inf spreads as +Inf.
+ * out (may be NULL): n x h x w smoothed maps; it must not overlap maps.  frame_max (may be NULL; not both): [n], the maximum of
+ * each smoothed frame with torch.amax semantics (NaN if any pixel of the frame is) - compare-only, the same for every batching,
+ * launch order and tiling.  ws: vad_smooth_workspace_bytes(n, h, w, radius) bytes (0 for arguments out of range), needed only with
+ * frame_max (VAD_ERR_WS when smaller).  VAD_ERR_ARG for radius outside 1 .. VAD_SMOOTH_MAX_RADIUS or above min(h, w), n < 0, both
+ * outputs NULL, out overlapping maps, a misaligned pointer.  n == 0 returns VAD_OK and launches nothing.  One launch (two with
+ * frame_max) on `stream`, no allocation, no host synchronisation: capturable in a graph.
+ * vad_smooth_tile reports the output tile of one work-group (rows, columns) - what a test needs to build a frame of several tiles. */
+#define VAD_SMOOTH_MAX_RADIUS 32
+size_t vad_smooth_workspace_bytes(long long n, int h, int w, int radius);
+int vad_smooth_maps(const float* maps, long long n, int h, int w, const float* taps_dev, int radius, float* out, float* frame_max,
+                    void* ws, size_t ws_bytes, void* stream);
+int vad_smooth_tile(int* tile_h, int* tile_w);
+
 /* ------------------------------------------------------------------ hipGraph capture / replay of a scoring call
  * vad_graph_begin(stream); <one vad_img_score* / vad_vid_score* call on `stream`>; vad_graph_end(stream, &exec) captures
  * the call's launch sequence (kernels, and the fork / join with the library's helper streams) into an instantiated

@@ -17,10 +17,13 @@ infinities are not binned; they are counted per class in `rejected`.
 
 The second half of the file is the per-region overlap (AUPRO): `label_regions`, `ProHistogram` (csrc/region_overlap.hip) and
 `aupro_from_counts` / `pro_curve_from_counts`, built on the same quantiser.
+
+The third part is what goes in front of both: `gaussian_taps` / `smooth_maps` (csrc/map_smooth.hip) smooth the anomaly maps with
+scipy's Gaussian on the device and give the per-frame maximum of the smoothed map, the image score of the MVTec evaluation.
 """
 from __future__ import annotations
 
-from typing import Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
@@ -705,3 +708,104 @@ class ProHistogram:
     def auroc(self) -> Tuple[float, float]:
         _, pos, neg, _ = self._host()
         return auroc_from_counts(np.stack([neg, pos]))
+
+
+# ====================================================================== smoothed anomaly maps
+# The two steps an MVTec-style evaluation takes before it ranks pixels and images: the map is smoothed with
+# a Gaussian - `scipy.ndimage.gaussian_filter(map, sigma=4)`; a raw squared-error map is speckle, and isolated hot pixels on normal
+# texture use up the false-positive budget AUPRO integrates over - and the image is scored by the maximum of the smoothed map.
+SMOOTH_MAX_RADIUS = hip.SMOOTH_MAX_RADIUS
+_TAPS = {}                     # (sigma, truncate, device) -> device taps: uploaded once, never written again
+
+
+def _gaussian_taps64(sigma: float, r: int) -> np.ndarray:
+    """scipy's `_gaussian_kernel1d(sigma, 0, r)`: float64 [2r + 1], normalised."""
+    x = np.arange(-r, r + 1, dtype=np.float64)
+    w = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    return w / w.sum()
+
+
+def gaussian_taps(sigma: float, truncate: float = 4.0) -> Tuple[int, np.ndarray]:
+    """(r, float32 [2r + 1]): the taps of `scipy.ndimage.gaussian_filter(sigma=sigma, truncate=truncate)` - r = int(truncate * sigma
+    + 0.5), w[k] = exp(-0.5 / sigma^2 * (k - r)^2) in float64, divided by their float64 sum, rounded once to float32.  Host only.
+    VadError for a sigma / truncate that is not a positive finite number, for a radius outside 1..32, and for taps that underflow
+    float32 (every tap must be > 0: a zero tap would turn an infinite pixel into NaN)."""
+    for name, v in (("sigma", sigma), ("truncate", truncate)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or v <= 0:
+            raise hip.VadError(f"gaussian_taps: {name} must be a positive finite number, got {v!r}")
+    sigma, truncate = float(sigma), float(truncate)
+    r = int(truncate * sigma + 0.5)
+    if not 1 <= r <= SMOOTH_MAX_RADIUS:
+        raise hip.VadError(f"gaussian_taps: radius int(truncate * sigma + 0.5) = {r} (sigma {sigma}, truncate {truncate}) must be in "
+                           f"1..{SMOOTH_MAX_RADIUS}")
+    w = _gaussian_taps64(sigma, r).astype(np.float32)
+    if not (w > 0).all():
+        raise hip.VadError(f"gaussian_taps: the outer taps of sigma {sigma}, truncate {truncate} underflow float32; use a smaller truncate")
+    return r, w
+
+
+def _device_taps(sigma: float, truncate: float, device, host_taps: np.ndarray) -> torch.Tensor:
+    """The taps of (sigma, truncate) on `device`: uploaded on first use, then read only."""
+    key = (float(sigma), float(truncate), str(device))
+    with hip._lock:
+        hit = _TAPS.get(key)
+    if hit is None:
+        hit = torch.from_numpy(host_taps).to(device)
+        with hip._lock:
+            hit = _TAPS.setdefault(key, hit)
+    return hit
+
+
+def smooth_maps(maps: torch.Tensor, sigma: float = 4.0, truncate: float = 4.0, out: Optional[torch.Tensor] = None, return_max=False):
+    """`scipy.ndimage.gaussian_filter(frame, sigma, truncate=truncate)` (mode="reflect") of every H x W frame of `maps` on the GPU
+    (`vad_smooth_maps`, csrc/map_smooth.hip).  `maps`: float32 GPU tensor, contiguous, the last two dimensions H, W and any leading
+    ones - `[B,1,H,W]` error / SSIM maps, the `[B,T,1,H,W]` maps of the video model's `score_all`, `[N,H,W]`; frames are smoothed one
+    by one, never across time.  The arithmetic is float32 and fully specified (first along H, then along W, ascending taps, every
+    product and sum rounded on its own): tests/map_smooth_ref.py restates it bit for bit; it is within 2 (2r + 3) 2^-24 G(|x|) of
+    scipy's float64 result.  The radius r = int(truncate * sigma + 0.5) must be in 1..32 and <= min(H, W) (one reflection).
+    Returns the smoothed tensor (written to `out` if given: same shape, float32, contiguous, not overlapping `maps`); with
+    `return_max=True` also the per-frame maxima of the smoothed maps in the leading shape (`torch.amax` semantics: NaN if any
+    pixel of the frame is NaN) - the image score of the MVTec evaluation; with `return_max="only"` just the maxima, and no map is
+    written.  Taps are uploaded once per (sigma, truncate, device).  Asynchronous on the current stream."""
+    what = "smooth_maps"
+    if not isinstance(maps, torch.Tensor):
+        raise hip.VadError(f"{what}: maps must be a torch tensor")
+    if not isinstance(return_max, bool) and return_max != "only":
+        raise hip.VadError(f"{what}: return_max must be False, True or 'only', got {return_max!r}")
+    r, host_taps = gaussian_taps(sigma, truncate)                 # refuses a bad sigma / truncate before anything else
+    if not maps.is_cuda:
+        raise hip.VadError(f"{what}: maps ({maps.device}) must be on the GPU (the smoothing runs on the device; there is no CPU fallback)")
+    if maps.dtype != torch.float32:
+        raise hip.VadError(f"{what}: maps must be float32, got {maps.dtype}")
+    if maps.dim() < 2:
+        raise hip.VadError(f"{what}: maps must have at least the two dimensions H, W, got {tuple(maps.shape)}")
+    if not maps.is_contiguous():
+        raise hip.VadError(f"{what}: maps must be contiguous (got strides {tuple(maps.stride())} for {tuple(maps.shape)}); it is not copied silently")
+    lead, h, w = tuple(maps.shape[:-2]), int(maps.shape[-2]), int(maps.shape[-1])
+    if h < 1 or w < 1 or h * w > hip.MAX_FRAME_PIXELS:
+        raise hip.VadError(f"{what}: frames of {h} x {w} are out of range (H, W >= 1 and H * W <= {hip.MAX_FRAME_PIXELS})")
+    if r > min(h, w):
+        raise hip.VadError(f"{what}: radius {r} (sigma {sigma}, truncate {truncate}) exceeds min(H, W) of {h} x {w} frames: only one "
+                           "reflection at the border is supported")
+    only = return_max == "only"
+    if only and out is not None:
+        raise hip.VadError(f"{what}: return_max='only' writes no map; out must be None")
+    if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(maps.shape) or out.dtype != torch.float32
+                            or out.device != maps.device or not out.is_contiguous()):
+        raise hip.VadError(f"{what}: out must be a contiguous float32 tensor {tuple(maps.shape)} on {maps.device}")
+    n = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    with torch.cuda.device(maps.device):
+        if out is None and not only:
+            out = torch.empty_like(maps)
+        fmax = torch.empty(lead, dtype=torch.float32, device=maps.device) if return_max else None
+        if n > 0:
+            l = hip.lib()
+            taps = _device_taps(sigma, truncate, maps.device, host_taps)
+            need = l.vad_smooth_workspace_bytes(n, h, w, r) if return_max else 0
+            ws = torch.empty(need, dtype=torch.uint8, device=maps.device) if need else None
+            hip.check(l.vad_smooth_maps(maps.data_ptr(), n, h, w, taps.data_ptr(), r, hip.ptr(out), hip.ptr(fmax), hip.ptr(ws), need,
+                                        hip.current_stream()), "vad_smooth_maps")
+            hip.calls["smooth_maps"] = hip.calls.get("smooth_maps", 0) + 1
+    if only:
+        return fmax
+    return (out, fmax) if return_max else out

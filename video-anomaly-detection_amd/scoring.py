@@ -63,6 +63,34 @@ def compute_auroc(model, test_loader: Iterable[dict], device):
     return auroc, labels, scores, per_defect
 
 
+def compute_auroc_smoothed(model, test_loader: Iterable[dict], device, sigma: float = 4.0, truncate: float = 4.0, map: str = "mse"):
+    """`compute_auroc` with the image score of the published MVTec evaluations: the maximum of the Gaussian-smoothed anomaly map
+    (`metrics.smooth_maps(..., return_max="only")`) instead of the mean squared error - a small defect on a large frame barely
+    moves the mean.  Same batches, same 4-tuple; `map` as in `pixel_auroc`.  The maps stay on the device: a batch's scores are read
+    back once, as `compute_auroc` does."""
+    from . import metrics
+    if map not in ("mse", "ssim"):
+        raise hip.VadError(f"compute_auroc_smoothed: map must be 'mse' or 'ssim', got {map!r}")
+    all_labels, all_scores, all_types = [], [], []
+    with torch.no_grad():
+        for batch in test_loader:
+            images = batch["image"].to(device)
+            values = _anomaly_maps(model, images, map, None, truncate)
+            scores = metrics.smooth_maps(values, sigma, truncate, return_max="only").reshape(images.shape[0])
+            all_scores.extend(scores.cpu().numpy())
+            all_labels.extend(np.asarray(batch["label"]))
+            all_types.extend(batch["defect_type"])
+    labels = np.array(all_labels)
+    scores = np.array(all_scores)
+    auroc = roc_auc(labels, scores)
+    per_defect = {}
+    for name in set(all_types):
+        m = np.array([d == name for d in all_types])
+        per_defect[name] = {"count": int(m.sum()), "mean_score": scores[m].mean(),
+                            "is_anomaly": labels[m][0] if m.any() else 0}
+    return auroc, labels, scores, per_defect
+
+
 def score_clips(model, loader: Iterable[dict], device, per_frame: bool = False):
     """Clip loop of the reference's evaluate_video.evaluate (evaluate_video.py:137-154): returns
     (clip scores float32[N], labels) and, when per_frame, also float32[N,T] frame scores computed in
@@ -343,7 +371,19 @@ def score_stream(model, seed: int, n_frames: int, chunk: int = 512, h: int = 256
 
 
 # ------------------------------------------------------------------------------ ranking metrics on the device
-def pixel_auroc(model, loader: Iterable[dict], device, map: str = "mse", mantissa_bits: int = 11, hist=None):
+def _anomaly_maps(model, images, map: str, sigma, truncate):
+    """The batch's anomaly map [B,1,H,W] of the pixel metrics: the error map or the SSIM map, through `metrics.smooth_maps` when a
+    sigma is given."""
+    from . import metrics
+    if map == "mse":
+        values = model.score_all(images)["errmap"]
+    else:
+        values = model.score_criteria(images, ssim_map=True)["ssim_map"]
+    return values if sigma is None else metrics.smooth_maps(values, sigma, truncate)
+
+
+def pixel_auroc(model, loader: Iterable[dict], device, map: str = "mse", mantissa_bits: int = 11, hist=None, sigma=None,
+                truncate: float = 4.0):
     """Pixel-level AUROC of an image model's anomaly map against the ground-truth masks - the localisation metric of MVTec-style
     datasets; the reference loads `sample['mask']` and only plots it beside the map (evaluate.py:142-171).  Batches are
     {'image', 'mask', ...} as `MVTecDataset` yields them (utils/dataset.py:150-156): mask float `[B,1,H,W]` (ToTensor: a pixel is
@@ -352,6 +392,8 @@ def pixel_auroc(model, loader: Iterable[dict], device, map: str = "mse", mantiss
     already holds 1 - SSIM per pixel (channel mean, `losses.ssim_per_frame`), so it is scored as it stands: higher = more
     anomalous, like the error map.  It can be slightly negative where SSIM exceeds 1 by rounding; such pixels are counted in
     `hist.rejected()`, not binned.
+    `sigma` (None = the raw map, as before): smooth every map with `metrics.smooth_maps(sigma, truncate)` first - scipy's
+    `gaussian_filter`, sigma = 4 in the published MVTec evaluations - still on the device.
     Each batch is ONE scoring call and ONE `accumulate`; no map is copied to the host - the only host read is the counters, once,
     at the end.  Returns (auroc, tie_bound, hist) (`metrics.auroc_from_counts`); pass `hist` to continue an earlier evaluation or
     to all-reduce before reading (`hist.all_reduce()`), in which case its own mantissa_bits applies."""
@@ -364,21 +406,18 @@ def pixel_auroc(model, loader: Iterable[dict], device, map: str = "mse", mantiss
         for batch in loader:
             images = batch["image"].to(device)
             masks = torch.as_tensor(batch["mask"]).to(device)
-            if map == "mse":
-                values = model.score_all(images)["errmap"]
-            else:
-                values = model.score_criteria(images, ssim_map=True)["ssim_map"]
-            hist.accumulate(values, masks)
+            hist.accumulate(_anomaly_maps(model, images, map, sigma, truncate), masks)
     auroc, tie_bound = hist.auroc()
     return auroc, tie_bound, hist
 
 
 def pixel_aupro(model, loader: Iterable[dict], device, map: str = "mse", fpr_limit: float = 0.3, mantissa_bits: int = 11, hist=None,
-                connectivity: int = 8):
+                connectivity: int = 8, sigma=None, truncate: float = 4.0):
     """Per-region overlap (AUPRO) of an image model's anomaly map against the ground-truth masks: every connected anomalous region
     of the masks weighs the same, and the curve is integrated up to a false-positive rate of `fpr_limit` - the localisation metric
     of the MVTec evaluation, where pixel AUROC is dominated by the large defects.  The loop of `pixel_auroc` (same batches, same
-    `map`): each batch is ONE scoring call and ONE `ProHistogram.accumulate`, which labels the masks' regions and adds the counters
+    `map`, same `sigma` / `truncate` - AUPRO is the metric speckle hurts most, its curve ends at FPR 0.3): each batch is ONE scoring
+    call and ONE `ProHistogram.accumulate`, which labels the masks' regions and adds the counters
     on the device; the only host read is the counters, once, at the end.  Returns (aupro, quant_bound, weight_bound, hist)
     (`metrics.aupro_from_counts`); pass `hist` to continue an earlier evaluation or to all-reduce before reading, in which case
     its own mantissa_bits and connectivity apply.  `hist.auroc()` is the pixel AUROC of the same evaluation."""
@@ -391,11 +430,7 @@ def pixel_aupro(model, loader: Iterable[dict], device, map: str = "mse", fpr_lim
         for batch in loader:
             images = batch["image"].to(device)
             masks = torch.as_tensor(batch["mask"]).to(device)
-            if map == "mse":
-                values = model.score_all(images)["errmap"]
-            else:
-                values = model.score_criteria(images, ssim_map=True)["ssim_map"]
-            hist.accumulate(values, masks)
+            hist.accumulate(_anomaly_maps(model, images, map, sigma, truncate), masks)
     aupro, quant_bound, weight_bound = hist.aupro(fpr_limit)
     return aupro, quant_bound, weight_bound, hist
 
