@@ -43,7 +43,11 @@ extern "C" {
  *   VAD_PREC_SPLIT split fp16: every fp32 operand v is used as hi = fp16(v), lo = fp16((v-hi)*2^11) and a*b is evaluated
  *      as ah*bh + (ah*bl + al*bh)*2^-11 with three v_mfma_f32_32x32x16_f16 and fp32 accumulation.  fp16 products are
  *      exact in fp32, so each product carries 22 significant bits (fp32 has 24); activations and outputs in HBM stay
- *      fp32.  Needs |activation| < 65504.  Opt-in; gated by the same golden-vector and trained-model tests. */
+ *      fp32.  Needs |activation| < 65504.  Opt-in; gated by the same golden-vector and trained-model tests.
+ *      Finite range: full accuracy for operand magnitudes in [2^-12, 65520); a finite operand of
+ *      65520 or more becomes (Inf, NaN) and every output that reads it NaN - the host packers refuse such a folded weight
+ *      with VAD_ERR_ARG, the device-side vad_train_pack_* cannot and write the Inf halves; below 2^-14 an operand is held to
+ *      2^-36 absolute (fp16 subnormals are kept), below 2^-36 it is zero. */
 #define VAD_PREC_FP32 0
 #define VAD_PREC_SPLIT 1
 /*   VAD_PREC_BF16  bf16 operands (round to nearest even), one v_mfma_f32_32x32x16_bf16 per 16 channels, fp32 accumulate -
@@ -73,7 +77,12 @@ const char* vad_last_error(void);   /* per thread */
 /* ------------------------------------------------------------------ weight packing (host, CPU)
  * Folds eval-mode BatchNorm2d (eps 1e-5; y = (x-mean)/sqrt(var+eps)*gamma+beta) into the preceding
  * conv in fp64, rounds once to fp32 and re-orders for the kernels' MFMA B-operand loads.
- * bn == NULL means "no BatchNorm after this conv"; bn = {gamma, beta, running_mean, running_var}. */
+ * bn == NULL means "no BatchNorm after this conv"; bn = {gamma, beta, running_mean, running_var}.
+ * With VAD_PREC_SPLIT, vad_pack_conv3x3 / vad_pack_convt2x2 and the model packers built on them (vad_img_pack, vad_vid_pack*,
+ * vad_convlstm_pack; these also check the first layer) return VAD_ERR_ARG for a finite FOLDED weight of magnitude >= 65520 - it
+ * would be packed as (Inf, NaN) halves; the message names the layer, the element and the value.  A weight that is already
+ * NaN / Inf is packed and propagates.  vad_pack_conv3x3_c3 takes no precision (its blob carries both forms) and checks nothing;
+ * vad_pack_conv1x1 has no split form.  VAD_PREC_FP32 and VAD_PREC_WINO blobs take every finite value. */
 
 /* Conv2d k3 p1 weight OIHW (Cout,Cin,3,3) -> [9][ceil(Cin/8)][Cout][8]; bias_out[Cout].
  * Replaces nn.Conv2d+nn.BatchNorm2d pairs of models/autoencoder.py:38-79,103-139 and
@@ -305,7 +314,9 @@ int vad_adam_step(float* p, const float* g, float* m, float* v, long long n, flo
  * `precision` like the host packers; VAD_PREC_WINO: both operands in Winograd form, vad_pack_conv3x3_wino_floats of room each):
  * fwd = the forward kernels' order (vad_pack_conv3x3 / vad_pack_convt2x2 / vad_pack_conv3x3_c3 layouts);
  * dgrad = the data-gradient operand: for conv3x3 a conv3x3 weight with cin/cout swapped and taps rotated (run it
- * through vad_conv3x3), for convT a 1x1 weight with K = 4*cout (run vad_conv1x1 on the space-to-depth gradient). */
+ * through vad_conv3x3), for convT a 1x1 weight with K = 4*cout (run vad_conv1x1 on the space-to-depth gradient).
+ * They never see the values on the host and cannot return an error that depends on them: with VAD_PREC_SPLIT a weight of
+ * magnitude >= 65520 is written as (Inf, NaN) halves and every output that reads it is NaN (the host packers refuse it). */
 int vad_train_pack_conv3x3(const float* w_oihw, int cout, int cin, float* fwd, float* dgrad, int precision, void* stream);
 int vad_train_pack_convt2x2(const float* w_iohw, int cin, int cout, float* fwd, float* dgrad, int precision, void* stream);
 int vad_train_pack_conv3x3_c3(const float* w_oihw, int cout, float* fwd, void* stream);

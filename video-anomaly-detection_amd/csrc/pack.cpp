@@ -48,21 +48,31 @@ static int base_prec(int precision) { return precision == VAD_PREC_WINO ? VAD_PR
 
 extern "C" size_t vad_pack_conv3x3_floats(int cout, int cin) { return (size_t)9 * ((cin + 7) / 8) * cout * 8; }
 
+// What a split-fp16 blob cannot hold: hi = fp16(v) is Inf for a FINITE |v| >= 65520 (halfway between fp16's largest value
+// 65504 and 2^16), lo = Inf - Inf, and every product with it is NaN where the exact path gives an ordinary number.  The
+// packers refuse such a folded weight instead of writing Inf halves.  A weight that is already NaN / Inf is packed as it is
+// and propagates ("Non-finite values").  Values that vanish at the other end (|v| < 2^-36: both halves zero) are
+// packed: that loss is bounded and documented ("Finite dynamic range of the arithmetic modes").
+static bool split_holds(float v) { return !(std::isfinite(v) && std::fabs(v) >= 65520.0f); }
+#define REQ_SPLIT_HOLDS(who, v, fmt, ...) REQ(split_holds(v), who ": split precision cannot hold folded weight " fmt " = %.9g (|w| >= 65520 rounds to Inf in fp16; pack this model as VAD_PREC_FP32 or VAD_PREC_WINO)", __VA_ARGS__, (double)(v))
+
 // Split-fp16 operand form of the same weights (same byte count): [tap][cin/16][cout][half h][8 x hi | 8 x lo] fp16,
 // element j of half h = input channel 16*c16 + 8*h + j; hi = fp16(w), lo = fp16((w - hi) * 2^11).
-static void pack_conv3x3_split(const float* w, const std::vector<double>& s, int cout, int cin, float* out) {
+static int pack_conv3x3_split(const float* w, const std::vector<double>& s, int cout, int cin, float* out) {
     _Float16* o = (_Float16*)out;
     const int c16n = cin / 16;
     for (int co = 0; co < cout; ++co)
         for (int ci = 0; ci < cin; ++ci)
             for (int tap = 0; tap < 9; ++tap) {
                 const float v = (float)((double)w[((size_t)co * cin + ci) * 9 + tap] * s[co]);
+                REQ_SPLIT_HOLDS("pack_conv3x3", v, "[cout %d][cin %d][tap %d]", co, ci, tap);
                 const _Float16 hi = (_Float16)v;
                 const _Float16 lo = (_Float16)((v - (float)hi) * 2048.0f);
                 const size_t base = ((((size_t)tap * c16n + ci / 16) * cout + co) * 2 + ((ci >> 3) & 1)) * 16;
                 o[base + (ci & 7)] = hi;
                 o[base + 8 + (ci & 7)] = lo;
             }
+    return VAD_OK;
 }
 
 extern "C" int vad_pack_conv3x3(const float* w, const float* bias, const float* const* bn,
@@ -76,8 +86,7 @@ extern "C" int vad_pack_conv3x3(const float* w, const float* bias, const float* 
     const int c8n = (cin + 7) / 8;
     memset(out, 0, vad_pack_conv3x3_floats(cout, cin) * sizeof(float));
     if (precision == VAD_PREC_SPLIT) {
-        pack_conv3x3_split(w, s, cout, cin, out);
-        return VAD_OK;
+        return pack_conv3x3_split(w, s, cout, cin, out);
     }
     for (int co = 0; co < cout; ++co)
         for (int ci = 0; ci < cin; ++ci)
@@ -117,11 +126,18 @@ extern "C" int vad_pack_conv3x3_wino(const float* w, const float* bias, const fl
 // [2 k-steps][cout][half h][8 x hi | 8 x lo] fp16 (K padded to 32), 32*cout halves*2 = 32*cout floats.
 extern "C" size_t vad_pack_conv3x3_c3_floats(int cout) { return (size_t)(28 + 32) * cout; }
 
-extern "C" int vad_pack_conv3x3_c3(const float* w, const float* bias, const float* const* bn,
-                                   int cout, float* out, float* bias_out) {
+// (the entry point takes no precision - one blob carries both forms - so only the model packers, which know the mode the
+// blob is for, can refuse a first layer whose split halves would be Inf: `split_checked`)
+static int pack_conv3x3_c3(const float* w, const float* bias, const float* const* bn, int cout, bool split_checked, float* out, float* bias_out) {
     REQ(w && out && bias_out && cout > 0, "pack_conv3x3_c3: bad arguments");
     std::vector<double> s;
     bn_scale_shift(bias, bn, cout, s, bias_out);
+    if (split_checked)
+        for (int co = 0; co < cout; ++co)
+            for (int k = 0; k < 27; ++k) {
+                const float v = (float)((double)w[(size_t)co * 27 + k] * s[co]);
+                REQ_SPLIT_HOLDS("pack_conv3x3_c3", v, "[cout %d][cin %d][tap %d]", co, k / 9, k % 9);
+            }
     for (int k = 0; k < 28; ++k)
         for (int co = 0; co < cout; ++co)
             out[(size_t)k * cout + co] = k < 27 ? (float)((double)w[(size_t)co * 27 + k] * s[co]) : 0.f;
@@ -135,6 +151,11 @@ extern "C" int vad_pack_conv3x3_c3(const float* w, const float* bias, const floa
             o[base + 8 + (k & 7)] = lo;
         }
     return VAD_OK;
+}
+
+extern "C" int vad_pack_conv3x3_c3(const float* w, const float* bias, const float* const* bn,
+                                   int cout, float* out, float* bias_out) {
+    return pack_conv3x3_c3(w, bias, bn, cout, false, out, bias_out);
 }
 
 extern "C" size_t vad_pack_convt2x2_floats(int cin, int cout) { return (size_t)4 * (cin / 8) * cout * 8; }
@@ -153,6 +174,7 @@ extern "C" int vad_pack_convt2x2(const float* w, const float* bias, const float*
             for (int co = 0; co < cout; ++co)
                 for (int q = 0; q < 4; ++q) {
                     const float v = (float)((double)w[((size_t)ci * cout + co) * 4 + q] * s[co]);
+                    REQ_SPLIT_HOLDS("pack_convt2x2", v, "[cin %d][cout %d][tap %d]", ci, co, q);
                     const _Float16 hi = (_Float16)v, lo = (_Float16)((v - (float)hi) * 2048.0f);
                     const size_t base = ((((size_t)q * (cin / 16) + ci / 16) * cout + co) * 2 + ((ci >> 3) & 1)) * 16;
                     o[base + (ci & 7)] = hi;
@@ -264,6 +286,13 @@ static int pack_convt2x2_slot(const float* w, const float* b, const float* const
 // --------------------------------------------------------------------------- image autoencoder
 static size_t align4(size_t x) { return (x + 3) & ~(size_t)3; }
 
+// A layer packer refused (rc, message in g_err): the same code with the model packer and the state-dict name of the layer in front.
+static int layer_refused(int rc, const char* who, const char* layer) {
+    char inner[sizeof g_err];
+    snprintf(inner, sizeof inner, "%s", g_err);
+    return vad_fail(rc, "%s: layer %s: %s", who, layer, inner);
+}
+
 // Every model blob starts with a 4-word header {magic, tag, dim0, dim1} (uint32 bit patterns in the float array): the tag
 // names the model kind and the arithmetic mode the operands were packed for.  The score entry points take the mode as an
 // argument; the kernel that finalises the scores compares it with the tag ON THE DEVICE and writes NaN scores on a
@@ -331,8 +360,8 @@ extern "C" int vad_img_pack(const float* const* P, int nparams, int in_ch, int l
     const ImgLayout L = img_layout(in_ch, latent);
     memset(out, 0, L.total * sizeof(float));
     put_header(out, VAD_BLOB_IMG, precision, latent, in_ch);
-    int pi = 0, rc = VAD_OK;
-    for (int li = 0; li < L.nlayers && rc == VAD_OK; ++li) {
+    int pi = 0, rc = VAD_OK, li = 0;
+    for (; li < L.nlayers && rc == VAD_OK; ++li) {
         const LayerSlot& s = L.layer[li];
         const float* w = P[pi], *b = P[pi + 1];
         if (s.kind == LK_TAIL_CONV) {
@@ -355,7 +384,7 @@ extern "C" int vad_img_pack(const float* const* P, int nparams, int in_ch, int l
         // real widths of this layer: only enc4.0 (cout), enc4.3 (both) and dec1.0 (cin) carry latent_dim
         const int cin = s.cin == L.latent_p && (li == 7 || li == 8) ? latent : s.cin;
         const int cout = s.cout == L.latent_p && (li == 6 || li == 7) ? latent : s.cout;
-        if (s.kind == LK_CONV_C3) rc = vad_pack_conv3x3_c3(w, b, bn, s.cout, out + s.w, out + s.b);
+        if (s.kind == LK_CONV_C3) rc = pack_conv3x3_c3(w, b, bn, s.cout, precision == VAD_PREC_SPLIT, out + s.w, out + s.b);
         else if (s.kind == LK_CONV) rc = pack_conv3x3_slot(w, b, bn, cout, cin, s, precision, out);
         // dec4.0 (li 14) is always packed for - and run on - the exact-fp32 path: it shares ONE kernel with dec4.3 and the
         // score (dec4_fused.hip), HBM-bound in either arithmetic, and that kernel's first GEMM is exact fp32
@@ -363,6 +392,11 @@ extern "C" int vad_img_pack(const float* const* P, int nparams, int in_ch, int l
         pi += 6;
     }
     if (rc == VAD_OK && pi != nparams) return vad_fail(VAD_ERR_ARG, "img_pack: consumed %d of %d parameters", pi, nparams);
+    if (rc != VAD_OK) {   // name the layer a layer packer refused: the loop stopped one past it
+        char name[16];
+        snprintf(name, sizeof name, "%s%d.%d", li <= 8 ? "enc" : "dec", ((li - 1) & 7) / 2 + 1, ((li - 1) & 1) ? 3 : 0);
+        return layer_refused(rc, "img_pack", name);
+    }
     return rc;
 }
 
@@ -446,14 +480,14 @@ extern "C" int vad_vid_pack_c(const float* const* P, int nparams, int in_ch, int
     memset(out, 0, L.total * sizeof(float));
     put_header(out, VAD_BLOB_VID, precision, latent, hid | (layers << 16));
     const int first_convt = 4 + layers + (L.has_proj ? 1 : 0);
-    int pi = 0;
-    for (int li = 0; li < L.nlayers && rc == VAD_OK; ++li) {
+    int pi = 0, li = 0;
+    for (; li < L.nlayers && rc == VAD_OK; ++li) {
         const LayerSlot& s = L.layer[li];
         const float* w = P[pi], *b = P[pi + 1];
         const float* bn[4] = {nullptr, nullptr, nullptr, nullptr};
         switch (s.kind) {
         case LK_CONV_C3: for (int i = 0; i < 4; ++i) bn[i] = P[pi + 2 + i];
-            rc = vad_pack_conv3x3_c3(w, b, bn, s.cout, out + s.w, out + s.b); pi += 6; break;
+            rc = pack_conv3x3_c3(w, b, bn, s.cout, precision == VAD_PREC_SPLIT, out + s.w, out + s.b); pi += 6; break;
         case LK_CONV: for (int i = 0; i < 4; ++i) bn[i] = P[pi + 2 + i];     // encoder.12 is the one whose cout is latent_dim; encoder.0 of a wide model reads in_ch planes
             rc = pack_conv3x3_slot(w, b, bn, li == 3 ? latent : s.cout, (li == 0 && L.wide) ? in_ch : s.cin, s, precision, out); pi += 6; break;
         case LK_CONVT:
@@ -478,6 +512,15 @@ extern "C" int vad_vid_pack_c(const float* const* P, int nparams, int in_ch, int
         }
     }
     if (rc == VAD_OK && pi != nparams) return vad_fail(VAD_ERR_ARG, "vid_pack: consumed %d of %d parameters", pi, nparams);
+    if (rc != VAD_OK) {   // name the layer a layer packer refused: the loop stopped one past it
+        const int bad = li - 1;
+        char name[40];
+        if (bad < 4) snprintf(name, sizeof name, "encoder.encoder.%d", 4 * bad);
+        else if (bad < 4 + layers) snprintf(name, sizeof name, "convlstm.cells.%d.conv", bad - 4);
+        else if (bad < first_convt) snprintf(name, sizeof name, "proj");
+        else snprintf(name, sizeof name, "decoder.decoder.%d", 3 * (bad - first_convt));
+        return layer_refused(rc, "vid_pack", name);
+    }
     return rc;
 }
 
@@ -516,6 +559,11 @@ extern "C" int vad_convlstm_pack(const float* const* P, int nparams, int cin, co
         const VadSeqSlot s = vad_seq_slot(cin_p, hid_p, l);
         // the x half of a layer above 0 is the layer below's h: its real width may differ from this layer's
         rc = pack_lstm_cell(P[2 * l], P[2 * l + 1], l ? hids[l - 1] : cin, l ? hid_p : cin_p, hids[l], hid_p, precision, out + s.w, out + s.b);
+        if (rc != VAD_OK) {
+            char name[24];
+            snprintf(name, sizeof name, "cells.%d.conv", l);
+            return layer_refused(rc, "convlstm_pack", name);
+        }
     }
     return rc;
 }
