@@ -844,6 +844,41 @@ int vad_smooth_maps(const float* maps, long long n, int h, int w, const float* t
                     void* ws, size_t ws_bytes, void* stream);
 int vad_smooth_tile(int* tile_h, int* tile_w);
 
+/* ------------------------------------------------------------------ Defect regions of an anomaly map (csrc/map_regions.hip)
+ * What turns a map and an operating threshold into detections: the connected regions of {v >= threshold} of every frame, as a
+ * compact table - where they are, how large, how strong.  The maps stay on the device; the table is what leaves it.
+ *
+ * vad_detect_regions: maps = n frames of h x w fp32, contiguous, 4-byte aligned (the limits of vad_label_regions: any h, w >= 1
+ * with h * w < 2^31 - 1; n * h * w <= 2^38).  A pixel is foreground iff v >= threshold - the predicate of the ROC thresholds, which
+ * apply as they stand; a NaN pixel never is (it is counted, below), +Inf always is; a NaN threshold is refused.  Regions are those
+ * of vad_label_regions (the same kernels, the same canonical labels, connectivity 8 or 4, every frame on its own, every walk
+ * bounded, the flag word in the first uint32 of ws).  labels_or_null int32 [n, h, w], when given, receives the labels of ALL
+ * foreground regions, those dropped for their area included.
+ * records uint32 [n, max_regions, VAD_REGION_WORDS], 16-byte aligned; one region is
+ *     word 0      root: the smallest y * w + x of the region
+ *     word 1      area in pixels
+ *     words 2-5   x0, y0, x1, y1 of the bounding box, inclusive
+ *     word 6      peak: the float bits of the region's maximum
+ *     word 7      peak index: the smallest y * w + x among the pixels that hold the maximum
+ *     words 8-9   uint64 sum of x over the region's pixels      (centroid = sum / area, exactly)
+ *     words 10-11 uint64 sum of y
+ * Values compare through the order-preserving key of their bits, so -0.0 < +0.0.  The regions with area >= min_area (>= 1) are
+ * kept, in ascending order of their roots - raster order of their first pixel, scipy.ndimage.label's numbering -, and the first
+ * min(kept, max_regions) are written (max_regions in 1 .. 65536); every other record of the frame is all-zero.
+ * counts uint32 [n, 4]: kept (the full number, which may exceed max_regions: truncation is visible), dropped for area, foreground
+ * pixels, NaN pixels.  Integer atomics, min and max only: both tables are the same words for any batching, launch order or tiling.
+ * ws: caller-provided, 16-byte aligned, vad_regions_workspace_bytes(n, h, w, labels_given) bytes (0 for arguments out of range; no
+ * device is needed): 16 bytes for the flag word, 4 bytes per chunk of 1024 pixels of every frame (padded to 16), then 4 bytes per
+ * pixel each for region sizes and record slots and, with labels_given = 0 (labels_or_null is NULL), for the label plane.
+ * VAD_ERR_ARG for a NULL or misaligned pointer, n, h, w out of range, a connectivity other than 4 or 8, min_area == 0, max_regions
+ * out of range and a NaN threshold; VAD_ERR_WS for a short workspace.  n == 0 clears the flag word only.  Every launch is
+ * asynchronous on `stream`; nothing is allocated, the host never waits, the call can be captured into a graph. */
+#define VAD_REGION_WORDS 12
+size_t vad_regions_workspace_bytes(long long n, int h, int w, int labels_given);
+int vad_detect_regions(const float* maps, long long n, int h, int w, float threshold, int connectivity, unsigned min_area,
+                       int max_regions, int32_t* labels_or_null, uint32_t* records /* [n, max_regions, 12] */,
+                       uint32_t* counts /* [n, 4] */, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ hipGraph capture / replay of a scoring call
  * vad_graph_begin(stream); <one vad_img_score* / vad_vid_score* call on `stream`>; vad_graph_end(stream, &exec) captures
  * the call's launch sequence (kernels, and the fork / join with the library's helper streams) into an instantiated

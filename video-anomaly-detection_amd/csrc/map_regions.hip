@@ -1,0 +1,353 @@
+// Defect regions of an anomaly map: the connected regions of {v >= threshold} of every frame as a table of records - root, area,
+// bounding box, peak and its position, coordinate sums - in raster order of their first pixel.  The
+// reference paints the map (evaluate.py:142-171, main.py:231-250) and compares one scalar with a constant (main.py:282-283); a
+// host route copies every map and runs scipy.ndimage label / find_objects / maximum_position per frame.  Here the maps stay on the
+// device and the table is what leaves it.
+//
+//   label    the union-find of csrc/region_overlap.hip through region_label.h (its init kernel with the predicate v >= threshold):
+//            labels[p] = 0 or 1 + root, sizes[root] = area.  A NaN pixel is never foreground.
+//   count    a frame is cut into chunks of REG_CHUNK pixels; chunk c of frame f counts its kept roots (sizes[root] >= min_area)
+//            into chunk_kept[f][c], and adds kept / dropped roots to counts[f][0 / 1]
+//   slot     the rank of a kept root = the kept roots of the chunks before it (a sum over chunk_kept[f][0 .. c)) + the kept roots in
+//            front of it inside its chunk (ballots, wave totals through LDS): raster order across the whole frame.  A root of rank
+//            r < max_regions gets slots[root] = r + 1 and its record's root, area and the identities of the reductions; any other
+//            root gets slots[root] = 0.  Only roots' slots are ever written or read.
+//   reduce   every foreground pixel whose root has a slot contributes x, y, (key(v) << 32 | ~index) to its record: min / max of
+//            the box, max of the 64-bit peak word (the largest key and, among equals, the smallest index), sums of x and y.  A lane
+//            first gathers its own pixels of one region in registers, then equal slots of a wave are combined by a butterfly, and
+//            one lane issues the seven integer atomics: a frame that is one region costs 28 atomics per 4096 pixels.  The same
+//            pass counts foreground and NaN pixels into counts[f][2 / 3].
+//   finish   the records in use get their peak word split into float bits and index; every other record of the table is zeroed.
+// Integer atomics, min and max only: the table is the same words for any batching, launch order or tiling.  Every launch is
+// asynchronous on the caller's stream, nothing is allocated, the host never waits.
+#include <hip/hip_runtime.h>
+
+#include "region_label.h"
+#include "vad_common.h"
+
+namespace {
+
+typedef unsigned long long u64;
+
+constexpr int REG_THREADS = 256;
+constexpr unsigned REG_CHUNK = 1024;            // pixels of one chunk of the count / slot passes: four rows of the work-group
+constexpr unsigned REG_RUN = 4096;              // pixels a work-group of the reduce pass takes at a time
+constexpr unsigned REG_MAX_BLOCKS_X = 4096;
+constexpr int REG_MAX_REGIONS = 65536;
+
+// The order-preserving key of a float's bits: a < b as floats (with -0.0 < +0.0) iff key(a) < key(b) as unsigned.
+__device__ __forceinline__ unsigned order_key(unsigned bits) { return (bits & 0x80000000u) ? ~bits : bits | 0x80000000u; }
+__device__ __forceinline__ unsigned order_key_inv(unsigned key) { return (key & 0x80000000u) ? key & 0x7fffffffu : ~key; }
+
+__device__ __forceinline__ unsigned wave_sum(unsigned v) {
+    for (int m = 32; m >= 1; m >>= 1) v += (unsigned)__shfl_xor((int)v, m);
+    return v;
+}
+
+struct RegionP {
+    const float* maps;
+    const int* labels;
+    const unsigned* sizes;
+    unsigned* slots;
+    unsigned* chunk_kept;    // [n][nchunks]
+    unsigned* records;       // [n][max_regions][VAD_REGION_WORDS]
+    unsigned* counts;        // [n][4]: kept, dropped for area, foreground pixels, NaN pixels
+    long long n;
+    unsigned npix, nchunks, w, min_area, max_regions;
+};
+
+// kept / dropped roots per chunk
+__global__ __launch_bounds__(REG_THREADS) void regions_count_kernel(RegionP p) {
+    __shared__ unsigned s_kept, s_dropped;
+    for (long long img = blockIdx.y; img < p.n; img += gridDim.y) {
+        const int* L = p.labels + img * (long long)p.npix;
+        const unsigned* S = p.sizes + img * (long long)p.npix;
+        for (unsigned c = blockIdx.x; c < p.nchunks; c += gridDim.x) {   // uniform over the work-group
+            if (threadIdx.x == 0) s_kept = s_dropped = 0u;
+            __syncthreads();
+            unsigned kept = 0u, dropped = 0u;
+            for (unsigned j = 0; j < REG_CHUNK / REG_THREADS; ++j) {
+                const unsigned i = c * REG_CHUNK + j * REG_THREADS + threadIdx.x;      // < 2^31 + 1024: no wrap
+                if (i < p.npix && L[i] == (int)(i + 1u)) {
+                    if (S[i] >= p.min_area) ++kept;
+                    else ++dropped;
+                }
+            }
+            kept = wave_sum(kept);
+            dropped = wave_sum(dropped);
+            if ((threadIdx.x & 63u) == 0u) {
+                if (kept) atomicAdd(&s_kept, kept);
+                if (dropped) atomicAdd(&s_dropped, dropped);
+            }
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                p.chunk_kept[img * (long long)p.nchunks + c] = s_kept;
+                if (s_kept) atomicAdd(p.counts + img * 4, s_kept);
+                if (s_dropped) atomicAdd(p.counts + img * 4 + 1, s_dropped);
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// ranks of the kept roots in raster order; the records' first words and the identities of the reductions
+__global__ __launch_bounds__(REG_THREADS) void regions_slot_kernel(RegionP p) {
+    __shared__ unsigned s_before, s_wave[REG_THREADS / 64];
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (long long img = blockIdx.y; img < p.n; img += gridDim.y) {
+        const int* L = p.labels + img * (long long)p.npix;
+        const unsigned* S = p.sizes + img * (long long)p.npix;
+        unsigned* slots = p.slots + img * (long long)p.npix;
+        const unsigned* kept_of = p.chunk_kept + img * (long long)p.nchunks;
+        unsigned* rec = p.records + (u64)img * p.max_regions * VAD_REGION_WORDS;
+        for (unsigned c = blockIdx.x; c < p.nchunks; c += gridDim.x) {   // uniform over the work-group
+            if (threadIdx.x == 0) s_before = 0u;
+            __syncthreads();
+            unsigned before = 0u;
+            for (unsigned k = threadIdx.x; k < c; k += REG_THREADS) before += kept_of[k];
+            before = wave_sum(before);
+            if (lane == 0u && before) atomicAdd(&s_before, before);
+            __syncthreads();
+            unsigned base = s_before;                                    // the kept roots of this frame in front of the chunk
+            for (unsigned j = 0; j < REG_CHUNK / REG_THREADS; ++j) {
+                const unsigned i = c * REG_CHUNK + j * REG_THREADS + threadIdx.x;
+                const bool root = i < p.npix && L[i] == (int)(i + 1u);
+                const unsigned area = root ? S[i] : 0u;
+                const bool kept = root && area >= p.min_area;
+                const u64 b = __ballot(kept);
+                if (lane == 0u) s_wave[wave] = (unsigned)__builtin_popcountll(b);
+                __syncthreads();
+                unsigned rank = base + (unsigned)__builtin_popcountll(b & ((1ull << lane) - 1ull));
+                unsigned row = 0u;
+                for (unsigned k = 0; k < REG_THREADS / 64; ++k) {
+                    if (k < wave) rank += s_wave[k];
+                    row += s_wave[k];
+                }
+                base += row;
+                __syncthreads();                                         // s_wave is written again in the next row
+                if (kept && rank < p.max_regions) {
+                    slots[i] = rank + 1u;
+                    unsigned* r = rec + (u64)rank * VAD_REGION_WORDS;
+                    *(u32x4*)r = u32x4{i, area, 0xffffffffu, 0xffffffffu};          // root, area, x0, y0 (min)
+                    *(u32x4*)(r + 4) = u32x4{0u, 0u, 0u, 0u};                       // x1, y1 (max), the 64-bit peak word (max)
+                    *(u32x4*)(r + 8) = u32x4{0u, 0u, 0u, 0u};                       // sum x, sum y
+                } else if (root) {
+                    slots[i] = 0u;
+                }
+            }
+        }
+    }
+}
+
+struct RegionAcc {
+    unsigned slot;           // 0 = nothing gathered
+    unsigned x0, y0, x1, y1;
+    u64 peak, sx, sy;
+};
+
+// Adds the lanes' gathered values to their records.  `pending` lanes hold a slot != 0; equal slots of the wave are combined first.
+// Called in converged control flow (the loop is wave-uniform; every round retires at least the leading lane).
+__device__ __forceinline__ void regions_flush(bool pending, const RegionAcc& a, unsigned* rec, unsigned lane) {
+    u64 left = __ballot(pending);
+    while (left != 0) {
+        const int lead = __builtin_ctzll(left);
+        const unsigned first = (unsigned)__builtin_amdgcn_readlane((int)a.slot, lead);
+        const bool mine = pending && a.slot == first;
+        const u64 same = __ballot(mine);
+        unsigned x0 = mine ? a.x0 : 0xffffffffu, y0 = mine ? a.y0 : 0xffffffffu, x1 = mine ? a.x1 : 0u, y1 = mine ? a.y1 : 0u;
+        u64 peak = mine ? a.peak : 0ull, sx = mine ? a.sx : 0ull, sy = mine ? a.sy : 0ull;
+        if ((same & (same - 1ull)) != 0) {                               // wave-uniform: more than one lane holds this slot
+            for (int m = 32; m >= 1; m >>= 1) {
+                const unsigned ox0 = (unsigned)__shfl_xor((int)x0, m), oy0 = (unsigned)__shfl_xor((int)y0, m);
+                const unsigned ox1 = (unsigned)__shfl_xor((int)x1, m), oy1 = (unsigned)__shfl_xor((int)y1, m);
+                const u64 opeak = __shfl_xor(peak, m);
+                x0 = ox0 < x0 ? ox0 : x0;
+                y0 = oy0 < y0 ? oy0 : y0;
+                x1 = ox1 > x1 ? ox1 : x1;
+                y1 = oy1 > y1 ? oy1 : y1;
+                peak = opeak > peak ? opeak : peak;
+                sx += __shfl_xor(sx, m);
+                sy += __shfl_xor(sy, m);
+            }
+        }
+        if (lane == (unsigned)lead) {
+            unsigned* r = rec + (u64)(first - 1u) * VAD_REGION_WORDS;
+            atomicMin(r + 2, x0);
+            atomicMin(r + 3, y0);
+            atomicMax(r + 4, x1);
+            atomicMax(r + 5, y1);
+            atomicMax((u64*)(r + 6), peak);
+            atomicAdd((u64*)(r + 8), sx);
+            atomicAdd((u64*)(r + 10), sy);
+        }
+        if (mine) pending = false;
+        left &= ~same;
+    }
+}
+
+__global__ __launch_bounds__(REG_THREADS) void regions_reduce_kernel(RegionP p) {
+    const unsigned lane = threadIdx.x & 63u;
+    const unsigned nruns = (p.npix + REG_RUN - 1u) / REG_RUN;            // npix < 2^31 - 1: no wrap
+    for (long long img = blockIdx.y; img < p.n; img += gridDim.y) {
+        const float* V = p.maps + img * (long long)p.npix;
+        const int* L = p.labels + img * (long long)p.npix;
+        const unsigned* slots = p.slots + img * (long long)p.npix;
+        unsigned* rec = p.records + (u64)img * p.max_regions * VAD_REGION_WORDS;
+        RegionAcc acc;
+        acc.slot = 0u;
+        acc.x0 = acc.y0 = 0xffffffffu;
+        acc.x1 = acc.y1 = 0u;
+        acc.peak = acc.sx = acc.sy = 0ull;
+        unsigned nfg = 0u, nnan = 0u;
+        for (unsigned run = blockIdx.x; run < nruns; run += gridDim.x) {  // uniform over the work-group
+            for (unsigned j = 0; j < REG_RUN / REG_THREADS; ++j) {       // the same trip count for every lane: converged ballots
+                const u64 i64 = (u64)run * REG_RUN + j * REG_THREADS + threadIdx.x;
+                const bool valid = i64 < p.npix;
+                const unsigned i = (unsigned)i64;
+                const unsigned bits = valid ? __float_as_uint(V[i]) : 0u;
+                const int lab = valid ? L[i] : 0;
+                nnan += (bits & 0x7fffffffu) > 0x7f800000u ? 1u : 0u;
+                nfg += lab != 0 ? 1u : 0u;
+                unsigned slot = 0u;
+                if (lab != 0) {
+                    const unsigned root = (unsigned)lab - 1u;
+                    slot = root < p.npix ? slots[root] : 0u;            // a label is a root of this frame: always inside
+                    if (slot > p.max_regions) slot = 0u;                 // never, short of a defect: no address is formed from it
+                }
+                // another region than the one gathered so far: that one goes to its record first
+                regions_flush(acc.slot != 0u && slot != 0u && slot != acc.slot, acc, rec, lane);
+                if (slot != 0u) {
+                    const unsigned y = i / p.w, x = i - y * p.w;
+                    const u64 peak = ((u64)order_key(bits) << 32) | (u64)(~i);
+                    if (slot != acc.slot) {
+                        acc.slot = slot;
+                        acc.x0 = acc.x1 = x;
+                        acc.y0 = acc.y1 = y;
+                        acc.peak = peak;
+                        acc.sx = x;
+                        acc.sy = y;
+                    } else {
+                        acc.x0 = x < acc.x0 ? x : acc.x0;
+                        acc.y0 = y < acc.y0 ? y : acc.y0;
+                        acc.x1 = x > acc.x1 ? x : acc.x1;
+                        acc.y1 = y > acc.y1 ? y : acc.y1;
+                        acc.peak = peak > acc.peak ? peak : acc.peak;
+                        acc.sx += x;
+                        acc.sy += y;
+                    }
+                }
+            }
+        }
+        regions_flush(acc.slot != 0u, acc, rec, lane);
+        nfg = wave_sum(nfg);
+        nnan = wave_sum(nnan);
+        if (lane == 0u) {
+            if (nfg) atomicAdd(p.counts + img * 4 + 2, nfg);
+            if (nnan) atomicAdd(p.counts + img * 4 + 3, nnan);
+        }
+    }
+}
+
+// the peak word of a record in use -> float bits, index; every record behind the frame's last one -> zeros
+__global__ __launch_bounds__(REG_THREADS) void regions_finish_kernel(RegionP p) {
+    const u64 total = (u64)p.n * p.max_regions;
+    for (u64 k = (u64)blockIdx.x * REG_THREADS + threadIdx.x; k < total; k += (u64)gridDim.x * REG_THREADS) {
+        const u64 img = k / p.max_regions;
+        const unsigned r = (unsigned)(k - img * p.max_regions);
+        unsigned* rec = p.records + k * VAD_REGION_WORDS;
+        if (r < p.counts[img * 4]) {                                     // kept may exceed max_regions; r does not
+            const unsigned not_index = rec[6], key = rec[7];
+            rec[6] = order_key_inv(key);
+            rec[7] = ~not_index;
+        } else {
+            *(u32x4*)rec = u32x4{0u, 0u, 0u, 0u};
+            *(u32x4*)(rec + 4) = u32x4{0u, 0u, 0u, 0u};
+            *(u32x4*)(rec + 8) = u32x4{0u, 0u, 0u, 0u};
+        }
+    }
+}
+
+unsigned regions_chunks(int h, int w) { return (unsigned)(((long long)h * w + REG_CHUNK - 1) / REG_CHUNK); }
+
+// the bytes in front of the planes: the flag word's 16, then chunk_kept [n][nchunks], padded to 16
+size_t regions_head_bytes(long long n, int h, int w) {
+    const size_t words = (size_t)n * regions_chunks(h, w);
+    return VAD_LABEL_WS_HEAD_BYTES + ((words * 4 + 15) & ~(size_t)15);
+}
+
+}  // namespace
+
+size_t vad_regions_workspace_bytes(long long n, int h, int w, int labels_given) {
+    long long total = 0;
+    if (!vad_label_dims_ok(n, h, w, &total) || (labels_given != 0 && labels_given != 1)) return 0;
+    return regions_head_bytes(n, h, w) + (size_t)(labels_given ? 8 : 12) * (size_t)total;   // [labels,] sizes, slots: 4 bytes each
+}
+
+int vad_detect_regions(const float* maps, long long n, int h, int w, float threshold, int connectivity, unsigned min_area,
+                       int max_regions, int32_t* labels_or_null, uint32_t* records, uint32_t* counts, void* ws, size_t ws_bytes,
+                       void* stream) {
+    VAD_REQUIRE(maps != nullptr, "detect_regions: maps is NULL");
+    VAD_REQUIRE((uintptr_t)maps % 4 == 0, "detect_regions: maps must be 4-byte aligned");
+    VAD_REQUIRE(n >= 0, "detect_regions: n must be >= 0, got %lld", n);
+    VAD_REQUIRE(h >= 1 && w >= 1 && (long long)h * w < 2147483647ll, "detect_regions: h and w must be >= 1 with h * w < 2^31 - 1, got %d x %d",
+                h, w);
+    long long total = 0;
+    VAD_REQUIRE(vad_label_dims_ok(n, h, w, &total), "detect_regions: n * h * w must be at most 2^38 (%lld x %d x %d)", n, h, w);
+    VAD_REQUIRE(threshold == threshold, "detect_regions: threshold is NaN");
+    VAD_REQUIRE(connectivity == 4 || connectivity == 8, "detect_regions: connectivity must be 4 or 8, got %d", connectivity);
+    VAD_REQUIRE(min_area >= 1u, "detect_regions: min_area must be >= 1, got 0");
+    VAD_REQUIRE(max_regions >= 1 && max_regions <= REG_MAX_REGIONS, "detect_regions: max_regions must be in 1..%d, got %d", REG_MAX_REGIONS,
+                max_regions);
+    VAD_REQUIRE((uintptr_t)labels_or_null % 4 == 0, "detect_regions: labels must be 4-byte aligned");
+    VAD_REQUIRE(records != nullptr, "detect_regions: records is NULL");
+    VAD_REQUIRE((uintptr_t)records % 16 == 0, "detect_regions: records must be 16-byte aligned");
+    VAD_REQUIRE(counts != nullptr, "detect_regions: counts is NULL");
+    VAD_REQUIRE((uintptr_t)counts % 4 == 0, "detect_regions: counts must be 4-byte aligned");
+    VAD_REQUIRE(ws != nullptr, "detect_regions: ws is NULL");
+    VAD_REQUIRE((uintptr_t)ws % 16 == 0, "detect_regions: ws must be 16-byte aligned");
+    const int given = labels_or_null != nullptr ? 1 : 0;
+    const size_t need = vad_regions_workspace_bytes(n, h, w, given);
+    if (ws_bytes < need)
+        return vad_fail(VAD_ERR_WS, "detect_regions: ws_bytes %zu is less than vad_regions_workspace_bytes(%lld, %d, %d, %d) = %zu", ws_bytes,
+                        n, h, w, given, need);
+    const hipStream_t s = (hipStream_t)stream;
+    if (n == 0) {                                            // nothing to detect: the flag word still reads "no defect"
+        VAD_HIP_TRY(hipMemsetAsync(ws, 0, VAD_LABEL_WS_HEAD_BYTES, s));
+        return VAD_OK;
+    }
+    unsigned* flags = (unsigned*)ws;
+    unsigned* planes = (unsigned*)((char*)ws + regions_head_bytes(n, h, w));
+    int* labels = given ? labels_or_null : (int*)planes;
+    unsigned* sizes = given ? planes : planes + total;
+    if (int rc = vad_label_launch(maps, VAD_LABEL_FMT_F32_GE, threshold, n, h, w, connectivity, labels, sizes, flags, s)) return rc;
+
+    RegionP p;
+    p.maps = maps;
+    p.labels = labels;
+    p.sizes = sizes;
+    p.slots = sizes + total;
+    p.chunk_kept = (unsigned*)((char*)ws + VAD_LABEL_WS_HEAD_BYTES);
+    p.records = records;
+    p.counts = counts;
+    p.n = n;
+    p.npix = (unsigned)h * (unsigned)w;
+    p.nchunks = regions_chunks(h, w);
+    p.w = (unsigned)w;
+    p.min_area = min_area;
+    p.max_regions = (unsigned)max_regions;
+    VAD_HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n * 16, s));
+    const unsigned gy = (unsigned)(n < 65535 ? n : 65535);
+    const dim3 chunk_grid(p.nchunks < REG_MAX_BLOCKS_X ? p.nchunks : REG_MAX_BLOCKS_X, gy);
+    hipLaunchKernelGGL(regions_count_kernel, chunk_grid, dim3(REG_THREADS), 0, s, p);
+    VAD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(regions_slot_kernel, chunk_grid, dim3(REG_THREADS), 0, s, p);
+    VAD_LAUNCH_CHECK();
+    const unsigned nruns = (p.npix + REG_RUN - 1u) / REG_RUN;
+    hipLaunchKernelGGL(regions_reduce_kernel, dim3(nruns < REG_MAX_BLOCKS_X ? nruns : REG_MAX_BLOCKS_X, gy), dim3(REG_THREADS), 0, s, p);
+    VAD_LAUNCH_CHECK();
+    const unsigned long long recs = (unsigned long long)n * p.max_regions;
+    const unsigned long long fin = (recs + REG_THREADS - 1) / REG_THREADS;
+    hipLaunchKernelGGL(regions_finish_kernel, dim3((unsigned)(fin < 65536ull ? fin : 65536ull)), dim3(REG_THREADS), 0, s, p);
+    VAD_LAUNCH_CHECK();
+    return VAD_OK;
+}

@@ -14,6 +14,8 @@
 // its two indices by a smaller one in every step (a step of a chase, or the parent another thread wrote), so it ends within
 // 2 * h * w steps whatever the other threads do.  A walk that runs out of its budget sets LABEL_FLAG_WALK in the workspace's
 // flag word and leaves: a defect gives an error (the Python layer raises on a set flag), never a spin.
+// The three kernels are also what csrc/map_regions.hip labels thresholded anomaly maps with (region_label.h: vad_label_launch and an
+// internal third predicate of the init kernel, v >= threshold, which the public entry points refuse like any unknown format).
 //
 // Histogram: the state is {u32 header[4]; u64 wpos[nbins], pos[nbins], neg[nbins]; u64 regions, max_region, rejected[2], flags}.
 // pos / neg are the counters of score_hist.hip (its quantiser, its rejection rules, its wave + LDS combining: score_hist_lds.h).
@@ -22,6 +24,7 @@
 // 64-bit global atomic.  Integer atomics only - the counters are exact and the same for any batching, order or sharding.
 #include <hip/hip_runtime.h>
 
+#include "region_label.h"
 #include "score_hist_lds.h"
 #include "vad_common.h"
 
@@ -34,7 +37,7 @@ constexpr unsigned LABEL_MAX_BLOCKS_X = 4096;
 constexpr unsigned LABEL_FLAG_WALK = 1u;       // a root chase or a union ran out of its step budget
 constexpr unsigned LABEL_FLAG_SIZE = 2u;       // an anomalous pixel's region has size 0 (the label planes are not a labelling)
 constexpr long long PRO_MAX_ELEMS = 1ll << 38; // n * h * w of one call: a work-group's run of a 256-group launch stays below 2^32
-constexpr size_t WS_HEAD_BYTES = 16;           // the flag word, padded so that the planes behind it are 16-byte aligned
+constexpr size_t WS_HEAD_BYTES = VAD_LABEL_WS_HEAD_BYTES;
 
 __device__ __forceinline__ bool pro_header_ok(const unsigned* hdr, int m) {
     return hdr[0] == PRO_MAGIC && hdr[1] == hist_tag(m) && hdr[2] == (unsigned)m;
@@ -48,6 +51,7 @@ struct LabelP {
     long long n;
     unsigned npix;           // h * w < 2^31 - 1
     int w, fmt, conn;
+    float threshold;         // VAD_LABEL_FMT_F32_GE only
 };
 
 __device__ __forceinline__ int label_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -95,8 +99,10 @@ __global__ __launch_bounds__(LABEL_THREADS) void label_init_kernel(LabelP p) {
     for (long long img = blockIdx.y; img < p.n; img += gridDim.y) {
         const long long off = img * (long long)p.npix;
         for (unsigned i = blockIdx.x * LABEL_THREADS + threadIdx.x; i < p.npix; i += gridDim.x * LABEL_THREADS) {
-            const bool fg = p.fmt == VAD_LBL_U8_ELEM ? ((const unsigned char*)p.masks)[off + i] >= 128
-                                                     : ((const float*)p.masks)[off + i] > 0.5f;
+            bool fg;
+            if (p.fmt == VAD_LBL_U8_ELEM) fg = ((const unsigned char*)p.masks)[off + i] >= 128;
+            else if (p.fmt == VAD_LABEL_FMT_F32_GE) fg = ((const float*)p.masks)[off + i] >= p.threshold;   // false for a NaN value
+            else fg = ((const float*)p.masks)[off + i] > 0.5f;
             p.labels[off + i] = fg ? (int)(i + 1u) : 0;
             if (p.sizes != nullptr) p.sizes[off + i] = 0u;
         }
@@ -163,30 +169,6 @@ __global__ __launch_bounds__(LABEL_THREADS) void label_flatten_kernel(LabelP p) 
         }
     }
     if (failed) atomicOr(p.flags, LABEL_FLAG_WALK);
-}
-
-int label_launch(const void* masks, int fmt, long long n, int h, int w, int conn, int* labels, unsigned* sizes, unsigned* flags,
-                 hipStream_t s) {
-    LabelP p;
-    p.masks = masks;
-    p.labels = labels;
-    p.sizes = sizes;
-    p.flags = flags;
-    p.n = n;
-    p.npix = (unsigned)h * (unsigned)w;
-    p.w = w;
-    p.fmt = fmt;
-    p.conn = conn;
-    unsigned bx = (p.npix + LABEL_THREADS - 1) / LABEL_THREADS;
-    if (bx > LABEL_MAX_BLOCKS_X) bx = LABEL_MAX_BLOCKS_X;
-    const dim3 grid(bx, (unsigned)(n < 65535 ? n : 65535));
-    hipLaunchKernelGGL(label_init_kernel, grid, dim3(LABEL_THREADS), 0, s, p);
-    VAD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(label_merge_kernel, grid, dim3(LABEL_THREADS), 0, s, p);
-    VAD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(label_flatten_kernel, grid, dim3(LABEL_THREADS), 0, s, p);
-    VAD_LAUNCH_CHECK();
-    return VAD_OK;
 }
 
 struct ProP {
@@ -342,6 +324,36 @@ int label_args(const char* fn, const void* masks, int label_format, long long n,
 
 }  // namespace
 
+bool vad_label_dims_ok(long long n, int h, int w, long long* total) {
+    return n >= 0 && h >= 1 && w >= 1 && (long long)h * w < 2147483647ll && !__builtin_mul_overflow(n, (long long)h * w, total) &&
+           *total <= PRO_MAX_ELEMS;
+}
+
+int vad_label_launch(const void* masks, int fmt, float threshold, long long n, int h, int w, int conn, int* labels, unsigned* sizes,
+                     unsigned* flags, hipStream_t s) {
+    LabelP p;
+    p.masks = masks;
+    p.labels = labels;
+    p.sizes = sizes;
+    p.flags = flags;
+    p.n = n;
+    p.npix = (unsigned)h * (unsigned)w;
+    p.w = w;
+    p.fmt = fmt;
+    p.conn = conn;
+    p.threshold = threshold;
+    unsigned bx = (p.npix + LABEL_THREADS - 1) / LABEL_THREADS;
+    if (bx > LABEL_MAX_BLOCKS_X) bx = LABEL_MAX_BLOCKS_X;
+    const dim3 grid(bx, (unsigned)(n < 65535 ? n : 65535));
+    hipLaunchKernelGGL(label_init_kernel, grid, dim3(LABEL_THREADS), 0, s, p);
+    VAD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(label_merge_kernel, grid, dim3(LABEL_THREADS), 0, s, p);
+    VAD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(label_flatten_kernel, grid, dim3(LABEL_THREADS), 0, s, p);
+    VAD_LAUNCH_CHECK();
+    return VAD_OK;
+}
+
 size_t vad_pro_state_bytes(int m) {
     if (!pro_m_ok(m)) return 0;
     return 16 + 8 * (3 * (size_t)hist_nbins(m) + PRO_TAIL_WORDS);
@@ -374,9 +386,7 @@ int vad_pro_merge(void* dst, const void* src, int m, void* stream) {
 
 size_t vad_pro_workspace_bytes(long long n, int h, int w) {
     long long total = 0;
-    if (n < 0 || h < 1 || w < 1 || (long long)h * w >= 2147483647ll || __builtin_mul_overflow(n, (long long)h * w, &total) ||
-        total > PRO_MAX_ELEMS)
-        return 0;
+    if (!vad_label_dims_ok(n, h, w, &total)) return 0;
     return WS_HEAD_BYTES + 8 * (size_t)total;                // the flag word; an int32 label and a uint32 size per pixel
 }
 
@@ -395,7 +405,7 @@ int vad_label_regions(const void* masks, int label_format, long long n, int h, i
         VAD_HIP_TRY(hipMemsetAsync(ws, 0, WS_HEAD_BYTES, s));
         return VAD_OK;
     }
-    return label_launch(masks, label_format, n, h, w, connectivity, labels, sizes_or_null, (unsigned*)ws, s);
+    return vad_label_launch(masks, label_format, 0.f, n, h, w, connectivity, labels, sizes_or_null, (unsigned*)ws, s);
 }
 
 int vad_pro_accumulate(const float* values, const void* masks, int label_format, long long n, int h, int w, int connectivity,
@@ -416,7 +426,7 @@ int vad_pro_accumulate(const float* values, const void* masks, int label_format,
     unsigned* flags = (unsigned*)ws;
     int* labels = (int*)((char*)ws + WS_HEAD_BYTES);
     unsigned* sizes = (unsigned*)(labels + total);
-    if (int rc = label_launch(masks, label_format, n, h, w, connectivity, labels, sizes, flags, s)) return rc;
+    if (int rc = vad_label_launch(masks, label_format, 0.f, n, h, w, connectivity, labels, sizes, flags, s)) return rc;
     ProP p;
     p.values = values;
     p.labels = labels;

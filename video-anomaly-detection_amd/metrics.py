@@ -20,6 +20,9 @@ The second half of the file is the per-region overlap (AUPRO): `label_regions`, 
 
 The third part is what goes in front of both: `gaussian_taps` / `smooth_maps` (csrc/map_smooth.hip) smooth the anomaly maps with
 scipy's Gaussian on the device and give the per-frame maximum of the smoothed map, the image score of the MVTec evaluation.
+
+The last part is what comes behind them on a deployed line: `detect_regions` (csrc/map_regions.hip) turns a map and an operating
+threshold into a table of connected regions per frame - box, area, peak, centroid sums - without a map leaving the device.
 """
 from __future__ import annotations
 
@@ -809,3 +812,130 @@ def smooth_maps(maps: torch.Tensor, sigma: float = 4.0, truncate: float = 4.0, o
     if only:
         return fmax
     return (out, fmax) if return_max else out
+
+
+# ====================================================================== defect regions of an anomaly map
+# What a deployed line needs after the thresholds above: which connected regions of a frame's map are at or
+# above the operating threshold, where they are, how large and how strong - as a compact table per frame, not as a picture.  The
+# host route is a copy of every map (256 KB per 256 x 256 frame) and scipy.ndimage label / find_objects / maximum_position /
+# center_of_mass per frame; here the maps stay on the device and the table is what a renderer, an alarm or a logger reads.
+REGION_WORDS = hip.REGION_WORDS
+MAX_REGIONS = hip.MAX_REGIONS
+
+
+class Regions:
+    """The table `detect_regions` returns, as device tensors with the leading shape of the maps (`[B]`, or `[B,T]` for clips):
+
+      records  int32 [..., R, 12]: the words of `vad_detect_regions` (include/vad_hip.h), R = max_regions; the kept regions of a
+               frame in raster order of their first pixel, all-zero records behind them
+      counts   int32 [..., 4]: kept regions (the full number: above R the table is truncated), regions dropped for their area,
+               foreground pixels, NaN pixels (a NaN is never foreground; it does not vanish silently)
+      labels   int32 [..., H, W] or None: 0, or 1 + root, for ALL foreground regions (with `return_labels=True`)
+
+    Views of `records` (no copies): `root`, `area`, `peak_index` int32 [..., R]; `box` int32 [..., R, 4] = x0, y0, x1, y1 inclusive;
+    `peak` float32 [..., R]; `sum_x`, `sum_y` int64 [..., R]."""
+
+    def __init__(self, records: torch.Tensor, counts: torch.Tensor, labels: Optional[torch.Tensor], frame_shape: Tuple[int, int],
+                 threshold: float, connectivity: int, min_area: int):
+        self.records, self.counts, self.labels = records, counts, labels
+        self.frame_shape, self.threshold, self.connectivity, self.min_area = frame_shape, threshold, connectivity, min_area
+        self.max_regions = int(records.shape[-2])
+
+    root = property(lambda self: self.records[..., 0])
+    area = property(lambda self: self.records[..., 1])
+    box = property(lambda self: self.records[..., 2:6])
+    peak = property(lambda self: self.records[..., 6].view(torch.float32))
+    peak_index = property(lambda self: self.records[..., 7])
+    sum_x = property(lambda self: self.records[..., 8:10].view(torch.int64)[..., 0])
+    sum_y = property(lambda self: self.records[..., 10:12].view(torch.int64)[..., 0])
+
+    def centroids(self) -> torch.Tensor:
+        """float64 [..., R, 2] on the device: (y, x) = (sum_y / area, sum_x / area), each quotient rounded once; NaN for the
+        all-zero records behind a frame's last region."""
+        area = self.area.to(torch.float64)
+        return torch.stack([self.sum_y.to(torch.float64) / area, self.sum_x.to(torch.float64) / area], dim=-1)
+
+    def truncated(self) -> torch.Tensor:
+        """bool [...]: the frame has more kept regions than the table has records."""
+        return self.counts[..., 0] > self.max_regions
+
+    def to_list(self) -> list:
+        """A host copy of the table - 48 bytes per record, never a map -: one list per frame (frames in row-major order of the
+        leading shape) of {'root', 'area', 'box': (x0, y0, x1, y1), 'peak', 'peak_yx', 'centroid_yx'} in table order."""
+        w = self.frame_shape[1]
+        rec = self.records.reshape(-1, self.max_regions, REGION_WORDS).cpu().numpy()
+        kept = self.counts.reshape(-1, 4)[:, 0].cpu().numpy()
+        out = []
+        for f in range(rec.shape[0]):
+            rows = []
+            for r in rec[f, :min(int(kept[f]), self.max_regions)]:
+                area = int(r[1])
+                sx, sy = (int(v) for v in r[8:12].copy().view(np.int64))
+                rows.append({"root": int(r[0]), "area": area, "box": tuple(int(v) for v in r[2:6]), "peak": float(r[6:7].copy().view(np.float32)[0]),
+                             "peak_yx": divmod(int(r[7]), w), "centroid_yx": (sy / area, sx / area)})
+            out.append(rows)
+        return out
+
+
+def _region_frames(maps: torch.Tensor, what: str):
+    """-> (contiguous [N,H,W] view / copy, leading shape) of maps [B,H,W], [B,1,H,W] or [B,T,1,H,W]."""
+    if maps.dim() == 3:
+        lead = (maps.shape[0],)
+    elif maps.dim() == 4 and maps.shape[1] == 1:
+        lead = (maps.shape[0],)
+    elif maps.dim() == 5 and maps.shape[2] == 1:
+        lead = (maps.shape[0], maps.shape[1])
+    else:
+        raise hip.VadError(f"{what}: maps must be [B,H,W], [B,1,H,W] or [B,T,1,H,W], got {tuple(maps.shape)}")
+    h, w = int(maps.shape[-2]), int(maps.shape[-1])
+    if h < 1 or w < 1:
+        raise hip.VadError(f"{what}: frames of {h} x {w} are out of range (H, W >= 1)")
+    return maps.reshape(-1, h, w).contiguous(), tuple(int(v) for v in lead)
+
+
+def detect_regions(maps: torch.Tensor, threshold: float, connectivity: int = 8, min_area: int = 1, max_regions: int = 64,
+                   return_labels: bool = False) -> Regions:
+    """The connected regions of `maps >= threshold` of every frame, on the GPU (`vad_detect_regions`, csrc/map_regions.hip).
+    `maps`: float32 GPU tensor `[B,H,W]`, `[B,1,H,W]` (error / SSIM / smoothed maps) or `[B,T,1,H,W]` (the video model's maps); every
+    frame is labelled on its own, never across time.  `threshold`: a float32 value (NaN is refused) - the predicate is the one of
+    `roc_curve_from_counts`, so `threshold_at_fpr` / `best_f1_threshold` results apply as they stand.  Regions are those of
+    `label_regions` (connectivity 8 or 4); the ones with at least `min_area` pixels are kept, in raster order of their first pixel
+    (scipy.ndimage.label's numbering), the first `max_regions` (1..65536) written.  Returns a `Regions`; like `label_regions` it
+    reads the kernels' flag word (one 4-byte copy, which waits for the call) and raises VadError if it is set.  No CPU fallback."""
+    what = "detect_regions"
+    connectivity = _check_connectivity(connectivity, what)
+    if not isinstance(maps, torch.Tensor):
+        raise hip.VadError(f"{what}: maps must be a torch tensor")
+    if not maps.is_cuda:
+        raise hip.VadError(f"{what}: maps ({maps.device}) must be on the GPU (regions are detected on the device; there is no CPU fallback)")
+    if maps.dtype != torch.float32:
+        raise hip.VadError(f"{what}: maps must be float32, got {maps.dtype}")
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)) or np.isnan(threshold):
+        raise hip.VadError(f"{what}: threshold must be a number that is not NaN, got {threshold!r}")
+    for name, v, hi in (("min_area", min_area, 2 ** 32 - 1), ("max_regions", max_regions, MAX_REGIONS)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= hi:
+            raise hip.VadError(f"{what}: {name} must be an int in 1..{hi}, got {v!r}")
+    min_area, max_regions = int(min_area), int(max_regions)
+    frames, lead = _region_frames(maps, what)
+    n, h, w = frames.shape
+    if n == 0:                                                            # nothing to detect, nothing to launch
+        return Regions(torch.zeros((*lead, max_regions, REGION_WORDS), dtype=torch.int32, device=frames.device),
+                       torch.zeros((*lead, 4), dtype=torch.int32, device=frames.device),
+                       torch.zeros((*lead, h, w), dtype=torch.int32, device=frames.device) if return_labels else None, (h, w),
+                       float(np.float32(threshold)), connectivity, min_area)
+    with torch.cuda.device(frames.device):
+        l = hip.lib()
+        size = l.vad_regions_workspace_bytes(n, h, w, 1 if return_labels else 0)
+        if size == 0:
+            raise hip.VadError(f"{what}: {n} frames of {h} x {w} are out of range (h * w < 2^31 - 1, n * h * w <= 2^38)")
+        ws = torch.empty(size, dtype=torch.uint8, device=frames.device)
+        records = torch.empty((n, max_regions, REGION_WORDS), dtype=torch.int32, device=frames.device)
+        counts = torch.empty((n, 4), dtype=torch.int32, device=frames.device)
+        labels = torch.empty((n, h, w), dtype=torch.int32, device=frames.device) if return_labels else None
+        hip.check(l.vad_detect_regions(frames.data_ptr(), n, h, w, float(np.float32(threshold)), connectivity, min_area, max_regions,
+                                       hip.ptr(labels), records.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(),
+                                       hip.current_stream()), "vad_detect_regions")
+    hip.calls["detect_regions"] = hip.calls.get("detect_regions", 0) + 1
+    _raise_on_flags(int(ws[:4].view(torch.int32).item()), what)
+    return Regions(records.view(*lead, max_regions, REGION_WORDS), counts.view(*lead, 4),
+                   labels.view(*lead, h, w) if return_labels else None, (h, w), float(np.float32(threshold)), connectivity, min_area)

@@ -450,3 +450,22 @@ def frame_auroc(model, loader: Iterable[dict], device, hist=None, mantissa_bits:
             hist.accumulate(model.score_seq_and_frames(frames)["frame"], labels)
     auroc, tie_bound = hist.auroc()
     return auroc, tie_bound, hist
+
+
+def localize(model, images, threshold: float, map: str = "mse", sigma=None, truncate: float = 4.0, connectivity: int = 8,
+             min_area: int = 1, max_regions: int = 64):
+    """Detections of one batch: the model's anomaly maps and the connected regions of `map >= threshold` in them - where the
+    reference paints the map (evaluate.py:142-171, main.py:231-250) and compares one scalar with a constant (main.py:282-283).
+    `images`: `[B,C,H,W]` frames for the image model, `[B,T,C,H,W]` clips for the video model (map "mse" only; every frame of a
+    clip is labelled on its own).  `map`, `sigma`, `truncate` as in `pixel_auroc`, so a threshold taken from its histogram
+    (`metrics.threshold_at_fpr`, `best_f1_threshold`) applies as it stands.  Per batch ONE scoring call, an optional smoothing call
+    and ONE `metrics.detect_regions` call; nothing but the flag word is read by the host.  Returns (`metrics.Regions`, maps): the
+    table with the leading shape `[B]` / `[B,T]`, and the maps it was made from, `[B,1,H,W]` / `[B,T,1,H,W]`, still on the device."""
+    from . import metrics
+    if map not in ("mse", "ssim"):
+        raise hip.VadError(f"localize: map must be 'mse' or 'ssim', got {map!r}")
+    if images.dim() == 5 and map != "mse":
+        raise hip.VadError(f"localize: clips [B,T,C,H,W] are localised on the error map only (map='mse'), got {map!r}")
+    with torch.no_grad():
+        maps = _anomaly_maps(model, images, map, sigma, truncate)
+        return metrics.detect_regions(maps, threshold, connectivity, min_area, max_regions), maps
