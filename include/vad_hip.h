@@ -879,6 +879,50 @@ int vad_detect_regions(const float* maps, long long n, int h, int w, float thres
                        int max_regions, int32_t* labels_or_null, uint32_t* records /* [n, max_regions, 12] */,
                        uint32_t* counts /* [n, 4] */, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ Per-pixel calibration of anomaly maps (csrc/map_stats.hip)
+ * The mean and standard deviation of every pixel of the anomaly map over the normal (training) frames, and the z-score map
+ * z = (map - mean) / std that is ranked, thresholded and labelled in place of the raw map.  The maps stay on the device.
+ *
+ * State blob (caller-owned device memory, 16-byte aligned, vad_mapstat_state_bytes(h, w) bytes; 0 for h, w below 1 or h * w above
+ * VAD_MAX_FRAME_PIXELS, no device needed):
+ *     uint32 magic "VADM", abi << 16;  int32 h, w;  uint64 n (frames seen), uint64 reserved;  float64 K[h*w], S1[h*w], S2[h*w]
+ * vad_mapstat_reset writes the header and zeroes the planes.  The count lives on the device, so every call below is asynchronous
+ * on `stream`, allocates nothing, never waits for the device and can be captured into a graph; a replayed accumulate accumulates
+ * again.  The header is compared with the call's h, w ON THE DEVICE (the host cannot see it without waiting): with a blob made
+ * for another geometry, or not a state, accumulate and merge change nothing and follow no offset of it, and finalize writes NaN.
+ *
+ * Arithmetic, float64, every operation rounded on its own (no fused multiply-add), so numpy restates it bit for bit and a result
+ * does not depend on how the frames were batched:
+ * vad_mapstat_accumulate: maps = n frames of h x w fp32, contiguous, 4-byte aligned.  Per pixel, in frame order: if the state is
+ *   empty K = (double)x[0]; for every frame d = (double)x - K, S1 = S1 + d, S2 = S2 + d * d; then n grows by the call's n.  One
+ *   thread owns a pixel (its additions are never split), with vad_mapstat_plan's frames_in_flight loads outstanding.  A NaN, or an
+ *   Inf in the first frame, makes the pixel's mean and std NaN; a later Inf makes its std NaN and its mean that infinity; no
+ *   other pixel changes a bit.  Two launches (the pixels, then the count).
+ * vad_mapstat_merge: state += other (two launches).  dl = K_b - K_a; S1 = S1_a + (S1_b + n_b dl); S2 = S2_a + (S2_b + ((2 dl) S1_b +
+ *   (n_b dl) dl)), evaluated in that order; the counts are added and K_a is kept; if either side is empty the result is the other.
+ * vad_mapstat_finalize: mean, std fp32 [h*w] (either may be NULL, not both).  mean = fl32(K + S1 / n); var = (S2 - S1 (S1 / n)) /
+ *   (n - ddof), var < 0 -> 0 (a NaN stays), std = sqrtf(fl32(var)): the root in fp32, correctly rounded.  ddof is 0 or 1.  With
+ *   n == 0 both are NaN everywhere, with n - ddof <= 0 std is.  One launch.
+ * vad_map_normalize: z = (x - mean) / den, den = std < min_std ? min_std : std (a NaN std stays NaN), fp32, each operation rounded
+ *   on its own, IEEE division; min_std finite and > 0.  out (may be NULL) may be maps itself - in place - but must not partly
+ *   overlap it.  frame_max (may be NULL; not both): [n], the maximum of each normalised frame with torch.amax semantics,
+ *   compare-only: the same for every batching and tiling.  ws: vad_map_normalize_workspace_bytes(n, h, w) bytes (0 for arguments
+ *   out of range), needed only with frame_max.  One launch (two with frame_max).
+ * vad_mapstat_plan reports pixels per thread, frames in flight per thread and threads per work-group of the accumulate kernel -
+ *   what a test needs to build shapes that cross its internal boundaries.
+ * VAD_ERR_ARG for h, w below 1 or h * w above VAD_MAX_FRAME_PIXELS, n < 0, a NULL or misaligned pointer (states 16 bytes, the rest 4),
+ * other overlapping state, ddof outside 0..1, a min_std that is not finite and > 0, both outputs NULL, a partly overlapping out;
+ * VAD_ERR_WS for a short workspace.  n == 0 returns VAD_OK and launches nothing. */
+size_t vad_mapstat_state_bytes(int h, int w);
+int vad_mapstat_reset(void* state, int h, int w, void* stream);
+int vad_mapstat_accumulate(const float* maps, long long n, int h, int w, void* state, void* stream);
+int vad_mapstat_merge(void* state, const void* other, int h, int w, void* stream);
+int vad_mapstat_finalize(const void* state, int h, int w, int ddof, float* mean, float* std_out, void* stream);
+size_t vad_map_normalize_workspace_bytes(long long n, int h, int w);
+int vad_map_normalize(const float* maps, long long n, int h, int w, const float* mean, const float* std_in, float min_std, float* out,
+                      float* frame_max, void* ws, size_t ws_bytes, void* stream);
+int vad_mapstat_plan(int* pixels_per_thread, int* frames_in_flight, int* threads);
+
 /* ------------------------------------------------------------------ hipGraph capture / replay of a scoring call
  * vad_graph_begin(stream); <one vad_img_score* / vad_vid_score* call on `stream`>; vad_graph_end(stream, &exec) captures
  * the call's launch sequence (kernels, and the fork / join with the library's helper streams) into an instantiated

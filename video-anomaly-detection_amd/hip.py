@@ -16,7 +16,7 @@ PKG_DIR = Path(__file__).resolve().parent
 REPO_DIR = PKG_DIR.parent
 CSRC = PKG_DIR / "csrc"
 LIB_PATH = Path(os.environ.get("VAD_LIB", PKG_DIR / "libvad_hip.so"))
-SOURCES = ["conv_mfma.hip", "conv_wino.hip", "dec4_fused.hip", "tail.hip", "wide_io.hip", "state_io.hip", "resize_u8.hip", "frame_gather.hip", "score_hist.hip", "region_overlap.hip", "map_regions.hip", "map_smooth.hip", "ssim.hip", "train_ops.hip", "wgrad.hip", "train_step.hip", "train_step_img.hip", "vad_api.hip", "pack.cpp"]
+SOURCES = ["conv_mfma.hip", "conv_wino.hip", "dec4_fused.hip", "tail.hip", "wide_io.hip", "state_io.hip", "resize_u8.hip", "frame_gather.hip", "score_hist.hip", "region_overlap.hip", "map_regions.hip", "map_smooth.hip", "map_stats.hip", "ssim.hip", "train_ops.hip", "wgrad.hip", "train_step.hip", "train_step_img.hip", "vad_api.hip", "pack.cpp"]
 
 VAD_OK = 0
 ABI_VERSION = 3
@@ -78,7 +78,8 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     flags = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", f"-I{REPO_DIR / 'include'}", f"-I{CSRC}"]
     # pack.cpp: the resize planner's doubles must round operation by operation (its function-level pragma says the same)
     # map_smooth.hip: every product and sum of the smoothing rounds on its own, so numpy float32 restates it bit for bit
-    extra = {"pack.cpp": ["-ffp-contract=off"], "map_smooth.hip": ["-ffp-contract=off"]}
+    # map_stats.hip: the float64 sums of the per-pixel statistics and the fp32 z-score likewise (tests/map_stats_ref.py)
+    extra = {"pack.cpp": ["-ffp-contract=off"], "map_smooth.hip": ["-ffp-contract=off"], "map_stats.hip": ["-ffp-contract=off"]}
 
     def compile_one(src: Path) -> Path:
         obj = objdir / (src.name + ".o")
@@ -300,6 +301,15 @@ SIGNATURES = {
     # defect regions of an anomaly map: boxes, areas, peaks (csrc/map_regions.hip)
     "vad_regions_workspace_bytes": (_sz, [_ll, _i, _i, _i]),
     "vad_detect_regions": (_i, [_vp, _ll, _i, _i, _f, _i, C.c_uint, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # per-pixel statistics of anomaly maps and the z-score map (csrc/map_stats.hip)
+    "vad_mapstat_state_bytes": (_sz, [_i, _i]),
+    "vad_mapstat_reset": (_i, [_vp, _i, _i, _vp]),
+    "vad_mapstat_accumulate": (_i, [_vp, _ll, _i, _i, _vp, _vp]),
+    "vad_mapstat_merge": (_i, [_vp, _vp, _i, _i, _vp]),
+    "vad_mapstat_finalize": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "vad_map_normalize_workspace_bytes": (_sz, [_ll, _i, _i]),
+    "vad_map_normalize": (_i, [_vp, _ll, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _sz, _vp]),
+    "vad_mapstat_plan": (_i, [C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "vad_graph_begin": (_i, [_vp]),
     "vad_graph_end": (_i, [_vp, C.POINTER(_vp)]),
     "vad_graph_launch": (_i, [_vp, _vp]),

@@ -23,6 +23,9 @@ scipy's Gaussian on the device and give the per-frame maximum of the smoothed ma
 
 The last part is what comes behind them on a deployed line: `detect_regions` (csrc/map_regions.hip) turns a map and an operating
 threshold into a table of connected regions per frame - box, area, peak, centroid sums - without a map leaving the device.
+
+Across all of them sits the calibration: `MapStatistics` (csrc/map_stats.hip) holds the per-pixel mean and standard deviation of the
+map over normal frames and turns a map into its z-score, which is then smoothed-and-ranked, thresholded and labelled like a raw map.
 """
 from __future__ import annotations
 
@@ -939,3 +942,218 @@ def detect_regions(maps: torch.Tensor, threshold: float, connectivity: int = 8, 
     _raise_on_flags(int(ws[:4].view(torch.int32).item()), what)
     return Regions(records.view(*lead, max_regions, REGION_WORDS), counts.view(*lead, 4),
                    labels.view(*lead, h, w) if return_labels else None, (h, w), float(np.float32(threshold)), connectivity, min_area)
+
+
+# ====================================================================== per-pixel calibration of anomaly maps
+# An autoencoder's error is not the same everywhere: on a fixed camera, edges, glossy patches and fine
+# texture reconstruct worse than flat background in every normal frame, so one global threshold either fires there all day or is
+# set so high that a defect on the background is missed.  Calibration on normal data: the per-pixel mean and standard deviation of
+# the map over the training frames, and z = (map - mean) / std in place of the map.  The host route is a copy of every training
+# map and numpy `mean` / `std` over N x H x W; here the maps never leave the device.
+_MS_MAGIC = 0x4d444156         # "VADM", csrc/map_stats.hip
+_MS_HEADER_BYTES = 32
+# The floor of the standard deviation: 2^-14 = 6.10e-5, the squared error of ONE grey level of an 8-bit input on the models' [-1, 1]
+# scale ((2 / 255)^2 = 6.15e-5) rounded to a power of two (the division by it is exact).  A pixel whose error varied by less than
+# that over the normal frames - a masked border, a saturated patch: std 0 - is treated as varying by one grey level, so rounding
+# noise there stays far below z = 1 and a real deviation still stands out.
+DEFAULT_MIN_STD = 2.0 ** -14
+
+
+def _check_min_std(min_std, what: str) -> float:
+    ok = not isinstance(min_std, bool) and isinstance(min_std, (int, float, np.integer, np.floating))
+    with np.errstate(over="ignore"):
+        v = np.float32(min_std) if ok else np.float32("nan")
+    if not (np.isfinite(v) and v > 0):                           # as float32: what the kernel divides by
+        raise hip.VadError(f"{what}: min_std must be a finite float32 greater than 0, got {min_std!r}")
+    return float(v)
+
+
+class MapStatistics:
+    """Per-pixel mean and standard deviation of anomaly maps over a stream of frames, in one device blob (include/vad_hip.h
+    `vad_mapstat_*`): a header with the geometry and the frame count, and three float64 planes K (the pixel's first value), S1 =
+    sum(x - K), S2 = sum((x - K)^2).  The arithmetic is fully specified (tests/map_stats_ref.py restates it bit for bit): every
+    frame is added in order, so the state does not depend on how the frames were batched.
+
+    `update(maps)` adds a batch on the GPU, asynchronously; `mean()` / `std(ddof)` are float32 `[H, W]` device tensors;
+    `normalize(maps)` is the z-score map (and its per-frame maxima); `merge`, `state_dict` / `load_state_dict` combine and carry
+    states.  `count` is the number of frames, tracked on the host as well so that a call that needs more frames than were seen is
+    refused with `ValueError`; `meta` records what kind of map was accumulated (`scoring.calibrate` fills it, the scoring drivers
+    compare it with their own arguments).  GPU only: there is no CPU fallback."""
+
+    def __init__(self, frame_shape, device="cuda"):
+        if not isinstance(frame_shape, (tuple, list)) or len(frame_shape) != 2 or any(
+                isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in frame_shape):
+            raise hip.VadError(f"MapStatistics: frame_shape must be (H, W), got {frame_shape!r}")
+        h, w = int(frame_shape[0]), int(frame_shape[1])
+        if h < 1 or w < 1 or h * w > hip.MAX_FRAME_PIXELS:
+            raise hip.VadError(f"MapStatistics: frames of {h} x {w} are out of range (H, W >= 1 and H * W <= {hip.MAX_FRAME_PIXELS})")
+        self.frame_shape = (h, w)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise hip.VadError(f"MapStatistics: device {self.device} is not a GPU (the statistics are gathered on the device; there is no CPU fallback)")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        nbytes = hip.lib().vad_mapstat_state_bytes(h, w)
+        assert nbytes == _MS_HEADER_BYTES + 24 * h * w
+        self._state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.meta = {}
+        self.reset()
+
+    # ------------------------------------------------------------------ state
+    def _planes(self) -> torch.Tensor:
+        """K, S1, S2 as one float64 view [3, H, W] of the blob."""
+        return self._state[_MS_HEADER_BYTES:].view(torch.float64).view(3, *self.frame_shape)
+
+    def reset(self) -> "MapStatistics":
+        h, w = self.frame_shape
+        with torch.cuda.device(self.device):
+            hip.check(hip.lib().vad_mapstat_reset(self._state.data_ptr(), h, w, hip.current_stream()), "vad_mapstat_reset")
+        self.count = 0
+        self._final = {}
+        return self
+
+    def device_count(self) -> int:
+        """The frame count of the device header (one 8-byte copy, which waits for the stream): what a replayed graph advanced."""
+        return int(self._state[16:24].view(torch.int64).item())
+
+    def state_dict(self) -> dict:
+        """{'frame_shape', 'count', 'K', 'S1', 'S2' float64 [H, W] on the host, 'meta'}: carry a calibration to another process."""
+        planes = self._planes().cpu()
+        return {"frame_shape": self.frame_shape, "count": self.device_count(), "K": planes[0].clone(), "S1": planes[1].clone(),
+                "S2": planes[2].clone(), "meta": dict(self.meta)}
+
+    def load_state_dict(self, state: dict) -> "MapStatistics":
+        if tuple(state.get("frame_shape", ())) != self.frame_shape:
+            raise hip.VadError(f"MapStatistics.load_state_dict: frame_shape {state.get('frame_shape')!r} of the saved state differs from "
+                               f"this object's {self.frame_shape}")
+        planes = [torch.as_tensor(np.asarray(state[k])) for k in ("K", "S1", "S2")]
+        if any(tuple(t.shape) != self.frame_shape or t.dtype != torch.float64 for t in planes):
+            raise hip.VadError(f"MapStatistics.load_state_dict: K, S1 and S2 must be float64 {self.frame_shape}")
+        count = int(state["count"])
+        if count < 0:
+            raise hip.VadError(f"MapStatistics.load_state_dict: count must not be negative, got {count}")
+        self.reset()
+        self._planes().copy_(torch.stack(planes))
+        self._state[16:24].view(torch.int64).fill_(count)
+        self.count = count
+        self.meta = dict(state.get("meta", {}))
+        return self
+
+    # ------------------------------------------------------------------ accumulate / combine
+    def _frames(self, maps: torch.Tensor, what: str) -> int:
+        """Checks a map batch [..., H, W]; -> the number of frames."""
+        if not isinstance(maps, torch.Tensor):
+            raise hip.VadError(f"{what}: maps must be a torch tensor")
+        if not maps.is_cuda:
+            raise hip.VadError(f"{what}: maps ({maps.device}) must be on the GPU (there is no CPU fallback)")
+        if maps.device != self.device:
+            raise hip.VadError(f"{what}: maps ({maps.device}) must be on the statistics' device {self.device}")
+        if maps.dtype != torch.float32:
+            raise hip.VadError(f"{what}: maps must be float32, got {maps.dtype}")
+        if maps.dim() < 2 or tuple(maps.shape[-2:]) != self.frame_shape:
+            raise ValueError(f"{what}: maps {tuple(maps.shape)} do not end in the frame shape {self.frame_shape} of the statistics")
+        if not maps.is_contiguous():
+            raise hip.VadError(f"{what}: maps must be contiguous (got strides {tuple(maps.stride())} for {tuple(maps.shape)}); it is not copied silently")
+        lead = tuple(maps.shape[:-2])
+        return int(np.prod(lead, dtype=np.int64)) if lead else 1
+
+    def update(self, maps: torch.Tensor) -> "MapStatistics":
+        """Add every H x W frame of `maps` (float32 GPU tensor, contiguous, any leading dimensions - `[B,1,H,W]` error / SSIM maps, the
+        `[B,T,1,H,W]` maps of the video model) in row-major order of the leading dimensions.  Asynchronous on the current stream."""
+        n = self._frames(maps, "MapStatistics.update")
+        if n == 0:
+            return self
+        h, w = self.frame_shape
+        with torch.cuda.device(self.device):
+            hip.check(hip.lib().vad_mapstat_accumulate(maps.data_ptr(), n, h, w, self._state.data_ptr(), hip.current_stream()),
+                      "vad_mapstat_accumulate")
+        hip.calls["mapstat_accumulate"] = hip.calls.get("mapstat_accumulate", 0) + 1
+        self.count += n
+        self._final = {}
+        return self
+
+    def merge(self, other: "MapStatistics") -> "MapStatistics":
+        """self += other, for statistics gathered separately (two streams, two loaders): as if other's frames had followed."""
+        if not isinstance(other, MapStatistics):
+            raise hip.VadError(f"MapStatistics.merge: other must be a MapStatistics, got {type(other).__name__}")
+        if other is self:
+            raise hip.VadError("MapStatistics.merge: other is this object")
+        if other.frame_shape != self.frame_shape:
+            raise ValueError(f"MapStatistics.merge: frame shapes differ ({self.frame_shape} and {other.frame_shape})")
+        if self.meta and other.meta and self.meta != other.meta:
+            raise ValueError(f"MapStatistics.merge: the statistics are of different maps ({self.meta} and {other.meta})")
+        if other.device != self.device:
+            raise hip.VadError(f"MapStatistics.merge: other ({other.device}) must be on this object's device {self.device}")
+        h, w = self.frame_shape
+        with torch.cuda.device(self.device):
+            hip.check(hip.lib().vad_mapstat_merge(self._state.data_ptr(), other._state.data_ptr(), h, w, hip.current_stream()),
+                      "vad_mapstat_merge")
+        self.count += other.count
+        self.meta = dict(self.meta or other.meta)
+        self._final = {}
+        return self
+
+    # ------------------------------------------------------------------ results
+    def _finalize(self, ddof: int):
+        """(mean, std) float32 [H, W] for `ddof`, computed once per state."""
+        if ddof not in self._final:
+            h, w = self.frame_shape
+            mean = torch.empty(self.frame_shape, dtype=torch.float32, device=self.device)
+            std = torch.empty(self.frame_shape, dtype=torch.float32, device=self.device)
+            with torch.cuda.device(self.device):
+                hip.check(hip.lib().vad_mapstat_finalize(self._state.data_ptr(), h, w, ddof, mean.data_ptr(), std.data_ptr(),
+                                                         hip.current_stream()), "vad_mapstat_finalize")
+            self._final[ddof] = (mean, std)
+        return self._final[ddof]
+
+    def _check_ddof(self, ddof, what: str) -> int:
+        if isinstance(ddof, bool) or not isinstance(ddof, (int, np.integer)) or int(ddof) not in (0, 1):
+            raise hip.VadError(f"{what}: ddof must be 0 or 1, got {ddof!r}")
+        if self.count - int(ddof) <= 0:
+            raise ValueError(f"{what}: {self.count} frames are not enough for a standard deviation with ddof={int(ddof)}")
+        return int(ddof)
+
+    def mean(self) -> torch.Tensor:
+        """float32 [H, W]: fl32(K + S1 / n); NaN everywhere before the first frame.  Do not write to it (it is kept)."""
+        return self._finalize(0 if self.count < 2 else 1)[0]
+
+    def std(self, ddof: int = 1) -> torch.Tensor:
+        """float32 [H, W]: sqrtf(fl32(max((S2 - S1^2 / n) / (n - ddof), 0))); `ValueError` when count - ddof <= 0.  Kept: do not write."""
+        return self._finalize(self._check_ddof(ddof, "MapStatistics.std"))[1]
+
+    def normalize(self, maps: torch.Tensor, min_std: float = DEFAULT_MIN_STD, out: Optional[torch.Tensor] = None, return_max=False,
+                  ddof: int = 1):
+        """z = (maps - mean) / max(std, min_std) of every frame on the GPU (`vad_map_normalize`), float32, each operation rounded on
+        its own; a pixel whose std is NaN (it saw a NaN or an Inf) gives NaN.  `maps` as in `update`.  Returns the z-score tensor
+        (written to `out` if given: same shape, float32, contiguous; `out=maps` normalises in place, a partly overlapping `out` is
+        refused); with `return_max=True` also the per-frame maxima in the leading shape (`torch.amax` semantics), with
+        `return_max="only"` just the maxima, and no map is written - the arguments of `smooth_maps`.  `ValueError` when
+        count - ddof <= 0.  Asynchronous on the current stream."""
+        what = "MapStatistics.normalize"
+        if not isinstance(return_max, bool) and return_max != "only":
+            raise hip.VadError(f"{what}: return_max must be False, True or 'only', got {return_max!r}")
+        min_std = _check_min_std(min_std, what)
+        n = self._frames(maps, what)
+        ddof = self._check_ddof(ddof, what)
+        only = return_max == "only"
+        if only and out is not None:
+            raise hip.VadError(f"{what}: return_max='only' writes no map; out must be None")
+        if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(maps.shape) or out.dtype != torch.float32
+                                or out.device != maps.device or not out.is_contiguous()):
+            raise hip.VadError(f"{what}: out must be a contiguous float32 tensor {tuple(maps.shape)} on {maps.device}")
+        lead, (h, w) = tuple(maps.shape[:-2]), self.frame_shape
+        mean, std = self._finalize(ddof)
+        with torch.cuda.device(self.device):
+            if out is None and not only:
+                out = torch.empty_like(maps)
+            fmax = torch.empty(lead, dtype=torch.float32, device=self.device) if return_max else None
+            if n > 0:
+                l = hip.lib()
+                need = l.vad_map_normalize_workspace_bytes(n, h, w) if return_max else 0
+                ws = torch.empty(need, dtype=torch.uint8, device=self.device) if need else None
+                hip.check(l.vad_map_normalize(maps.data_ptr(), n, h, w, mean.data_ptr(), std.data_ptr(), min_std, hip.ptr(out), hip.ptr(fmax),
+                                              hip.ptr(ws), need, hip.current_stream()), "vad_map_normalize")
+                hip.calls["map_normalize"] = hip.calls.get("map_normalize", 0) + 1
+        if only:
+            return fmax
+        return (out, fmax) if return_max else out

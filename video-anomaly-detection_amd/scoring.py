@@ -63,20 +63,28 @@ def compute_auroc(model, test_loader: Iterable[dict], device):
     return auroc, labels, scores, per_defect
 
 
-def compute_auroc_smoothed(model, test_loader: Iterable[dict], device, sigma: float = 4.0, truncate: float = 4.0, map: str = "mse"):
+def compute_auroc_smoothed(model, test_loader: Iterable[dict], device, sigma: float = 4.0, truncate: float = 4.0, map: str = "mse",
+                           calibration=None, min_std: Optional[float] = None):
     """`compute_auroc` with the image score of the published MVTec evaluations: the maximum of the Gaussian-smoothed anomaly map
     (`metrics.smooth_maps(..., return_max="only")`) instead of the mean squared error - a small defect on a large frame barely
     moves the mean.  Same batches, same 4-tuple; `map` as in `pixel_auroc`.  The maps stay on the device: a batch's scores are read
-    back once, as `compute_auroc` does."""
+    back once, as `compute_auroc` does.  `calibration`, `min_std` as in `pixel_auroc`: the score is the maximum of the z-score of the
+    smoothed map (the smoothed map is normalised, its maximum taken by the same call)."""
     from . import metrics
     if map not in ("mse", "ssim"):
         raise hip.VadError(f"compute_auroc_smoothed: map must be 'mse' or 'ssim', got {map!r}")
+    if calibration is not None:
+        min_std = _check_calibration(calibration, "compute_auroc_smoothed", map, sigma, truncate, min_std)
     all_labels, all_scores, all_types = [], [], []
     with torch.no_grad():
         for batch in test_loader:
             images = batch["image"].to(device)
             values = _anomaly_maps(model, images, map, None, truncate)
-            scores = metrics.smooth_maps(values, sigma, truncate, return_max="only").reshape(images.shape[0])
+            if calibration is None:
+                scores = metrics.smooth_maps(values, sigma, truncate, return_max="only").reshape(images.shape[0])
+            else:
+                values = metrics.smooth_maps(values, sigma, truncate)
+                scores = calibration.normalize(values, min_std, return_max="only").reshape(images.shape[0])
             all_scores.extend(scores.cpu().numpy())
             all_labels.extend(np.asarray(batch["label"]))
             all_types.extend(batch["defect_type"])
@@ -371,19 +379,72 @@ def score_stream(model, seed: int, n_frames: int, chunk: int = 512, h: int = 256
 
 
 # ------------------------------------------------------------------------------ ranking metrics on the device
-def _anomaly_maps(model, images, map: str, sigma, truncate):
+def _anomaly_maps(model, images, map: str, sigma, truncate, calibration=None, min_std=None):
     """The batch's anomaly map [B,1,H,W] of the pixel metrics: the error map or the SSIM map, through `metrics.smooth_maps` when a
-    sigma is given."""
+    sigma is given, then - with a `calibration` - turned into its z-score in place (the map is this call's own)."""
     from . import metrics
     if map == "mse":
         values = model.score_all(images)["errmap"]
     else:
         values = model.score_criteria(images, ssim_map=True)["ssim_map"]
-    return values if sigma is None else metrics.smooth_maps(values, sigma, truncate)
+    if sigma is not None:
+        values = metrics.smooth_maps(values, sigma, truncate)
+    if calibration is not None:
+        values = calibration.normalize(values, min_std, out=values)
+    return values
+
+
+def _map_meta(map: str, sigma, truncate) -> dict:
+    """What kind of map a calibration holds the statistics of: `MapStatistics.meta`."""
+    return {"map": map, "sigma": None if sigma is None else float(sigma), "truncate": float(truncate)}
+
+
+def _check_calibration(calibration, what: str, map: str, sigma, truncate, min_std) -> float:
+    """A calibration applies to the maps it was gathered on: `ValueError` for another map, sigma or truncate - thresholds on such
+    z-scores would be meaningless.  -> the min_std to use."""
+    from . import metrics
+    if not isinstance(calibration, metrics.MapStatistics):
+        raise hip.VadError(f"{what}: calibration must be a metrics.MapStatistics, got {type(calibration).__name__}")
+    want = _map_meta(map, sigma, truncate)
+    if calibration.meta != want:
+        raise ValueError(f"{what}: the calibration was gathered on {calibration.meta}, this call makes {want}")
+    return metrics.DEFAULT_MIN_STD if min_std is None else min_std
+
+
+def calibrate(model, loader: Iterable[dict], device, map: str = "mse", sigma=None, truncate: float = 4.0, stats=None):
+    """Per-pixel statistics of a model's anomaly map over NORMAL data - the train split; the reference trains on normal frames only
+    (utils/dataset.py, utils/video_dataset.py) -: the loop of `pixel_auroc` without masks.  Batches {'image' [B,C,H,W]} for the image
+    model, {'frames' [B,T,C,H,W]} for the video model (map "mse" only), where every frame of every clip goes into the same per-pixel
+    statistics.  `map`, `sigma`, `truncate` as in `pixel_auroc`.  Each batch is ONE scoring call, an optional smoothing call and ONE
+    `MapStatistics.update`; no map is copied to the host.  Returns the `metrics.MapStatistics` with `meta` = {map, sigma, truncate};
+    pass `stats` to continue one (its meta must be that of this call).  Hand the result to `pixel_auroc` / `pixel_aupro` /
+    `compute_auroc_smoothed` / `localize` as `calibration=`."""
+    from . import metrics
+    if map not in ("mse", "ssim"):
+        raise hip.VadError(f"calibrate: map must be 'mse' or 'ssim', got {map!r}")
+    meta = _map_meta(map, sigma, truncate)
+    if stats is not None:
+        if not isinstance(stats, metrics.MapStatistics):
+            raise hip.VadError(f"calibrate: stats must be a metrics.MapStatistics, got {type(stats).__name__}")
+        if stats.meta and stats.meta != meta:
+            raise ValueError(f"calibrate: stats was gathered on {stats.meta}, this call makes {meta}")
+    with torch.no_grad():
+        for batch in loader:
+            video = "frames" in batch
+            if video and map != "mse":
+                raise hip.VadError(f"calibrate: clips [B,T,C,H,W] are calibrated on the error map only (map='mse'), got {map!r}")
+            values = _anomaly_maps(model, batch["frames" if video else "image"].to(device), map, sigma, truncate)
+            if stats is None:
+                stats = metrics.MapStatistics(tuple(int(v) for v in values.shape[-2:]), values.device)
+            stats.update(values)
+    if stats is None:
+        raise ValueError("calibrate needs at least one batch")
+    stats.meta = meta
+    return stats
 
 
 def pixel_auroc(model, loader: Iterable[dict], device, map: str = "mse", mantissa_bits: int = 11, hist=None, sigma=None,
-                truncate: float = 4.0):
+                truncate: float = 4.0, calibration=None, min_std: Optional[float] = None):
     """Pixel-level AUROC of an image model's anomaly map against the ground-truth masks - the localisation metric of MVTec-style
     datasets; the reference loads `sample['mask']` and only plots it beside the map (evaluate.py:142-171).  Batches are
     {'image', 'mask', ...} as `MVTecDataset` yields them (utils/dataset.py:150-156): mask float `[B,1,H,W]` (ToTensor: a pixel is
@@ -396,23 +457,30 @@ def pixel_auroc(model, loader: Iterable[dict], device, map: str = "mse", mantiss
     `gaussian_filter`, sigma = 4 in the published MVTec evaluations - still on the device.
     Each batch is ONE scoring call and ONE `accumulate`; no map is copied to the host - the only host read is the counters, once,
     at the end.  Returns (auroc, tie_bound, hist) (`metrics.auroc_from_counts`); pass `hist` to continue an earlier evaluation or
-    to all-reduce before reading (`hist.all_reduce()`), in which case its own mantissa_bits applies."""
+    to all-reduce before reading (`hist.all_reduce()`), in which case its own mantissa_bits applies.
+    `calibration` (None = the map as it stands, as before): a `metrics.MapStatistics` from `calibrate` with the same `map`, `sigma`
+    and `truncate` (`ValueError` otherwise, or for another frame shape) - the map is turned into its per-pixel z-score
+    (`MapStatistics.normalize`, floor `min_std`, default `metrics.DEFAULT_MIN_STD`) after the smoothing and before the histogram, in
+    place, still on the device.  The histogram bins values >= 0: z-scores below 0 - pixels less anomalous than on the normal frames'
+    average - are counted in `hist.rejected()`, so the curve and its thresholds are those of the z-scores above 0."""
     from . import metrics
     if map not in ("mse", "ssim"):
         raise hip.VadError(f"pixel_auroc: map must be 'mse' or 'ssim', got {map!r}")
+    if calibration is not None:
+        min_std = _check_calibration(calibration, "pixel_auroc", map, sigma, truncate, min_std)
     if hist is None:
         hist = metrics.ScoreHistogram(mantissa_bits, device)
     with torch.no_grad():
         for batch in loader:
             images = batch["image"].to(device)
             masks = torch.as_tensor(batch["mask"]).to(device)
-            hist.accumulate(_anomaly_maps(model, images, map, sigma, truncate), masks)
+            hist.accumulate(_anomaly_maps(model, images, map, sigma, truncate, calibration, min_std), masks)
     auroc, tie_bound = hist.auroc()
     return auroc, tie_bound, hist
 
 
 def pixel_aupro(model, loader: Iterable[dict], device, map: str = "mse", fpr_limit: float = 0.3, mantissa_bits: int = 11, hist=None,
-                connectivity: int = 8, sigma=None, truncate: float = 4.0):
+                connectivity: int = 8, sigma=None, truncate: float = 4.0, calibration=None, min_std: Optional[float] = None):
     """Per-region overlap (AUPRO) of an image model's anomaly map against the ground-truth masks: every connected anomalous region
     of the masks weighs the same, and the curve is integrated up to a false-positive rate of `fpr_limit` - the localisation metric
     of the MVTec evaluation, where pixel AUROC is dominated by the large defects.  The loop of `pixel_auroc` (same batches, same
@@ -420,17 +488,20 @@ def pixel_aupro(model, loader: Iterable[dict], device, map: str = "mse", fpr_lim
     call and ONE `ProHistogram.accumulate`, which labels the masks' regions and adds the counters
     on the device; the only host read is the counters, once, at the end.  Returns (aupro, quant_bound, weight_bound, hist)
     (`metrics.aupro_from_counts`); pass `hist` to continue an earlier evaluation or to all-reduce before reading, in which case
-    its own mantissa_bits and connectivity apply.  `hist.auroc()` is the pixel AUROC of the same evaluation."""
+    its own mantissa_bits and connectivity apply.  `hist.auroc()` is the pixel AUROC of the same evaluation.  `calibration`,
+    `min_std` as in `pixel_auroc`."""
     from . import metrics
     if map not in ("mse", "ssim"):
         raise hip.VadError(f"pixel_aupro: map must be 'mse' or 'ssim', got {map!r}")
+    if calibration is not None:
+        min_std = _check_calibration(calibration, "pixel_aupro", map, sigma, truncate, min_std)
     if hist is None:
         hist = metrics.ProHistogram(mantissa_bits, device, connectivity)
     with torch.no_grad():
         for batch in loader:
             images = batch["image"].to(device)
             masks = torch.as_tensor(batch["mask"]).to(device)
-            hist.accumulate(_anomaly_maps(model, images, map, sigma, truncate), masks)
+            hist.accumulate(_anomaly_maps(model, images, map, sigma, truncate, calibration, min_std), masks)
     aupro, quant_bound, weight_bound = hist.aupro(fpr_limit)
     return aupro, quant_bound, weight_bound, hist
 
@@ -453,19 +524,23 @@ def frame_auroc(model, loader: Iterable[dict], device, hist=None, mantissa_bits:
 
 
 def localize(model, images, threshold: float, map: str = "mse", sigma=None, truncate: float = 4.0, connectivity: int = 8,
-             min_area: int = 1, max_regions: int = 64):
+             min_area: int = 1, max_regions: int = 64, calibration=None, min_std: Optional[float] = None):
     """Detections of one batch: the model's anomaly maps and the connected regions of `map >= threshold` in them - where the
     reference paints the map (evaluate.py:142-171, main.py:231-250) and compares one scalar with a constant (main.py:282-283).
     `images`: `[B,C,H,W]` frames for the image model, `[B,T,C,H,W]` clips for the video model (map "mse" only; every frame of a
     clip is labelled on its own).  `map`, `sigma`, `truncate` as in `pixel_auroc`, so a threshold taken from its histogram
     (`metrics.threshold_at_fpr`, `best_f1_threshold`) applies as it stands.  Per batch ONE scoring call, an optional smoothing call
     and ONE `metrics.detect_regions` call; nothing but the flag word is read by the host.  Returns (`metrics.Regions`, maps): the
-    table with the leading shape `[B]` / `[B,T]`, and the maps it was made from, `[B,1,H,W]` / `[B,T,1,H,W]`, still on the device."""
+    table with the leading shape `[B]` / `[B,T]`, and the maps it was made from, `[B,1,H,W]` / `[B,T,1,H,W]`, still on the device.
+    `calibration`, `min_std` as in `pixel_auroc`: `threshold` is then a z-score (3.0 = three standard deviations of that pixel over
+    the normal frames), the regions are those of `z >= threshold`, and the maps returned are the z-score maps."""
     from . import metrics
     if map not in ("mse", "ssim"):
         raise hip.VadError(f"localize: map must be 'mse' or 'ssim', got {map!r}")
     if images.dim() == 5 and map != "mse":
         raise hip.VadError(f"localize: clips [B,T,C,H,W] are localised on the error map only (map='mse'), got {map!r}")
+    if calibration is not None:
+        min_std = _check_calibration(calibration, "localize", map, sigma, truncate, min_std)
     with torch.no_grad():
-        maps = _anomaly_maps(model, images, map, sigma, truncate)
+        maps = _anomaly_maps(model, images, map, sigma, truncate, calibration, min_std)
         return metrics.detect_regions(maps, threshold, connectivity, min_area, max_regions), maps
