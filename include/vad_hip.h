@@ -879,6 +879,56 @@ int vad_detect_regions(const float* maps, long long n, int h, int w, float thres
                        int max_regions, int32_t* labels_or_null, uint32_t* records /* [n, max_regions, 12] */,
                        uint32_t* counts /* [n, 4] */, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ Anomaly events of a clip (csrc/map_events.hip)
+ * Regions linked across the frames of a clip: an event is a connected component of {v >= threshold} in the volume [t, h, w] of one
+ * clip.  The predicate is the one of vad_detect_regions (a NaN pixel never is foreground and is counted, +Inf always is, a NaN
+ * threshold is refused).  Inside a frame pixels connect as there (connectivity 8 or 4); between consecutive frames
+ *     temporal 1   (t, y, x) links to (t-1, y, x)
+ *     temporal 9   (t, y, x) links to every foreground pixel of the 3 x 3 around (y, x) in frame t-1; connectivity 8 only
+ * so (4, 1), (8, 1) and (8, 9) are scipy.ndimage.label's 6-structure, its 3 x 3 centre plane with single-pixel outer planes, and
+ * its 26-structure.  Frames of different clips never link, nor do rows of different frames.  An event has no gaps in time.
+ *
+ * vad_detect_events: maps = b clips of t frames of h x w fp32, contiguous, 4-byte aligned; h, w, t >= 1, t * h * w < 2^31 - 1 (a
+ * volume index fits the int32 label plane), b * t * h * w <= 2^38.  The root of an event is the smallest volume index
+ * t * h * w + y * w + x of its pixels.  labels_or_null int32 [b, t, h, w], when given, receives 0 or 1 + root for every foreground
+ * pixel, whether its event passes the filters or not.
+ * records uint32 [b, max_events, VAD_EVENT_WORDS], 16-byte aligned; one event is
+ *     word 0       root
+ *     word 1       volume in pixels
+ *     words 2-3    t0, t1: first and last frame, inclusive
+ *     words 4-7    x0, y0, x1, y1 of the union of its frames' boxes, inclusive
+ *     word 8       peak: the float bits of the event's maximum
+ *     word 9       peak index: the smallest volume index among the pixels that hold the maximum
+ *     words 10-11  uint64 sum of x over the event's pixels      (centroid = sum / volume, exactly)
+ *     words 12-13  uint64 sum of y
+ *     words 14-15  uint64 sum of t
+ * Values compare through the order-preserving key of their bits, so -0.0 < +0.0.  The events with t1 - t0 + 1 >= min_duration
+ * (>= 1) and volume >= min_volume (>= 1) are kept, in ascending order of their roots - scipy.ndimage.label's numbering of a 3-D
+ * array -, and the first min(kept, max_events) are written (max_events in 1 .. 65536); every other record of the clip is all-zero.
+ * counts uint32 [b, 4]: kept (the full number, which may exceed max_events), dropped by a filter, foreground pixels, NaN pixels.
+ * frame_counts uint32 [b, t, 3]: foreground pixels of the frame, pixels of the frame that belong to KEPT events (whether or not
+ * the event has a record: the word does not depend on max_events; the frame alarms iff it is non-zero), NaN pixels of the frame.
+ * Integer atomics, min and max only: every output is the same words for any batching of clips, launch order or tiling.
+ * Every walk of the union-find is bounded by a number known at launch (2 * t * h * w + 2 steps); one that runs out of it sets the
+ * flag word - the first uint32 of ws - and leaves.
+ * ws: caller-provided, 16-byte aligned, vad_events_workspace_bytes(b, t, h, w, labels_given) bytes (0 for arguments out of range;
+ * no device is needed): 16 bytes for the flag word, 4 bytes per chunk of 1024 pixels of every clip (padded to 16), then 4 bytes
+ * per pixel each for event sizes and for last frames / record slots and, with labels_given = 0, for the label plane.
+ * vad_events_plan reports the pixels one grid round of each pass covers (the labeller inside a frame; rebase, link and flatten
+ * over a clip's volume; the count / slot scan; the reduction) and the threads of a work-group - what a test needs to build a
+ * volume that is larger than one round of every pass.
+ * VAD_ERR_ARG for a NULL or misaligned pointer, b, t, h, w out of range, a connectivity other than 4 or 8, a temporal other than 1
+ * or 9, temporal 9 with connectivity 4, min_duration == 0, min_volume == 0, max_events out of range and a NaN threshold;
+ * VAD_ERR_WS for a short workspace.  b == 0 clears the flag word only.  Every launch is asynchronous on `stream`; nothing is
+ * allocated, the host never waits, the call can be captured into a graph. */
+#define VAD_EVENT_WORDS 16
+size_t vad_events_workspace_bytes(long long b, int t, int h, int w, int labels_given);
+int vad_detect_events(const float* maps, long long b, int t, int h, int w, float threshold, int connectivity, int temporal,
+                      unsigned min_duration, unsigned min_volume, int max_events, int32_t* labels_or_null,
+                      uint32_t* records /* [b, max_events, 16] */, uint32_t* counts /* [b, 4] */,
+                      uint32_t* frame_counts /* [b, t, 3] */, void* ws, size_t ws_bytes, void* stream);
+int vad_events_plan(int* label_round, int* volume_round, int* scan_round, int* reduce_round, int* threads);
+
 /* ------------------------------------------------------------------ Per-pixel calibration of anomaly maps (csrc/map_stats.hip)
  * The mean and standard deviation of every pixel of the anomaly map over the normal (training) frames, and the z-score map
  * z = (map - mean) / std that is ranked, thresholded and labelled in place of the raw map.  The maps stay on the device.

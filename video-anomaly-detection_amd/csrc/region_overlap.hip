@@ -34,10 +34,11 @@ constexpr unsigned PRO_MAGIC = 0x50444156u;    // "VADP"
 constexpr int PRO_TAIL_WORDS = 5;              // regions, max_region, rejected[2], flags
 constexpr int LABEL_THREADS = 256;
 constexpr unsigned LABEL_MAX_BLOCKS_X = 4096;
-constexpr unsigned LABEL_FLAG_WALK = 1u;       // a root chase or a union ran out of its step budget
+constexpr unsigned LABEL_FLAG_WALK = VAD_LABEL_FLAG_WALK;   // a root chase or a union ran out of its step budget
 constexpr unsigned LABEL_FLAG_SIZE = 2u;       // an anomalous pixel's region has size 0 (the label planes are not a labelling)
 constexpr long long PRO_MAX_ELEMS = 1ll << 38; // n * h * w of one call: a work-group's run of a 256-group launch stays below 2^32
 constexpr size_t WS_HEAD_BYTES = VAD_LABEL_WS_HEAD_BYTES;
+static_assert(LABEL_MAX_BLOCKS_X * LABEL_THREADS == VAD_LABEL_ROUND_PIXELS, "region_label.h reports the labeller's grid round");
 
 __device__ __forceinline__ bool pro_header_ok(const unsigned* hdr, int m) {
     return hdr[0] == PRO_MAGIC && hdr[1] == hist_tag(m) && hdr[2] == (unsigned)m;
@@ -54,45 +55,7 @@ struct LabelP {
     float threshold;         // VAD_LABEL_FMT_F32_GE only
 };
 
-__device__ __forceinline__ int label_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// The root of x (indices inside one image; L[x] = parent + 1).  At most `budget` steps, each to a smaller index.  A parent that is
-// not a smaller index (the plane is not a union-find: never, short of a defect) ends the walk with the budget spent - no address
-// is ever formed from it.
-__device__ __forceinline__ unsigned label_find(const int* L, unsigned x, unsigned& budget) {
-    while (budget != 0u) {
-        const unsigned parent = (unsigned)label_load(L + x) - 1u;
-        if (parent == x) break;
-        if (parent > x) {
-            budget = 0u;
-            break;
-        }
-        x = parent;
-        --budget;
-    }
-    return x;
-}
-
-// Unite the sets of a and b.  Returns false when the budget ran out.
-__device__ __forceinline__ bool label_union(int* L, unsigned a, unsigned b, unsigned budget) {
-    while (budget != 0u) {
-        a = label_find(L, a, budget);
-        b = label_find(L, b, budget);
-        if (a == b) return budget != 0u;
-        if (a < b) {
-            const unsigned t = a;
-            a = b;
-            b = t;
-        }
-        if (budget == 0u) break;
-        const unsigned old = (unsigned)atomicMin(L + a, (int)(b + 1u)) - 1u;
-        if (old == a) return true;                           // a was a root and now hangs below b
-        if (old > a) break;                                  // not a union-find plane (see label_find)
-        a = old;                                            // another thread gave a a parent first (old < a): unite that with b
-        --budget;
-    }
-    return false;
-}
+// label_load, label_find, label_union - the bounded walks - live in region_label.h: csrc/map_events.hip unites with them too
 
 __global__ __launch_bounds__(LABEL_THREADS) void label_init_kernel(LabelP p) {
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) p.flags[0] = 0u;

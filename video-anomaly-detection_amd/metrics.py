@@ -22,7 +22,8 @@ The third part is what goes in front of both: `gaussian_taps` / `smooth_maps` (c
 scipy's Gaussian on the device and give the per-frame maximum of the smoothed map, the image score of the MVTec evaluation.
 
 The last part is what comes behind them on a deployed line: `detect_regions` (csrc/map_regions.hip) turns a map and an operating
-threshold into a table of connected regions per frame - box, area, peak, centroid sums - without a map leaving the device.
+threshold into a table of connected regions per frame - box, area, peak, centroid sums - without a map leaving the device; `detect_events` (csrc/map_events.hip) links those regions across the frames of a
+clip into events - first and last frame, union box, peak, volume - and counts per frame the pixels of the events that persist.
 
 Across all of them sits the calibration: `MapStatistics` (csrc/map_stats.hip) holds the per-pixel mean and standard deviation of the
 map over normal frames and turns a map into its z-score, which is then smoothed-and-ranked, thresholded and labelled like a raw map.
@@ -942,6 +943,155 @@ def detect_regions(maps: torch.Tensor, threshold: float, connectivity: int = 8, 
     _raise_on_flags(int(ws[:4].view(torch.int32).item()), what)
     return Regions(records.view(*lead, max_regions, REGION_WORDS), counts.view(*lead, 4),
                    labels.view(*lead, h, w) if return_labels else None, (h, w), float(np.float32(threshold)), connectivity, min_area)
+
+
+# ====================================================================== anomaly events of a clip
+# Nobody alarms on a single-frame blob: regions that overlap from frame to frame are one event, and a line
+# alarms on the events that last.  An event is a connected component of `map >= threshold` in the volume [T,H,W] of one clip; the
+# host route is a copy of every map of the clip and scipy.ndimage.label with a 3-D structure, find_objects and maximum_position.
+EVENT_WORDS = hip.EVENT_WORDS
+MAX_EVENTS = hip.MAX_EVENTS
+
+
+class Events:
+    """The table `detect_events` returns, as device tensors with the leading shape of the clips (`[B]`, or `()` for one clip):
+
+      records       int32 [..., E, 16]: the words of `vad_detect_events` (include/vad_hip.h), E = max_events; the kept events of a
+                    clip in ascending order of their first voxel, all-zero records behind them
+      counts        int32 [..., 4]: kept events (the full number: above E the table is truncated), events dropped by a filter,
+                    foreground pixels, NaN pixels
+      frame_counts  int32 [..., T, 3]: foreground pixels of the frame, pixels of the frame that belong to kept events (whether or
+                    not the event has a record: independent of max_events), NaN pixels of the frame
+      labels        int32 [..., T, H, W] or None: 0, or 1 + root, for ALL foreground pixels (with `return_labels=True`)
+
+    Views of `records` (no copies): `root`, `volume`, `t0`, `t1`, `peak_index` int32 [..., E]; `box` int32 [..., E, 4] = x0, y0, x1,
+    y1 inclusive, the union over the event's frames; `peak` float32 [..., E]; `sum_x`, `sum_y`, `sum_t` int64 [..., E].  A root or a
+    peak index is a volume index t * H * W + y * W + x."""
+
+    def __init__(self, records: torch.Tensor, counts: torch.Tensor, frame_counts: torch.Tensor, labels: Optional[torch.Tensor],
+                 volume_shape: Tuple[int, int, int], threshold: float, connectivity: int, temporal: int, min_duration: int, min_volume: int):
+        self.records, self.counts, self.frame_counts, self.labels = records, counts, frame_counts, labels
+        self.volume_shape, self.threshold, self.connectivity, self.temporal = volume_shape, threshold, connectivity, temporal
+        self.min_duration, self.min_volume = min_duration, min_volume
+        self.max_events = int(records.shape[-2])
+
+    root = property(lambda self: self.records[..., 0])
+    volume = property(lambda self: self.records[..., 1])
+    t0 = property(lambda self: self.records[..., 2])
+    t1 = property(lambda self: self.records[..., 3])
+    box = property(lambda self: self.records[..., 4:8])
+    peak = property(lambda self: self.records[..., 8].view(torch.float32))
+    peak_index = property(lambda self: self.records[..., 9])
+    sum_x = property(lambda self: self.records[..., 10:12].view(torch.int64)[..., 0])
+    sum_y = property(lambda self: self.records[..., 12:14].view(torch.int64)[..., 0])
+    sum_t = property(lambda self: self.records[..., 14:16].view(torch.int64)[..., 0])
+
+    def durations(self) -> torch.Tensor:
+        """int32 [..., E]: t1 - t0 + 1 of the records in use, 0 for the all-zero records behind them."""
+        return torch.where(self.volume > 0, self.t1 - self.t0 + 1, torch.zeros_like(self.t1))
+
+    def centroids(self) -> torch.Tensor:
+        """float64 [..., E, 3] on the device: (t, y, x) = sums / volume, each quotient rounded once; NaN for the all-zero records."""
+        volume = self.volume.to(torch.float64)
+        return torch.stack([s.to(torch.float64) / volume for s in (self.sum_t, self.sum_y, self.sum_x)], dim=-1)
+
+    def alarms(self) -> torch.Tensor:
+        """bool [..., T]: the frame holds a pixel of a kept event - the debounced alarm signal; it does not depend on max_events."""
+        return self.frame_counts[..., 1] > 0
+
+    def truncated(self) -> torch.Tensor:
+        """bool [...]: the clip has more kept events than the table has records."""
+        return self.counts[..., 0] > self.max_events
+
+    def to_list(self) -> list:
+        """A host copy of the table - 64 bytes per record, never a map -: one list per clip (clips in order) of {'root', 'volume',
+        't0', 't1', 'duration', 'box': (x0, y0, x1, y1), 'peak', 'peak_tyx', 'centroid_tyx'} in table order."""
+        _, h, w = self.volume_shape
+        rec = self.records.reshape(-1, self.max_events, EVENT_WORDS).cpu().numpy()
+        kept = self.counts.reshape(-1, 4)[:, 0].cpu().numpy()
+        out = []
+        for c in range(rec.shape[0]):
+            rows = []
+            for r in rec[c, :min(int(kept[c]), self.max_events)]:
+                volume = int(r[1])
+                sx, sy, st = (int(v) for v in r[10:16].copy().view(np.int64))
+                pt, pp = divmod(int(r[9]), h * w)
+                rows.append({"root": int(r[0]), "volume": volume, "t0": int(r[2]), "t1": int(r[3]), "duration": int(r[3]) - int(r[2]) + 1,
+                             "box": tuple(int(v) for v in r[4:8]), "peak": float(r[8:9].copy().view(np.float32)[0]),
+                             "peak_tyx": (pt, *divmod(pp, w)), "centroid_tyx": (st / volume, sy / volume, sx / volume)})
+            out.append(rows)
+        return out
+
+
+def detect_events(maps: torch.Tensor, threshold: float, connectivity: int = 8, temporal: int = 9, min_duration: int = 1,
+                  min_volume: int = 1, max_events: int = 64, return_labels: bool = False) -> Events:
+    """The events of every clip, on the GPU (`vad_detect_events`, csrc/map_events.hip): the connected components of `maps >=
+    threshold` in the volume `[T,H,W]` - the regions of `detect_regions` linked across consecutive frames.  `maps`: float32 GPU
+    tensor `[T,H,W]` (one clip), `[B,T,H,W]` or `[B,T,1,H,W]` (the video model's maps); clips never link.  Inside a frame pixels
+    connect as in `label_regions` (connectivity 8 or 4); `temporal` 1 links (t, y, x) to (t-1, y, x), `temporal` 9 to the set pixels
+    of the 3 x 3 around it in frame t-1 (connectivity 8 only): (4, 1), (8, 1), (8, 9) are scipy.ndimage.label's 3-D structures
+    `generate_binary_structure(3, 1)`, the full centre plane with single-pixel outer planes, and `generate_binary_structure(3, 3)`.
+    Events that last at least `min_duration` frames and have at least `min_volume` pixels are kept, in ascending order of their
+    first voxel (scipy's numbering), the first `max_events` (1..65536) written.  Returns an `Events`; like `detect_regions` it reads
+    the kernels' flag word (one 4-byte copy, which waits for the call) and raises VadError if it is set.  No CPU fallback."""
+    what = "detect_events"
+    connectivity = _check_connectivity(connectivity, what)
+    if isinstance(temporal, bool) or not isinstance(temporal, (int, np.integer)) or int(temporal) not in (1, 9):
+        raise hip.VadError(f"{what}: temporal must be 1 or 9, got {temporal!r}")
+    temporal = int(temporal)
+    if temporal == 9 and connectivity != 8:
+        raise hip.VadError(f"{what}: temporal=9 (the 3 x 3 of the frame before) needs connectivity=8, got connectivity={connectivity}")
+    if not isinstance(maps, torch.Tensor):
+        raise hip.VadError(f"{what}: maps must be a torch tensor")
+    if not maps.is_cuda:
+        raise hip.VadError(f"{what}: maps ({maps.device}) must be on the GPU (events are detected on the device; there is no CPU fallback)")
+    if maps.dtype != torch.float32:
+        raise hip.VadError(f"{what}: maps must be float32, got {maps.dtype}")
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)) or np.isnan(threshold):
+        raise hip.VadError(f"{what}: threshold must be a number that is not NaN, got {threshold!r}")
+    for name, v, hi in (("min_duration", min_duration, 2 ** 32 - 1), ("min_volume", min_volume, 2 ** 32 - 1), ("max_events", max_events, MAX_EVENTS)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= hi:
+            raise hip.VadError(f"{what}: {name} must be an int in 1..{hi}, got {v!r}")
+    min_duration, min_volume, max_events = int(min_duration), int(min_volume), int(max_events)
+    if maps.dim() == 3:
+        lead = ()
+    elif maps.dim() == 4 or (maps.dim() == 5 and maps.shape[2] == 1):
+        lead = (int(maps.shape[0]),)
+    else:
+        raise hip.VadError(f"{what}: maps must be [T,H,W], [B,T,H,W] or [B,T,1,H,W], got {tuple(maps.shape)}")
+    t, h, w = int(maps.shape[-4] if maps.dim() == 5 else maps.shape[-3]), int(maps.shape[-2]), int(maps.shape[-1])
+    if t < 1 or h < 1 or w < 1:
+        raise hip.VadError(f"{what}: clips of {t} x {h} x {w} are out of range (T, H, W >= 1)")
+    clips = maps.reshape(-1, t, h, w).contiguous()
+    b = int(clips.shape[0])
+    thr = float(np.float32(threshold))
+    dev = clips.device
+
+    def result(records, counts, frame_counts, labels):
+        return Events(records.view(*lead, max_events, EVENT_WORDS), counts.view(*lead, 4), frame_counts.view(*lead, t, 3),
+                      labels.view(*lead, t, h, w) if labels is not None else None, (t, h, w), thr, connectivity, temporal, min_duration,
+                      min_volume)
+
+    if b == 0:                                                            # nothing to detect, nothing to launch
+        return result(torch.zeros((0, max_events, EVENT_WORDS), dtype=torch.int32, device=dev), torch.zeros((0, 4), dtype=torch.int32, device=dev),
+                      torch.zeros((0, t, 3), dtype=torch.int32, device=dev),
+                      torch.zeros((0, t, h, w), dtype=torch.int32, device=dev) if return_labels else None)
+    with torch.cuda.device(dev):
+        l = hip.lib()
+        size = l.vad_events_workspace_bytes(b, t, h, w, 1 if return_labels else 0)
+        if size == 0:
+            raise hip.VadError(f"{what}: {b} clips of {t} x {h} x {w} are out of range (t * h * w < 2^31 - 1, b * t * h * w <= 2^38)")
+        ws = torch.empty(size, dtype=torch.uint8, device=dev)
+        records = torch.empty((b, max_events, EVENT_WORDS), dtype=torch.int32, device=dev)
+        counts = torch.empty((b, 4), dtype=torch.int32, device=dev)
+        frame_counts = torch.empty((b, t, 3), dtype=torch.int32, device=dev)
+        labels = torch.empty((b, t, h, w), dtype=torch.int32, device=dev) if return_labels else None
+        hip.check(l.vad_detect_events(clips.data_ptr(), b, t, h, w, thr, connectivity, temporal, min_duration, min_volume, max_events,
+                                      hip.ptr(labels), records.data_ptr(), counts.data_ptr(), frame_counts.data_ptr(), ws.data_ptr(),
+                                      ws.numel(), hip.current_stream()), "vad_detect_events")
+    hip.calls["detect_events"] = hip.calls.get("detect_events", 0) + 1
+    _raise_on_flags(int(ws[:4].view(torch.int32).item()), what)
+    return result(records, counts, frame_counts, labels)
 
 
 # ====================================================================== per-pixel calibration of anomaly maps

@@ -544,3 +544,26 @@ def localize(model, images, threshold: float, map: str = "mse", sigma=None, trun
     with torch.no_grad():
         maps = _anomaly_maps(model, images, map, sigma, truncate, calibration, min_std)
         return metrics.detect_regions(maps, threshold, connectivity, min_area, max_regions), maps
+
+
+def localize_events(model, images, threshold: float, map: str = "mse", sigma=None, truncate: float = 4.0, calibration=None,
+                    min_std: Optional[float] = None, connectivity: int = 8, temporal: int = 9, min_duration: int = 1, min_volume: int = 1,
+                    max_events: int = 64):
+    """`localize` with the event table: the model's anomaly maps and the events of `map >= threshold` in them - regions linked
+    across consecutive frames (`metrics.detect_events`), so that a line alarms on what persists (`min_duration`) and not on one
+    noisy map.  `images`: `[B,T,C,H,W]` clips for the video model (map "mse" only), every clip its own volume; `[N,C,H,W]` frames
+    for the image model, the batch in order being N consecutive frames of one camera: one volume.  `map`, `sigma`, `truncate`,
+    `calibration`, `min_std` as in `localize`.  Per batch ONE scoring call, the optional smoothing and calibration calls and ONE
+    `detect_events` call; nothing but the flag word is read by the host.  Returns (`metrics.Events`, maps): the table with the
+    leading shape `[B]` (video) or `()` (image), and the maps it was made from, `[B,T,1,H,W]` / `[N,1,H,W]`, still on the device."""
+    from . import metrics
+    if map not in ("mse", "ssim"):
+        raise hip.VadError(f"localize_events: map must be 'mse' or 'ssim', got {map!r}")
+    if images.dim() == 5 and map != "mse":
+        raise hip.VadError(f"localize_events: clips [B,T,C,H,W] are localised on the error map only (map='mse'), got {map!r}")
+    if calibration is not None:
+        min_std = _check_calibration(calibration, "localize_events", map, sigma, truncate, min_std)
+    with torch.no_grad():
+        maps = _anomaly_maps(model, images, map, sigma, truncate, calibration, min_std)
+        volumes = maps if maps.dim() == 5 else maps[:, 0]                 # [B,T,1,H,W], or the image batch as one clip [N,H,W]
+        return metrics.detect_events(volumes, threshold, connectivity, temporal, min_duration, min_volume, max_events), maps
