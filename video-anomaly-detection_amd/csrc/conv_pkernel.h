@@ -179,8 +179,11 @@ __global__ __launch_bounds__(256, (FUSE_C3 && !PREC) ? 3 : 2) void conv3x3_mfma_
 
     const int nch_a = p.cin_a / CK;
     const int nch = (p.in2 ? p.cin : p.cin_a) / CK;
-    const unsigned wstep = (unsigned)p.cout * (PREC ? 64u : 32u);  // bytes per (tap, k-step) slab
-    const unsigned wtap = (unsigned)(p.cin / KS) * wstep;          // bytes per tap
+    // (exact-fp32 fused first layer: cin = cout = 32 by construction, so every weight offset is an immediate and none sits in
+    // a scalar register across the frame loop)
+    constexpr bool C32 = FUSE_C3 && !PREC;
+    const unsigned wstep = C32 ? 32u * 32u : (unsigned)p.cout * (PREC ? 64u : 32u);   // bytes per (tap, k-step) slab
+    const unsigned wtap = C32 ? (unsigned)(32 / KS) * 32u * 32u : (unsigned)(p.cin / KS) * wstep;   // bytes per tap
     const __amdgpu_buffer_rsrc_t rw = vad_rsrc(p.w, (p.stagger & 1) ? 0u : 9u * wtap);   // stagger bit 0 (debug): price the weight traffic
 
     // staging slots: slot i of this thread is float4 (or float) number tid + 256 i of the staged tile.
@@ -269,7 +272,7 @@ __global__ __launch_bounds__(256, (FUSE_C3 && !PREC) ? 3 : 2) void conv3x3_mfma_
             const int lx_ = idx_ % XW, t_ = idx_ / XW;   /* t = c * XH + ly */                           \
             float xv_ = pf_get_f(pf[i_]);                                                                \
             if (p.xu8) xv_ = svo[i_] == VAD_OOB ? 0.f : vad_norm_u8(__float_as_uint(xv_));               \
-            if (idx_ < TOT) (xb_)[t_ * XS + lx_] = xv_;                                                  \
+            if (256 * (i_ + 1) <= TOT || idx_ < TOT) (xb_)[t_ * XS + lx_] = xv_;   /* only the last slot is partial */ \
         }                                                                                                \
     }
 
@@ -343,6 +346,7 @@ __global__ __launch_bounds__(256, (FUSE_C3 && !PREC) ? 3 : 2) void conv3x3_mfma_
     f16x8 b0h[(FUSE_C3 && PREC) ? 2 : 1], b0l[(FUSE_C3 && PREC) ? 2 : 1];
     float bias0 = 0.f;
     bool interior = false;
+    unsigned zflag = 0u;
     if constexpr (FUSE_C3) {
         if constexpr (PREC) {
             const f32x4* ws = (const f32x4*)(p.w0 + 28 * 32);          // split-fp16 copy of the first-layer weights
@@ -359,6 +363,19 @@ __global__ __launch_bounds__(256, (FUSE_C3 && !PREC) ? 3 : 2) void conv3x3_mfma_
         }
         bias0 = p.b0[li];
         interior = y0 > 0 && x0 > 0 && y0 + TH < H && x0 + 16 < W;
+        if constexpr (!PREC) {
+            // exact fp32: bit u = the pixel this lane zeroes behind the write-out of the wave's M-tile u (pixel (wave + 4u) * 32 + li
+            // of the halo tile) exists and lies outside the image - the 1-pixel ring of a border position and everything a ragged
+            // right / bottom position hangs over
+            if (!interior) {
+#pragma unroll
+                for (int u = 0; u < (NT0 + 3) / 4; ++u) {
+                    const int q = (wave + 4 * u) * 32 + li, ly = q / LW, lx = q - ly * LW;
+                    const bool inside = (unsigned)(y0 - 1 + ly) < (unsigned)H && (unsigned)(x0 - 1 + lx) < (unsigned)W;
+                    if (q < NPIX && !inside) zflag |= 1u << u;
+                }
+            }
+        }
     }
     // Touch the per-lane constants so hipcc retires their loads BEFORE the frame loop: otherwise it guards
     // MFMAs inside the loop with descending vmcnt waits that also drain the freshly issued prefetch.
@@ -374,7 +391,7 @@ __global__ __launch_bounds__(256, (FUSE_C3 && !PREC) ? 3 : 2) void conv3x3_mfma_
 
     // epilogue geometry: per-lane byte offset of (mt 0, q 0, pos 0) for each N-tile, plus wave-uniform strides
     const bool full_tile = (y0 + TH <= H) && (x0 + 16 <= W);
-    const int ech = (MODE == MODE_LSTM) ? p.hid : p.cout;
+    const int ech = C32 ? 32 : (MODE == MODE_LSTM) ? p.hid : p.cout;
     const int ow = (MODE == MODE_POOL) ? (W >> 1) : W, oh = (MODE == MODE_POOL) ? (H >> 1) : H;
     const int ey0 = (MODE == MODE_POOL) ? (y0 >> 1) + wm * MT : y0 + 2 * wm * MT;      // first output row of this lane
     const int ex0 = (MODE == MODE_POOL) ? (x0 >> 1) + lh : x0 + 2 * lh;                // first output column
@@ -547,28 +564,40 @@ __global__ __launch_bounds__(256, (FUSE_C3 && !PREC) ? 3 : 2) void conv3x3_mfma_
                     __builtin_amdgcn_s_setprio(0);
                     __builtin_amdgcn_sched_barrier(0);
                 }
+                // Write-out: every M-tile of every tile position stores its activated values in one straight line, at immediate
+                // offsets from one per-lane base (accumulator register r of lane half lh is pixel t*32 + (r&3) + 8*(r>>2) + 4*lh,
+                // channel li).  Nothing is tested per value.  The last M-tile holds REM < 32 pixels: which of its registers exist
+                // is known at compile time (none is emitted for a row at or beyond NPIX) and what is left sits under one lane
+                // predicate.
+                constexpr int REM = NPIX - (NT0 - 1) * 32, TLAST = NT0 - 1;
+                static_assert(REM >= 1 && REM <= 4, "last M-tile: rows 0..REM-1 of lane half 0 only");
+                float* const wbase = &tile[(wave * 32 + 4 * lh) * PS + li];
+                const int wave_s = __builtin_amdgcn_readfirstlane(wave);   // in a scalar register: the tests below are branches, not lane masks
 #pragma unroll
                 for (int u = 0; u < TPW; ++u) {
-                    const int t = wave + 4 * u;
-                    if (t < NT0) {   // wave-uniform
-                        // straight-line stores (the tile is padded to NT0*32 pixels); only border tiles need the
-                        // per-pixel inside test that provides conv #2's zero padding
-                        const int qb = (t * 32 + 4 * lh) * PS + li;
-                        if (interior && t < NT0 - 1) {
+                    float* const wb = wbase + u * (4 * 32 * PS);
+                    if (4 * u + 3 < TLAST || wave_s + 4 * u < TLAST) {   // (compile time || wave-uniform) a whole M-tile
 #pragma unroll
-                            for (int r = 0; r < 16; ++r)
-                                tile_put_t<PREC>(tile, qb + ((r & 3) + 8 * (r >> 2)) * PS, li, vad_act(c0[u][r], VAD_ACT_LEAKY));
-                        } else {
+                        for (int r = 0; r < 16; ++r) wb[((r & 3) + 8 * (r >> 2)) * PS] = vad_act(c0[u][r], VAD_ACT_LEAKY);
+                    } else if (wave_s + 4 * u == TLAST) {                // (wave-uniform)
+                        if (lh == 0) {
 #pragma unroll
-                            for (int r = 0; r < 16; ++r) {
-                                const int q2 = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                                const int ly2 = q2 / LW, lx2 = q2 - ly2 * LW;
-                                const bool inside = (unsigned)(y0 - 1 + ly2) < (unsigned)H && (unsigned)(x0 - 1 + lx2) < (unsigned)W;
-                                const float v = vad_act(c0[u][r], VAD_ACT_LEAKY);
-                                if (q2 < NPIX) tile_put_t<PREC>(tile, qb + ((r & 3) + 8 * (r >> 2)) * PS, li, inside ? v : 0.f);
-                            }
+                            for (int r = 0; r < REM; ++r) wb[r * PS] = vad_act(c0[u][r], VAD_ACT_LEAKY);
                         }
                     }
+                }
+                // Zero padding of the second convolution: a position that touches the image's edge (or hangs over it) overwrites
+                // the out-of-image pixels among those this wave has just written with +0.0 - whatever was computed there, NaN and
+                // Inf included.  One lane = one pixel x 16 channels; a wave's LDS operations complete in order, so the zeros land
+                // behind the values, and the barrier below publishes both.  zflag is fixed for the work-group's life.
+                if (!interior) {                                         // (uniform)
+                    float* const zb = &tile[(wave * 32 + li) * PS + 16 * lh];
+#pragma unroll
+                    for (int u = 0; u < TPW; ++u)
+                        if ((zflag >> u) & 1u) {
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) *(f32x4*)&zb[u * (4 * 32 * PS) + 4 * j] = f32x4{0.f, 0.f, 0.f, 0.f};
+                        }
                 }
                 }
                 STAMP(8);
@@ -726,13 +755,15 @@ __global__ __launch_bounds__(256, (FUSE_C3 && !PREC) ? 3 : 2) void conv3x3_mfma_
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         const bool ok = full_tile || ((ey0 + mt) < oh && (ex0 + 2 * q) < ow);
-                        const unsigned so = mt * erow + 2 * q * ecol;
+                        // (C32: the pixel stride is the constant 128 B, so the column part joins the per-lane offset - hipcc
+                        // keeps the eight sums in registers - and the eight stores of a tile share two scalar offsets, 0 and erow)
+                        const unsigned so = mt * erow + (C32 ? 0u : 2 * q * ecol), io = C32 ? 2u * q * 128u : 0u;
 #pragma unroll
                         for (int nt = 0; nt < NT; ++nt) {
                             // MaxPool2d(act(.)) == act(MaxPool2d(.)) bit for bit (ReLU / LeakyReLU are non-decreasing): one
                             // activation per window instead of four (VALU work shares the pipe with the exact-fp32 MFMAs)
                             const float m = vad_vmax4(acc[mt][nt][4 * q], acc[mt][nt][4 * q + 1], acc[mt][nt][4 * q + 2], acc[mt][nt][4 * q + 3]);
-                            vad_bstore1(vad_act(m, ACT), ro, ok ? eoff[nt] : VAD_OOB, so);
+                            vad_bstore1(vad_act(m, ACT), ro, (ok ? eoff[nt] : VAD_OOB) + io, so);
                         }
                     }
                 }
