@@ -443,8 +443,16 @@ int vad_debug_set_bn_wide(int on);
  * fp16 range at large batches); default 1 = scaled by a power of two and unscaled at the end (csrc/train_step.hip). */
 int vad_debug_set_split_grad_scale(int on);
 int vad_split_grad_scale_enabled(void);
-int vad_debug_set_train_stop(int stage);   /* debug: stop vad_vid_train_fwd_bwd after a backward stage (see csrc/train_step.hip) */
+/* debug: return from vad_vid_train_fwd_bwd(_l) early with the gradient scratch intact.  20 = after the last layer and the
+ * criterion; 2, 1, 0 = after the backward of decoder stage j; 10 + l = after the backward of ConvLSTM layer l; 30 + k = after the
+ * backward of encoder stage k; -1 (default) = the whole step.  Every stop runs without the weight-gradient helper stream, stops
+ * >= 10 also without the layer wavefront (bit-identical orders).  What g0 / g2 hold at each stop: csrc/train_step.hip. */
+int vad_debug_set_train_stop(int stage);
 int vad_vid_train_debug_layout(int b, int t, int h, int w, int latent, int hid, int layers, long long* out, int cap);
+/* debug: the offsets vad_vid_train_debug_layout leaves out, for the criterion loss_kind: pseq (0 without proj), dcat[l], dzl[l],
+ * dc[l], recon, drecon (both 0 with loss_kind 0), ksums (k1 / k2 of the last BatchNorm backward), ws_floats.  Same return
+ * convention. */
+int vad_vid_train_debug_layout2(int b, int t, int h, int w, int latent, int hid, int layers, int loss_kind, long long* out, int cap);
 int vad_vid_train_fwd_bwd(const float* x, int b, int t, int h, int w, int latent, int hid, int layers,
                           const float* params, float* grads, float* running, void* workspace, size_t workspace_bytes,
                           int precision, float* loss, float* recon, void* stream);

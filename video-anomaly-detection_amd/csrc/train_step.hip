@@ -222,9 +222,16 @@ int train_streams(int layers, TrainStreams** out) {
 }  // namespace
 extern "C" int vad_lstm_wavefront_mode(void);   // vad_api.hip: vad_debug_set_lstm_wavefront (0 = never, 1 = small launch groups, 2 = always)
 
-// Debug: return from vad_vid_train_fwd_bwd right after the backward of decoder stage `j` (2, 1, 0), 10 + l after ConvLSTM
-// layer l, leaving the gradient scratch (g0 = gradient of that stage's input, g2 = gradient of its conv output)
-// in the workspace for inspection (tools/diag_stream.py).  -1 = run the whole step (default).
+// Debug: return from vad_vid_train_fwd_bwd early, leaving the gradient scratch in the workspace for inspection
+// (tests/test_hip_train_audit.py).  Stages:
+//   20      after the last layer and the criterion: g0 = gradient of the last decoder activation r2, dpre intact
+//   2, 1, 0 after the backward of decoder stage j: g2 = gradient of its conv output u_j (space-to-depth), g0 = gradient of its input
+//   10 + l  after the backward of ConvLSTM layer l (layers-outer order); g0 / g2 still hold d hseq
+//   30 + k  after the backward of encoder stage k (3, 2, 1, 0): g2 = gradient of its conv output y_k (the routing bytes of a routed
+//           first layer), g0 = gradient of its input a_{k-1} (k > 0)
+//   -1      run the whole step (default).
+// Every stop runs the step without the weight-gradient helper stream (one dy buffer, g2); stops >= 10 also without the
+// ConvLSTM layer wavefront.  Same launches and operands as the default run: bit-identical results.
 static int g_vad_train_stop = -1;
 extern "C" int vad_debug_set_train_stop(int stage) { g_vad_train_stop = stage; return VAD_OK; }
 
@@ -285,6 +292,28 @@ extern "C" int vad_vid_train_debug_layout(int b, int t, int h, int w, int latent
     for (int i = 0; i < 3; ++i) v.push_back((long long)p.g[i]);
     v.push_back((long long)p.ws_floats);
     VAD_REQUIRE((int)v.size() <= cap, "vid_train_debug_layout: need room for %d entries", (int)v.size());
+    for (size_t i = 0; i < v.size(); ++i) out[i] = v[i];
+    return (int)v.size();
+}
+
+// Debug: the rest of the workspace carve, for a launch-by-launch audit of the step (tests/test_hip_train_audit.py).  Float
+// offsets for the criterion `loss_kind`, in the order
+//   pseq (0 without proj), dcat[0..NL), dzl[0..NL), dc[0..NL), recon, drecon (both 0 with loss_kind 0),
+//   ksums ({k1[c], k2[c]} of the last BatchNorm backward, 2 x 1024 floats), ws_floats
+// vad_vid_train_debug_layout keeps its own order (tools/diag_flip.py indexes it by position).  Returns the number written or < 0.
+extern "C" int vad_vid_train_debug_layout2(int b, int t, int h, int w, int latent, int hid, int layers, int loss_kind, long long* out, int cap) {
+    Plan p;
+    VAD_REQUIRE(out && make_plan(p, b, t, h, w, latent, hid, layers, loss_kind), "vid_train_debug_layout2: unsupported configuration");
+    std::vector<long long> v;
+    v.push_back((long long)p.pseq);
+    for (int l = 0; l < layers; ++l) v.push_back((long long)p.dcat[l]);
+    for (int l = 0; l < layers; ++l) v.push_back((long long)p.dzl[l]);
+    for (int l = 0; l < layers; ++l) v.push_back((long long)p.dc[l]);
+    v.push_back((long long)p.recon);
+    v.push_back((long long)p.drecon);
+    v.push_back((long long)p.ksums);
+    v.push_back((long long)p.ws_floats);
+    VAD_REQUIRE((int)v.size() <= cap, "vid_train_debug_layout2: need room for %d entries", (int)v.size());
     for (size_t i = 0; i < v.size(); ++i) out[i] = v[i];
     return (int)v.size();
 }
@@ -368,9 +397,16 @@ extern "C" int vad_vid_train_fwd_bwd_l(const float* x, int b, int t, int h, int 
         const int ci = p.encC[k], co = p.encC[k + 1], hk = H >> k, wk = W >> k;
         float* y = A(p.y[k]);
         int sblocks = 0;      // > 0: the convolution wrote the BatchNorm partial sums itself (first layer: no second pass over y)
+        // A handful of samples per channel (the last stages of a single small frame): the convolutions shift their partial sums by
+        // the BIAS, and the finalize's q/M - sm^2 then loses ~2^-24 sm^2.  That is harmless while (mean - bias)^2 / var stays at its
+        // population level (5 .. 19 measured), but the variance of FOUR samples collapsed to 1/189 of the shift in one channel and
+        // 1/std was off by 3.2e-6 of itself (tests/test_hip_train_audit.py).  Up to 16 samples (beyond that a sample variance no
+        // longer falls far below the population's) vad_bn_stats does it, shifted by a SAMPLE; its second pass over 16 pixels costs
+        // nothing.  fp32 tensors only: the bf16 step has no stand-alone statistics pass (see above).
+        const bool few = !io && (long long)N * hk * wk <= 16;
         // (bf16 tensors: the first layer on bf16 MFMA operands too - out16 = 2 - so that it runs at the rate of its stores)
         if (k == 0) { PS(TS_C3_FWD); TRY(vad_conv3x3_c3_stats_t(x, VAD_X_F32_NCHW, ws + p.pk_e[0], P + p.e_b[0], y, io ? 2 : 0, N, hk, wk, co, VAD_ACT_NONE, 0, ws + p.chan_ws, &sblocks, s)); }
-        else { PS(TS_CONV_FWD); TRY(conv3(A(p.a[k - 1]), ws + p.pk_e[k], P + p.e_b[k], y, N, hk, wk, ci, co, ws + p.chan_ws, &sblocks, s)); }
+        else { PS(TS_CONV_FWD); TRY(conv3(A(p.a[k - 1]), ws + p.pk_e[k], P + p.e_b[k], y, N, hk, wk, ci, co, few ? nullptr : ws + p.chan_ws, few ? nullptr : &sblocks, s)); }
         float* rs = running ? running + p.e_rs[k] : nullptr;
         if (sblocks > 0) { PS(TS_STATS_MISC); TRY(vad_bn_stats_from_partials(ws + p.chan_ws, sblocks, (long long)N * hk * wk, co, eps, mom, ws + p.st_e[k], rs, rs ? rs + co : nullptr, P + p.e_b[k], s)); }
         else {
@@ -441,7 +477,8 @@ extern "C" int vad_vid_train_fwd_bwd_l(const float* x, int b, int t, int h, int 
         const float* in = j == 0 ? dec_in : A(p.r[j - 1]);
         float* u = A(p.u[j]);
         int srows = 0;        // > 0: the transposed convolution wrote the BatchNorm partial sums itself
-        { PS(TS_CONVT_FWD); TRY(vad_convt2x2_stats(in, 0, ws + p.pk_d[j], P + p.d_b[j], u, 0, N, hj, wj, ci, co, VAD_ACT_NONE, precision, ws + p.chan_ws, &srows, s)); }
+        const bool few = !io && (long long)N * 4 * hj * wj <= 16;      // (as in the encoder: sample-shifted statistics for a handful of samples)
+        { PS(TS_CONVT_FWD); TRY(vad_convt2x2_stats(in, 0, ws + p.pk_d[j], P + p.d_b[j], u, 0, N, hj, wj, ci, co, VAD_ACT_NONE, precision, few ? nullptr : ws + p.chan_ws, few ? nullptr : &srows, s)); }
         float* rs = running ? running + p.d_rs[j] : nullptr;
         if (srows > 0) { PS(TS_STATS_MISC); TRY(vad_bn_stats_from_partials(ws + p.chan_ws, srows, (long long)N * 4 * hj * wj, co, eps, mom, ws + p.st_d[j], rs, rs ? rs + co : nullptr, P + p.d_b[j], s)); }
         else {
@@ -611,6 +648,7 @@ extern "C" int vad_vid_train_fwd_bwd_l(const float* x, int b, int t, int h, int 
             PS(TS_CONV_DGRAD);
             TRY(conv3(g2, ws + p.pk_e_dg[k], zeros, g0, N, hk, wk, co, ci, nullptr, nullptr, s));
         }
+        if (g_vad_train_stop == 30 + k) return VAD_OK;
     }
     if (overlap) {             // join: the optimiser reads every gradient
         VAD_HIP_TRY(hipEventRecord(TS->wg_in, wgs));

@@ -216,6 +216,7 @@ SIGNATURES = {
     "vad_debug_set_split_grad_scale": (_i, [_i]),
     "vad_split_grad_scale_enabled": (_i, []),
     "vad_vid_train_debug_layout": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _i]),
+    "vad_vid_train_debug_layout2": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _vp, _i]),
     "vad_vid_train_fwd_bwd": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _i, _vp, _vp, _vp]),
     "vad_vid_train_workspace_bytes_l": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i]),
     "vad_vid_train_fwd_bwd_l": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _i, _f, _i, _i, _vp, _vp, _vp]),
