@@ -937,6 +937,74 @@ int vad_detect_events(const float* maps, long long b, int t, int h, int w, float
                       uint32_t* frame_counts /* [b, t, 3] */, void* ws, size_t ws_bytes, void* stream);
 int vad_events_plan(int* label_round, int* volume_round, int* scan_round, int* reduce_round, int* threads);
 
+/* ------------------------------------------------------------------ Anomaly events across the calls of a live stream (csrc/map_track.hip)
+ * The events of vad_detect_events, continued frame by frame: a stream is the sequence of its maps [h, w] since the last init, an
+ * event a connected component of {v >= threshold} in the stream's volume so far - same predicate, same three structures
+ * (connectivity, temporal) = (4, 1), (8, 1), (8, 9).  The frame numbers t = 0, 1, ... are counted on the device, in the state: the
+ * host passes none, so a captured call can be replayed.  After frame t an event is OPEN iff it has a pixel in frame t; it CLOSES at
+ * the arrival of frame t1 + 1 when no pixel of that frame links to it.  Two open events joined by a region of the new frame are one
+ * from then on (root: the smaller (t0, root pixel); sums, volume and box combined); a split leaves one event; an event absent for
+ * one frame closes and a new one begins.  Streams never link.
+ *
+ * One record is VAD_TRACK_WORDS = 20 uint32 words (80 bytes, 16-byte aligned):
+ *     word 0       root_pixel: y * w + x of the smallest pixel of the event's first frame (root = t0 * h * w + root_pixel)
+ *     words 1-2    t0, t1: first and last frame, inclusive
+ *     word 3       handle: the smallest pixel of the event in frame t1
+ *     words 4-7    x0, y0, x1, y1 of the union of its frames' boxes, inclusive
+ *     word 8       peak: the float bits of the event's maximum (order key of vad_detect_regions: -0.0 < +0.0)
+ *     words 9-10   peak_pixel, peak_frame: among the pixels that hold the maximum the earliest frame, then the smallest pixel
+ *     word 11      reserved, zero
+ *     words 12-13  uint64 volume in pixels (an all-foreground 256 x 256 stream passes 2^32 pixels in 36 minutes at 30 frames/s)
+ *     words 14-15  uint64 sum of x             (centroid = sum / volume, exactly)
+ *     words 16-17  uint64 sum of y
+ *     words 18-19  uint64 sum of t, exact modulo 2^64: it wraps once h * w * T * (T - 1) / 2 of an always-foreground stream reaches
+ *                  2^64 - at 256 x 256 from T = 23.7 million frames on (nine days at 30 frames/s), at 2^24 pixels from 1.48 million
+ *
+ * State (caller-owned device memory, 16-byte aligned, vad_track_state_bytes(b, h, w, max_open) bytes; 0 for arguments out of range,
+ * no device needed), per stream: a header of 16 words - frames seen, open events, events lost in total (sticky), flags (sticky:
+ * VAD_LABEL flag bit 0 = a walk ran out of its budget, VAD_TRACK_FLAG_COUNTER = the frame counter stands at 2^32 - 1 and no longer
+ * advances), a magic word, h, w, max_open, zeros -, the open table [max_open, 20] (slot r = the open event whose handle has rank r
+ * in raster order; all-zero records behind the open ones), the slot plane [h * w] of the newest frame (0, slot + 1, or 0xffffffff
+ * for an open event without a record), padded to 16 bytes.  vad_track_init writes a fresh header, table and plane (asynchronous).
+ * max_open in 1 .. 65536: an open event of rank >= max_open has no record; it is counted as LOST, once, in counts and in the
+ * header; its pixels never alarm and count as background for the links of the next frame.  Visible, never silent.
+ *
+ * vad_track_events continues b streams by t >= 1 maps each (maps fp32 [b, t, h, w], contiguous, 4-byte aligned; h * w <= 2^24,
+ * b <= 2^20, b * t * h * w <= 2^38):
+ * closed uint32 [b, max_closed, 20], 16-byte aligned: the events that closed in this call and pass t1 - t0 + 1 >= min_duration and
+ *     volume >= min_volume with their final values, in ascending (t1, handle) order - the same for any split of the frames over
+ *     calls -, the first min(kept, max_closed) written (max_closed in 1 .. 65536), every other record all-zero.
+ * counts uint32 [b, 6]: closed and kept (the full number), closed and dropped by a filter, foreground pixels, NaN pixels, events
+ *     open after the call, events lost in this call.
+ * frame_counts uint32 [b, t, 3]: foreground pixels of the frame; pixels of the frame that belong to events which alarm NOW
+ *     (t - t0 + 1 >= min_duration and the volume so far >= min_volume: the causal counterpart of vad_detect_events' word,
+ *     independent of max_closed); NaN pixels of the frame.
+ * vad_track_flush closes every open event as if an empty frame had arrived, without advancing the counter, in slot order through
+ * the same filters; the table and the plane are zero afterwards.  Its ws is vad_track_workspace_bytes(b, 0, h, w, max_open).
+ * ws: caller-provided, 16-byte aligned, vad_track_workspace_bytes(b, t, h, w, max_open) bytes (0 out of range, no device needed):
+ * 16 bytes for the flag word (its first uint32: cleared by every call, set by a walk out of budget or the counter's end), then -
+ * each padded to 16 - the labels 4 * b * t * h * w, 4 * b * max_open, 4 per chunk of 1024 pixels of a frame and stream, 4 * b * h * w,
+ * the working records 96 * b * max_open, 4 * b.
+ * vad_track_plan: the pixels one grid round covers in the labeller, in the link / reduce passes, in the flatten / slot scan, the
+ * slots one round of the table passes covers, and the threads of a work-group.
+ * Integer atomics, min and max only: every output, the table and the plane are the same words for any batching of streams and any
+ * split of the frames over calls.  VAD_ERR_ARG for a NULL or misaligned pointer, b, t, h, w out of range, a connectivity other than
+ * 4 or 8, a temporal other than 1 or 9, temporal 9 with connectivity 4, min_duration == 0, min_volume == 0, max_open or max_closed
+ * out of range and a NaN threshold; VAD_ERR_WS for a short workspace.  Every launch is asynchronous on `stream`; nothing is
+ * allocated, the host never waits; a call with fixed t can be captured into a graph. */
+#define VAD_TRACK_WORDS 20
+#define VAD_TRACK_FLAG_COUNTER 4u
+size_t vad_track_state_bytes(long long b, int h, int w, int max_open);
+size_t vad_track_workspace_bytes(long long b, int t, int h, int w, int max_open);
+int vad_track_init(void* state, long long b, int h, int w, int max_open, void* stream);
+int vad_track_events(const float* maps, long long b, int t, int h, int w, float threshold, int connectivity, int temporal,
+                     unsigned min_duration, unsigned min_volume, int max_open, int max_closed, void* state,
+                     uint32_t* closed /* [b, max_closed, 20] */, uint32_t* counts /* [b, 6] */,
+                     uint32_t* frame_counts /* [b, t, 3] */, void* ws, size_t ws_bytes, void* stream);
+int vad_track_flush(long long b, int h, int w, unsigned min_duration, unsigned min_volume, int max_open, int max_closed, void* state,
+                    uint32_t* closed /* [b, max_closed, 20] */, uint32_t* counts /* [b, 6] */, void* ws, size_t ws_bytes, void* stream);
+int vad_track_plan(int* label_round, int* pixel_round, int* scan_round, int* table_round, int* threads);
+
 /* ------------------------------------------------------------------ Per-pixel calibration of anomaly maps (csrc/map_stats.hip)
  * The mean and standard deviation of every pixel of the anomaly map over the normal (training) frames, and the z-score map
  * z = (map - mean) / std that is ranked, thresholded and labelled in place of the raw map.  The maps stay on the device.

@@ -16,7 +16,7 @@ PKG_DIR = Path(__file__).resolve().parent
 REPO_DIR = PKG_DIR.parent
 CSRC = PKG_DIR / "csrc"
 LIB_PATH = Path(os.environ.get("VAD_LIB", PKG_DIR / "libvad_hip.so"))
-SOURCES = ["conv_mfma.hip", "conv_wino.hip", "dec4_fused.hip", "tail.hip", "wide_io.hip", "state_io.hip", "resize_u8.hip", "frame_gather.hip", "score_hist.hip", "region_overlap.hip", "map_regions.hip", "map_events.hip", "map_smooth.hip", "map_stats.hip", "ssim.hip", "train_ops.hip", "wgrad.hip", "train_step.hip", "train_step_img.hip", "vad_api.hip", "pack.cpp"]
+SOURCES = ["conv_mfma.hip", "conv_wino.hip", "dec4_fused.hip", "tail.hip", "wide_io.hip", "state_io.hip", "resize_u8.hip", "frame_gather.hip", "score_hist.hip", "region_overlap.hip", "map_regions.hip", "map_events.hip", "map_track.hip", "map_smooth.hip", "map_stats.hip", "ssim.hip", "train_ops.hip", "wgrad.hip", "train_step.hip", "train_step_img.hip", "vad_api.hip", "pack.cpp"]
 
 VAD_OK = 0
 ABI_VERSION = 3
@@ -54,6 +54,10 @@ REGION_WORDS = 12         # VAD_REGION_WORDS: uint32 words of one record of vad_
 MAX_REGIONS = 65536       # largest max_regions of vad_detect_regions
 EVENT_WORDS = 16          # VAD_EVENT_WORDS: uint32 words of one record of vad_detect_events
 MAX_EVENTS = 65536        # largest max_events of vad_detect_events
+TRACK_WORDS = 20          # VAD_TRACK_WORDS: uint32 words of one record of vad_track_events
+TRACK_HEADER_WORDS = 16   # the header of one stream's tracker state: frames, open, lost in total, flags, magic, h, w, max_open, zeros
+TRACK_MAX_OPEN = 65536    # largest max_open / max_closed of vad_track_events
+TRACK_NO_RECORD = 0xFFFFFFFF   # slot plane: a pixel of an open event behind the table
 SMOOTH_TILE = (32, 64)    # csrc/map_smooth.hip SM_TH x SM_TW: the output tile of one work-group (vad_smooth_tile reports the library's)
 MAX_FRAME_PIXELS = 2 ** 23 - 1    # VAD_MAX_FRAME_PIXELS: largest H * W (pixel indices are 24-bit multiply operands inside the kernels)
 FRAME_RULE = f"H and W must be multiples of 16 with H * W <= {MAX_FRAME_PIXELS}"
@@ -308,6 +312,13 @@ SIGNATURES = {
     "vad_events_workspace_bytes": (_sz, [_ll, _i, _i, _i, _i]),
     "vad_detect_events": (_i, [_vp, _ll, _i, _i, _i, _f, _i, _i, C.c_uint, C.c_uint, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vad_events_plan": (_i, [C.POINTER(_i)] * 5),
+    # anomaly events across the calls of a live stream (csrc/map_track.hip)
+    "vad_track_state_bytes": (_sz, [_ll, _i, _i, _i]),
+    "vad_track_workspace_bytes": (_sz, [_ll, _i, _i, _i, _i]),
+    "vad_track_init": (_i, [_vp, _ll, _i, _i, _i, _vp]),
+    "vad_track_events": (_i, [_vp, _ll, _i, _i, _i, _f, _i, _i, C.c_uint, C.c_uint, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "vad_track_flush": (_i, [_ll, _i, _i, C.c_uint, C.c_uint, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "vad_track_plan": (_i, [C.POINTER(_i)] * 5),
     # per-pixel statistics of anomaly maps and the z-score map (csrc/map_stats.hip)
     "vad_mapstat_state_bytes": (_sz, [_i, _i]),
     "vad_mapstat_reset": (_i, [_vp, _i, _i, _vp]),

@@ -1094,6 +1094,265 @@ def detect_events(maps: torch.Tensor, threshold: float, connectivity: int = 8, t
     return result(records, counts, frame_counts, labels)
 
 
+# ====================================================================== anomaly events across the calls of a live stream
+# `detect_events` closes every event at the end of its clip.  A camera that hands over its newest frame (`score_stateful`) needs the
+# events continued between calls: the open events and the newest frame's slot plane are state on the
+# device, a call takes the new maps in and returns the events that closed and the causal alarm of every new frame.
+TRACK_WORDS = hip.TRACK_WORDS
+TRACK_MAX_OPEN = hip.TRACK_MAX_OPEN
+
+
+class _TrackRecords:
+    """Views of tracker records int32 [..., E, 20] (include/vad_hip.h, VAD_TRACK_WORDS), no copies."""
+    records: torch.Tensor
+
+    root_pixel = property(lambda self: self.records[..., 0])
+    t0 = property(lambda self: self.records[..., 1])
+    t1 = property(lambda self: self.records[..., 2])
+    handle = property(lambda self: self.records[..., 3])
+    box = property(lambda self: self.records[..., 4:8])
+    peak = property(lambda self: self.records[..., 8].view(torch.float32))
+    peak_pixel = property(lambda self: self.records[..., 9])
+    peak_frame = property(lambda self: self.records[..., 10])
+    volume = property(lambda self: self.records[..., 12:14].view(torch.int64)[..., 0])
+    sum_x = property(lambda self: self.records[..., 14:16].view(torch.int64)[..., 0])
+    sum_y = property(lambda self: self.records[..., 16:18].view(torch.int64)[..., 0])
+    sum_t = property(lambda self: self.records[..., 18:20].view(torch.int64)[..., 0])
+
+    def durations(self) -> torch.Tensor:
+        """int64 [..., E]: t1 - t0 + 1 of the records in use (frame numbers are unsigned 32-bit words), 0 for the all-zero ones."""
+        span = (self.t1.to(torch.int64) & 0xFFFFFFFF) - (self.t0.to(torch.int64) & 0xFFFFFFFF) + 1
+        return torch.where(self.volume != 0, span, torch.zeros_like(span))
+
+    def centroids(self) -> torch.Tensor:
+        """float64 [..., E, 3] on the device: (t, y, x) = sums / volume; NaN for the all-zero records."""
+        volume = self.volume.to(torch.float64)
+        return torch.stack([s.to(torch.float64) / volume for s in (self.sum_t, self.sum_y, self.sum_x)], dim=-1)
+
+    def _rows(self, used) -> list:
+        rec = self.records.reshape(-1, self.records.shape[-2], TRACK_WORDS).cpu().numpy()
+        w = self.frame_shape[1]
+        out = []
+        for c in range(rec.shape[0]):
+            rows = []
+            for r in rec[c, :int(used[c])]:
+                u = r.view(np.uint32)
+                volume, sx, sy, st = (int(v) for v in u[12:20].copy().view(np.uint64))
+                rows.append({"root_pixel": int(u[0]), "t0": int(u[1]), "t1": int(u[2]), "duration": int(u[2]) - int(u[1]) + 1, "handle": int(u[3]),
+                             "volume": volume, "box": tuple(int(v) for v in u[4:8]), "peak": float(u[8:9].copy().view(np.float32)[0]),
+                             "peak_tyx": (int(u[10]), *divmod(int(u[9]), w)), "centroid_tyx": (st / volume, sy / volume, sx / volume)})
+            out.append(rows)
+        return out
+
+
+class TrackUpdate(_TrackRecords):
+    """What one `EventTracker.update` / `flush` returns, as device tensors with the leading shape `[B]` of the streams:
+
+      records       int32 [B, E, 20]: the events that CLOSED in this call and pass the filters, in ascending (t1, handle) order, E =
+                    max_closed; all-zero records behind them
+      counts        int32 [B, 6]: closed and kept (the full number: above E the table is truncated), closed and dropped by a filter,
+                    foreground pixels, NaN pixels, events open after the call, events lost in this call
+      frame_counts  int32 [B, T, 3]: foreground pixels of the frame, pixels of the frame that belong to events which alarm NOW
+                    (duration so far >= min_duration, volume so far >= min_volume), NaN pixels of the frame; T = 0 for a flush
+
+    Views of `records` as in `Events`, with `root_pixel` / `t0` in place of `root`, `peak_pixel` / `peak_frame` in place of
+    `peak_index`, `handle`, and `volume` as int64."""
+
+    def __init__(self, records, counts, frame_counts, frame_shape, max_closed):
+        self.records, self.counts, self.frame_counts, self.frame_shape, self.max_closed = records, counts, frame_counts, frame_shape, max_closed
+
+    def alarms(self) -> torch.Tensor:
+        """bool [B, T]: the frame holds a pixel of an event that has lasted min_duration frames and gathered min_volume pixels."""
+        return self.frame_counts[..., 1] > 0
+
+    def truncated(self) -> torch.Tensor:
+        """bool [B]: more events closed and passed the filters in this call than the table has records."""
+        return self.counts[..., 0] > self.max_closed
+
+    def lost(self) -> torch.Tensor:
+        """int32 [B]: open events that found no slot in the open table in this call (max_open): they have no record, never alarm."""
+        return self.counts[..., 5]
+
+    def to_list(self) -> list:
+        """A host copy of the closed table - 80 bytes per record, never a map -: one list per stream of dicts in table order."""
+        return self._rows(torch.clamp(self.counts[:, 0], max=self.max_closed).cpu().numpy())
+
+
+class OpenEvents(_TrackRecords):
+    """The live table of an `EventTracker`: `records` int32 [B, max_open, 20] - a view of the state, slot r = the open event whose
+    handle has rank r in raster order -, `counts` int32 [B] = the open events with a record."""
+
+    def __init__(self, records, counts, frame_shape):
+        self.records, self.counts, self.frame_shape = records, counts, frame_shape
+
+    def to_list(self) -> list:
+        return self._rows(self.counts.cpu().numpy())
+
+
+class EventTracker:
+    """Events of B live streams, carried across calls on the device (`vad_track_events`, csrc/map_track.hip).
+    The specification is `detect_events` applied to prefixes of a stream: the same predicate (`v >= threshold`, NaN never, `+Inf`
+    always), the same structures (`connectivity`, `temporal`) = (4, 1), (8, 1), (8, 9).  `update(maps)` continues every stream by
+    T >= 1 maps and returns a `TrackUpdate`: the events that closed (no pixel of the next frame links to them) and pass
+    `min_duration` / `min_volume`, and per new frame the pixels of the events that alarm now.  Closed + flushed events are exactly
+    the events `detect_events` finds in the whole stream, for any split of the frames over calls - while nothing is lost: at most
+    `max_open` (1..65536) events are open at a time, one behind that has no record and is counted in `TrackUpdate.lost()`.
+    The frame number is counted on the device, so a captured `update` can be replayed.  Like `detect_events`, every call reads the
+    kernels' 4-byte flag word (which waits for the call) and raises VadError if it is set - unless the call is being captured into
+    a graph: then read `flags()` after the replays.  No CPU fallback."""
+
+    def __init__(self, streams: int, h: int, w: int, threshold: float, connectivity: int = 8, temporal: int = 9, min_duration: int = 1,
+                 min_volume: int = 1, max_open: int = 1024, max_closed: int = 64, device=None):
+        what = "EventTracker"
+        self.connectivity = _check_connectivity(connectivity, what)
+        if isinstance(temporal, bool) or not isinstance(temporal, (int, np.integer)) or int(temporal) not in (1, 9):
+            raise hip.VadError(f"{what}: temporal must be 1 or 9, got {temporal!r}")
+        self.temporal = int(temporal)
+        if self.temporal == 9 and self.connectivity != 8:
+            raise hip.VadError(f"{what}: temporal=9 (the 3 x 3 of the frame before) needs connectivity=8, got connectivity={connectivity}")
+        if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)) or np.isnan(threshold):
+            raise hip.VadError(f"{what}: threshold must be a number that is not NaN, got {threshold!r}")
+        for name, v, lo, hi in (("streams", streams, 0, 2 ** 20), ("h", h, 1, 2 ** 24), ("w", w, 1, 2 ** 24), ("min_duration", min_duration, 1, 2 ** 32 - 1),
+                                ("min_volume", min_volume, 1, 2 ** 32 - 1), ("max_open", max_open, 1, TRACK_MAX_OPEN),
+                                ("max_closed", max_closed, 1, TRACK_MAX_OPEN)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+                raise hip.VadError(f"{what}: {name} must be an int in {lo}..{hi}, got {v!r}")
+        self.streams, self.h, self.w = int(streams), int(h), int(w)
+        self.min_duration, self.min_volume, self.max_open, self.max_closed = int(min_duration), int(min_volume), int(max_open), int(max_closed)
+        self.threshold = float(np.float32(threshold))
+        if self.h * self.w > 2 ** 24:
+            raise hip.VadError(f"{what}: frames of {h} x {w} are out of range (h * w <= 2^24)")
+        dev = torch.device("cuda" if device is None else device)
+        if dev.type != "cuda":
+            raise hip.VadError(f"{what}: device ({dev}) must be a GPU (events are tracked on the device; there is no CPU fallback)")
+        self.device = dev
+        l = hip.lib()
+        size = l.vad_track_state_bytes(self.streams, self.h, self.w, self.max_open)
+        if self.streams and size == 0:
+            raise hip.VadError(f"{what}: {streams} streams of {h} x {w} with max_open {max_open} are out of range")
+        self._stream_words = size // 4 // max(self.streams, 1)
+        self.state = torch.empty(size // 4, dtype=torch.int32, device=dev)
+        self._ws = None
+        self.reset()
+
+    def _blob(self) -> torch.Tensor:
+        return self.state.view(self.streams, self._stream_words) if self.streams else self.state.view(0, hip.TRACK_HEADER_WORDS)
+
+    def reset(self, streams=None) -> None:
+        """A fresh header, table and plane (asynchronous): of every stream, or of the streams in `streams` (indices)."""
+        l = hip.lib()
+        with torch.cuda.device(self.device):
+            if streams is None:
+                if self.streams:
+                    hip.check(l.vad_track_init(self.state.data_ptr(), self.streams, self.h, self.w, self.max_open, hip.current_stream()), "vad_track_init")
+                return
+            for s in streams:
+                s = int(s)
+                if not 0 <= s < self.streams:
+                    raise hip.VadError(f"EventTracker.reset: stream {s} is out of range (0..{self.streams - 1})")
+                hip.check(l.vad_track_init(self.state.data_ptr() + 4 * s * self._stream_words, 1, self.h, self.w, self.max_open,
+                                           hip.current_stream()), "vad_track_init")
+
+    @property
+    def header(self) -> torch.Tensor:
+        """int32 [B, 16] view: frames seen, open events, lost in total, flags, magic, h, w, max_open, zeros."""
+        return self._blob()[:, :hip.TRACK_HEADER_WORDS]
+
+    @property
+    def frames_seen(self) -> torch.Tensor:
+        """int64 [B] on the device: the frames every stream has taken in since its last reset."""
+        return self.header[:, 0].to(torch.int64) & 0xFFFFFFFF
+
+    @property
+    def slot_plane(self) -> torch.Tensor:
+        """int32 [B, H, W] view of the state: 0, slot + 1 of the pixel's open event in the newest frame, or -1 (no record)."""
+        at = hip.TRACK_HEADER_WORDS + self.max_open * TRACK_WORDS
+        return self._blob()[:, at:at + self.h * self.w].view(self.streams, self.h, self.w)
+
+    def open_events(self) -> OpenEvents:
+        at = hip.TRACK_HEADER_WORDS
+        table = self._blob()[:, at:at + self.max_open * TRACK_WORDS].view(self.streams, self.max_open, TRACK_WORDS)
+        return OpenEvents(table, self.header[:, 1], (self.h, self.w))
+
+    def lost_total(self) -> torch.Tensor:
+        return self.header[:, 2]
+
+    def flags(self) -> int:
+        """The sticky flag words of every stream, OR-ed (a host read): 0, or what `update` would have raised on."""
+        return int(np.bitwise_or.reduce(self.header[:, 3].cpu().numpy(), initial=0)) if self.streams else 0
+
+    def _workspace(self, t: int) -> torch.Tensor:
+        size = hip.lib().vad_track_workspace_bytes(self.streams, t, self.h, self.w, self.max_open)
+        if size == 0:
+            raise hip.VadError(f"EventTracker: {self.streams} streams of {t} x {self.h} x {self.w} are out of range (b * t * h * w <= 2^38)")
+        if self._ws is None or self._ws.numel() < size:
+            self._ws = torch.empty(size, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def _done(self, ws, what):
+        hip.calls["track_events"] = hip.calls.get("track_events", 0) + 1
+        if torch.cuda.is_current_stream_capturing():
+            return
+        flags = int(ws[:4].view(torch.int32).item())
+        if flags & ~3:
+            raise hip.VadError(f"{what}: flags {flags:#x} are set - a stream's frame counter stands at 2^32 - 1; reset the tracker")
+        _raise_on_flags(flags, what)
+
+    def update(self, maps: torch.Tensor) -> TrackUpdate:
+        """maps: float32 GPU tensor `[B,H,W]` (one new map per stream), `[B,T,H,W]` or `[B,T,1,H,W]`."""
+        what = "EventTracker.update"
+        if not isinstance(maps, torch.Tensor):
+            raise hip.VadError(f"{what}: maps must be a torch tensor")
+        if not maps.is_cuda:
+            raise hip.VadError(f"{what}: maps ({maps.device}) must be on the GPU (events are tracked on the device; there is no CPU fallback)")
+        if maps.dtype != torch.float32:
+            raise hip.VadError(f"{what}: maps must be float32, got {maps.dtype}")
+        if maps.dim() == 3:
+            maps = maps[:, None]
+        elif maps.dim() == 5 and maps.shape[2] == 1:
+            maps = maps[:, :, 0]
+        elif maps.dim() != 4:
+            raise hip.VadError(f"{what}: maps must be [B,H,W], [B,T,H,W] or [B,T,1,H,W], got {tuple(maps.shape)}")
+        b, t = int(maps.shape[0]), int(maps.shape[1])
+        if (b, int(maps.shape[2]), int(maps.shape[3])) != (self.streams, self.h, self.w):
+            raise hip.VadError(f"{what}: maps {tuple(maps.shape)} do not match the tracker's state: {self.streams} streams of {self.h} x {self.w}")
+        if t < 1:
+            raise hip.VadError(f"{what}: every stream needs at least one new map, got T = {t}")
+        if maps.device != self.state.device:
+            raise hip.VadError(f"{what}: maps ({maps.device}) and the tracker's state ({self.state.device}) are on different devices")
+        maps = maps.contiguous()
+        dev = self.state.device
+        records = torch.empty((b, self.max_closed, TRACK_WORDS), dtype=torch.int32, device=dev)
+        counts = torch.empty((b, 6), dtype=torch.int32, device=dev)
+        frame_counts = torch.empty((b, t, 3), dtype=torch.int32, device=dev)
+        if b == 0:
+            return TrackUpdate(records, counts, frame_counts, (self.h, self.w), self.max_closed)
+        with torch.cuda.device(dev):
+            ws = self._workspace(t)
+            hip.check(hip.lib().vad_track_events(maps.data_ptr(), b, t, self.h, self.w, self.threshold, self.connectivity, self.temporal,
+                                                 self.min_duration, self.min_volume, self.max_open, self.max_closed, self.state.data_ptr(),
+                                                 records.data_ptr(), counts.data_ptr(), frame_counts.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                 hip.current_stream()), "vad_track_events")
+            self._done(ws, what)
+        return TrackUpdate(records, counts, frame_counts, (self.h, self.w), self.max_closed)
+
+    def flush(self) -> TrackUpdate:
+        """Closes every open event as if an empty frame had arrived - in slot order, through the same filters -, without advancing
+        the frame counter: the end of a recording.  The table and the plane are empty afterwards."""
+        b, dev = self.streams, self.state.device
+        records = torch.empty((b, self.max_closed, TRACK_WORDS), dtype=torch.int32, device=dev)
+        counts = torch.empty((b, 6), dtype=torch.int32, device=dev)
+        frame_counts = torch.zeros((b, 0, 3), dtype=torch.int32, device=dev)
+        if b:
+            with torch.cuda.device(dev):
+                ws = self._workspace(0)
+                hip.check(hip.lib().vad_track_flush(b, self.h, self.w, self.min_duration, self.min_volume, self.max_open, self.max_closed,
+                                                    self.state.data_ptr(), records.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                    hip.current_stream()), "vad_track_flush")
+                self._done(ws, "EventTracker.flush")
+        return TrackUpdate(records, counts, frame_counts, (self.h, self.w), self.max_closed)
+
+
 # ====================================================================== per-pixel calibration of anomaly maps
 # An autoencoder's error is not the same everywhere (DESIGN.md section 4.17): on a fixed camera, edges, glossy patches and fine
 # texture reconstruct worse than flat background in every normal frame, so one global threshold either fires there all day or is

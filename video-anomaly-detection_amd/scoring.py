@@ -567,3 +567,34 @@ def localize_events(model, images, threshold: float, map: str = "mse", sigma=Non
         maps = _anomaly_maps(model, images, map, sigma, truncate, calibration, min_std)
         volumes = maps if maps.dim() == 5 else maps[:, 0]                 # [B,T,1,H,W], or the image batch as one clip [N,H,W]
         return metrics.detect_events(volumes, threshold, connectivity, temporal, min_duration, min_volume, max_events), maps
+
+
+def localize_stream(model, frames, tracker, state=None, sigma=None, truncate: float = 4.0, calibration=None, min_std: Optional[float] = None):
+    """One step of a live stream with events carried between calls (`metrics.EventTracker`): the newest
+    frames are scored, their error maps smoothed and calibrated as in `localize_events`, and handed to `tracker.update`.
+    Video model: `frames` `[B,T,C,H,W]` (or the uint8 layouts `score_stateful` takes) are the next T frames of B streams; ONE
+    `score_stateful(errmap=True)` call continues the ConvLSTM `state` (None = fresh streams).  Image model: `frames` `[B,C,H,W]`
+    is the newest frame of B cameras; ONE `score_all`; `state` must be None and None is returned.  The error map only ("mse").
+    Returns (`metrics.TrackUpdate`, maps, state): the events that closed in this step and the causal alarms of its frames, the maps
+    they were made from (`[B,T,1,H,W]` / `[B,1,H,W]`, on the device), and the scoring state for the next call.  The tracker's
+    threshold applies to the maps as made here: with a `calibration` it is a z-score."""
+    from . import metrics
+    if not isinstance(tracker, metrics.EventTracker):
+        raise hip.VadError(f"localize_stream: tracker must be a metrics.EventTracker, got {type(tracker).__name__}")
+    if calibration is not None:
+        min_std = _check_calibration(calibration, "localize_stream", "mse", sigma, truncate, min_std)
+    video = hasattr(model, "score_stateful")
+    if not video and state is not None:
+        raise hip.VadError("localize_stream: the image model carries no state between calls; pass state=None")
+    with torch.no_grad():
+        if video:
+            out = model.score_stateful(frames, state, errmap=True)
+            maps, state = out["errmap"], out["state"]
+        else:
+            maps = model.score_all(frames)["errmap"]
+        if sigma is not None:
+            maps = metrics.smooth_maps(maps, sigma, truncate)
+        if calibration is not None:
+            maps = calibration.normalize(maps, min_std, out=maps)
+        update = tracker.update(maps if video else maps[:, 0])
+    return update, maps, state
