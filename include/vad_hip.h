@@ -852,6 +852,32 @@ int vad_smooth_maps(const float* maps, long long n, int h, int w, const float* t
                     void* ws, size_t ws_bytes, void* stream);
 int vad_smooth_tile(int* tile_h, int* tile_w);
 
+/* ------------------------------------------------------------------ Grey morphology of anomaly maps (csrc/map_morph.hip)
+ * The clean-up between the map and its threshold: an opening removes speckle that no Gaussian removes without blurring real
+ * defects, a closing fills pinholes and joins the fragments of one defect.  Flat rectangular structuring element.
+ *
+ * vad_morph_maps: maps = n frames of h x w fp32, contiguous (any h, w >= 1 with h * w <= VAD_MAX_FRAME_PIXELS; 4-byte aligned).
+ * The structuring element is size_h x size_w, each side in 1 .. VAD_MORPH_MAX_SIZE, even sizes included; a side may exceed h or w.
+ * Semantics: scipy.ndimage.grey_erosion / grey_dilation / grey_opening / grey_closing with size=(size_h, size_w), mode="reflect" -
+ * for a flat element, windows clamped to the image with scipy's even-size convention; per axis of length L and size s
+ *   VAD_MORPH_ERODE   out[i] = min x[max(0, i - s/2)       .. min(L - 1, i + (s - 1)/2)]
+ *   VAD_MORPH_DILATE  out[i] = max x[max(0, i - (s - 1)/2) .. min(L - 1, i + s/2)]
+ *   VAD_MORPH_OPEN    dilate(erode(x)),   VAD_MORPH_CLOSE   erode(dilate(x));  the second step clamps its windows to the image on
+ *                     the intermediate image, which has no values outside the frame.
+ * Nothing is rounded; min and max are the IEEE-754-2019 minimum / maximum: a NaN makes exactly the pixels whose window holds it NaN
+ * (open / close: the windows of both steps), -0 orders below +0, +-Inf are ordinary values.  Size 1 x 1 is a copy.  Because the
+ * operations only compare, they commute with a threshold: op(x) >= t is the binary op of x >= t.
+ * out: n x h x w; it must not overlap maps.  VAD_ERR_ARG for an unknown op, a size outside 1 .. VAD_MORPH_MAX_SIZE, n < 0, h or w
+ * out of range, a NULL or misaligned pointer, out overlapping maps.  n == 0 returns VAD_OK and launches nothing.  One launch per
+ * call (open and close included) on `stream`, one read and one write of the maps, no workspace, no allocation, no host
+ * synchronisation: capturable in a graph.
+ * vad_morph_tile reports the output tile of one work-group (rows, columns) for a size and op - what a test needs to build a frame of
+ * several tiles; VAD_ERR_ARG for an unknown op or a size out of range. */
+#define VAD_MORPH_MAX_SIZE 31
+enum { VAD_MORPH_ERODE = 0, VAD_MORPH_DILATE = 1, VAD_MORPH_OPEN = 2, VAD_MORPH_CLOSE = 3 };
+int vad_morph_maps(const float* maps, long long n, int h, int w, int op, int size_h, int size_w, float* out, void* stream);
+int vad_morph_tile(int size_h, int size_w, int op, int* tile_h, int* tile_w);
+
 /* ------------------------------------------------------------------ Defect regions of an anomaly map (csrc/map_regions.hip)
  * What turns a map and an operating threshold into detections: the connected regions of {v >= threshold} of every frame, as a
  * compact table - where they are, how large, how strong.  The maps stay on the device; the table is what leaves it.

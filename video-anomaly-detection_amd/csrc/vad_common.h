@@ -78,6 +78,9 @@ __device__ __forceinline__ unsigned vad_xcd_remap(unsigned b, unsigned nb) {
 // The builtin lowers to v_maximum3_f32 - a max with 0 behind a pair folds into one instruction, no canonicalising v_max(v, v) -
 // and, being no asm statement, gets its MFMA wait states from hipcc.  Same bits as maxNum for operands that are not NaN.
 __device__ __forceinline__ float vad_vmax(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+// The IEEE-754-2019 `minimum` beside it (v_minimum3_f32): NaN if either operand is NaN, -0 below +0.  v_min_f32 / fminf are
+// `minNum` and would drop a NaN from a window (the grey morphology of csrc/map_morph.hip takes its erosions with this).
+__device__ __forceinline__ float vad_vmin(float a, float b) { return __builtin_elementwise_minimum(a, b); }
 __device__ __forceinline__ float vad_vmax4(float a, float b, float c, float d) { return vad_vmax(vad_vmax(a, b), vad_vmax(c, d)); }
 __device__ __forceinline__ float vad_act(float v, int act) {
     if (act == VAD_ACT_LEAKY) return vad_vmax(v, 0.2f * v);

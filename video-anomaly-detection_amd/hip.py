@@ -16,7 +16,7 @@ PKG_DIR = Path(__file__).resolve().parent
 REPO_DIR = PKG_DIR.parent
 CSRC = PKG_DIR / "csrc"
 LIB_PATH = Path(os.environ.get("VAD_LIB", PKG_DIR / "libvad_hip.so"))
-SOURCES = ["conv_mfma.hip", "conv_wino.hip", "dec4_fused.hip", "tail.hip", "wide_io.hip", "state_io.hip", "resize_u8.hip", "frame_gather.hip", "score_hist.hip", "region_overlap.hip", "map_regions.hip", "map_events.hip", "map_track.hip", "map_smooth.hip", "map_stats.hip", "ssim.hip", "train_ops.hip", "wgrad.hip", "train_step.hip", "train_step_img.hip", "vad_api.hip", "pack.cpp"]
+SOURCES = ["conv_mfma.hip", "conv_wino.hip", "dec4_fused.hip", "tail.hip", "wide_io.hip", "state_io.hip", "resize_u8.hip", "frame_gather.hip", "score_hist.hip", "region_overlap.hip", "map_regions.hip", "map_events.hip", "map_track.hip", "map_smooth.hip", "map_morph.hip", "map_stats.hip", "ssim.hip", "train_ops.hip", "wgrad.hip", "train_step.hip", "train_step_img.hip", "vad_api.hip", "pack.cpp"]
 
 VAD_OK = 0
 ABI_VERSION = 3
@@ -58,6 +58,8 @@ TRACK_WORDS = 20          # VAD_TRACK_WORDS: uint32 words of one record of vad_t
 TRACK_HEADER_WORDS = 16   # the header of one stream's tracker state: frames, open, lost in total, flags, magic, h, w, max_open, zeros
 TRACK_MAX_OPEN = 65536    # largest max_open / max_closed of vad_track_events
 TRACK_NO_RECORD = 0xFFFFFFFF   # slot plane: a pixel of an open event behind the table
+MORPH_MAX_SIZE = 31       # VAD_MORPH_MAX_SIZE: largest side of the structuring element of vad_morph_maps
+MORPH_OPS = {"erode": 0, "dilate": 1, "open": 2, "close": 3}   # VAD_MORPH_*
 SMOOTH_TILE = (32, 64)    # csrc/map_smooth.hip SM_TH x SM_TW: the output tile of one work-group (vad_smooth_tile reports the library's)
 MAX_FRAME_PIXELS = 2 ** 23 - 1    # VAD_MAX_FRAME_PIXELS: largest H * W (pixel indices are 24-bit multiply operands inside the kernels)
 FRAME_RULE = f"H and W must be multiples of 16 with H * W <= {MAX_FRAME_PIXELS}"
@@ -305,6 +307,9 @@ SIGNATURES = {
     "vad_smooth_workspace_bytes": (_sz, [_ll, _i, _i, _i]),
     "vad_smooth_maps": (_i, [_vp, _ll, _i, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "vad_smooth_tile": (_i, [C.POINTER(_i), C.POINTER(_i)]),
+    # grey morphology of anomaly maps: erode, dilate, open, close (csrc/map_morph.hip)
+    "vad_morph_maps": (_i, [_vp, _ll, _i, _i, _i, _i, _i, _vp, _vp]),
+    "vad_morph_tile": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
     # defect regions of an anomaly map: boxes, areas, peaks (csrc/map_regions.hip)
     "vad_regions_workspace_bytes": (_sz, [_ll, _i, _i, _i]),
     "vad_detect_regions": (_i, [_vp, _ll, _i, _i, _f, _i, C.c_uint, _i, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -818,6 +818,107 @@ def smooth_maps(maps: torch.Tensor, sigma: float = 4.0, truncate: float = 4.0, o
     return (out, fmax) if return_max else out
 
 
+# ====================================================================== grey morphology of anomaly maps
+# The clean-up a deployed line applies between the map and its threshold: an opening removes speckle that no
+# Gaussian removes without blurring real defects, a closing fills pinholes and joins the fragments of one cracked defect.  Flat
+# rectangular structuring element; scipy.ndimage.grey_erosion / grey_dilation / grey_opening / grey_closing to the bit.
+MORPH_MAX_SIZE = hip.MORPH_MAX_SIZE
+MORPH_OPS = tuple(hip.MORPH_OPS)
+MORPH_MAX_STEPS = 4
+
+
+def _morph_size(size, what: str) -> Tuple[int, int]:
+    """An int or (size_h, size_w), each in 1..31 -> (size_h, size_w)."""
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+    if is_int(size):
+        size = (size, size)
+    if not isinstance(size, (tuple, list)) or len(size) != 2 or not all(is_int(v) for v in size):
+        raise hip.VadError(f"{what}: size must be an int or (size_h, size_w), got {size!r}")
+    sh, sw = int(size[0]), int(size[1])
+    if not (1 <= sh <= MORPH_MAX_SIZE and 1 <= sw <= MORPH_MAX_SIZE):
+        raise hip.VadError(f"{what}: size must be in 1..{MORPH_MAX_SIZE} per side, got {sh} x {sw}")
+    return sh, sw
+
+
+def _morph_op(op, what: str) -> str:
+    if not isinstance(op, str) or op not in hip.MORPH_OPS:
+        raise hip.VadError(f"{what}: op must be one of {MORPH_OPS}, got {op!r}")
+    return op
+
+
+def morph_steps(spec) -> Tuple[Tuple[str, Tuple[int, int]], ...]:
+    """What the `morph=` arguments of the scoring entry points take, normalised to a tuple of (op, (size_h, size_w)) steps: None ->
+    (), one step `("open", 3)` / `("open", (3, 5))`, or a list of at most four steps such as `[("open", 2), ("close", 5)]` (despeckle,
+    then join fragments).  `VadError` for anything else: an unknown op, a size outside 1..31, an empty list, more than four steps."""
+    what = "morph_steps"
+    if spec is None:
+        return ()
+    if isinstance(spec, tuple) and len(spec) == 2 and isinstance(spec[0], str):
+        spec = [spec]
+    if not isinstance(spec, list):
+        raise hip.VadError(f"{what}: a spec is None, one step (op, size) or a list of steps, got {spec!r}")
+    if not 1 <= len(spec) <= MORPH_MAX_STEPS:
+        raise hip.VadError(f"{what}: a list holds 1..{MORPH_MAX_STEPS} steps, got {len(spec)}")
+    steps = []
+    for step in spec:
+        if not isinstance(step, (tuple, list)) or len(step) != 2:
+            raise hip.VadError(f"{what}: a step is (op, size), got {step!r}")
+        steps.append((_morph_op(step[0], what), _morph_size(step[1], what)))
+    return tuple(steps)
+
+
+def morph_maps(maps: torch.Tensor, op: str, size, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`scipy.ndimage.grey_erosion` / `grey_dilation` / `grey_opening` / `grey_closing` (`op` = "erode" | "dilate" | "open" | "close")
+    with `size=(size_h, size_w)` (an int = a square) and mode="reflect" of every H x W frame of `maps` on the GPU (`vad_morph_maps`,
+    csrc/map_morph.hip): for a flat rectangle, the minimum / maximum over a window clamped to the frame, even sizes by scipy's
+    convention (erode reaches size // 2 towards index 0, dilate (size - 1) // 2); sides in 1..31, larger than the frame allowed.
+    `maps` as `smooth_maps` takes them: float32 GPU tensor, contiguous, the last two dimensions H, W and any leading ones; frames
+    are processed one by one.  Nothing is rounded, so the result is specified to the bit (tests/map_morph_ref.py): a NaN makes
+    exactly the pixels whose window holds it NaN (open / close: the windows of both steps), -0 orders below +0.  The operations
+    commute with a threshold: `morph_maps(x, op, s) >= t` is the binary `op` of `x >= t`.  Returns a new tensor, or `out` (same
+    shape, float32, contiguous, not overlapping `maps`).  One launch, no workspace; asynchronous on the current stream."""
+    what = "morph_maps"
+    if not isinstance(maps, torch.Tensor):
+        raise hip.VadError(f"{what}: maps must be a torch tensor")
+    code = hip.MORPH_OPS[_morph_op(op, what)]
+    sh, sw = _morph_size(size, what)
+    if not maps.is_cuda:
+        raise hip.VadError(f"{what}: maps ({maps.device}) must be on the GPU (the morphology runs on the device; there is no CPU fallback)")
+    if maps.dtype != torch.float32:
+        raise hip.VadError(f"{what}: maps must be float32, got {maps.dtype}")
+    if maps.dim() < 2:
+        raise hip.VadError(f"{what}: maps must have at least the two dimensions H, W, got {tuple(maps.shape)}")
+    if not maps.is_contiguous():
+        raise hip.VadError(f"{what}: maps must be contiguous (got strides {tuple(maps.stride())} for {tuple(maps.shape)}); it is not copied silently")
+    lead, h, w = tuple(maps.shape[:-2]), int(maps.shape[-2]), int(maps.shape[-1])
+    if h < 1 or w < 1 or h * w > hip.MAX_FRAME_PIXELS:
+        raise hip.VadError(f"{what}: frames of {h} x {w} are out of range (H, W >= 1 and H * W <= {hip.MAX_FRAME_PIXELS})")
+    if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(maps.shape) or out.dtype != torch.float32
+                            or out.device != maps.device or not out.is_contiguous()):
+        raise hip.VadError(f"{what}: out must be a contiguous float32 tensor {tuple(maps.shape)} on {maps.device}")
+    n = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    with torch.cuda.device(maps.device):
+        if out is None:
+            out = torch.empty_like(maps)
+        if n > 0:
+            hip.check(hip.lib().vad_morph_maps(maps.data_ptr(), n, h, w, code, sh, sw, out.data_ptr(), hip.current_stream()), "vad_morph_maps")
+            hip.calls["morph_maps"] = hip.calls.get("morph_maps", 0) + 1
+    return out
+
+
+def apply_morph(maps: torch.Tensor, steps) -> torch.Tensor:
+    """`maps` through the steps of `morph_steps(...)`, one launch per step.  One step returns a new tensor; a list ping-pongs two
+    buffers of its own, so `maps` is never written.  No steps: `maps` itself."""
+    bufs = []
+    for op, size in steps:
+        if len(bufs) < 2:
+            bufs.append(morph_maps(maps, op, size))
+        else:
+            bufs.append(morph_maps(maps, op, size, out=bufs[-2]))
+        maps = bufs[-1]
+    return maps
+
+
 # ====================================================================== defect regions of an anomaly map
 # What a deployed line needs after the thresholds above (DESIGN.md section 4.16): which connected regions of a frame's map are at or
 # above the operating threshold, where they are, how large and how strong - as a compact table per frame, not as a picture.  The

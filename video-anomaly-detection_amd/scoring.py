@@ -379,9 +379,10 @@ def score_stream(model, seed: int, n_frames: int, chunk: int = 512, h: int = 256
 
 
 # ------------------------------------------------------------------------------ ranking metrics on the device
-def _anomaly_maps(model, images, map: str, sigma, truncate, calibration=None, min_std=None):
+def _anomaly_maps(model, images, map: str, sigma, truncate, calibration=None, min_std=None, morph=()):
     """The batch's anomaly map [B,1,H,W] of the pixel metrics: the error map or the SSIM map, through `metrics.smooth_maps` when a
-    sigma is given, then - with a `calibration` - turned into its z-score in place (the map is this call's own)."""
+    sigma is given, then - with a `calibration` - turned into its z-score in place (the map is this call's own), then through the
+    steps of `morph` (`metrics.morph_steps`), in z-score units when calibrated."""
     from . import metrics
     if map == "mse":
         values = model.score_all(images)["errmap"]
@@ -391,6 +392,8 @@ def _anomaly_maps(model, images, map: str, sigma, truncate, calibration=None, mi
         values = metrics.smooth_maps(values, sigma, truncate)
     if calibration is not None:
         values = calibration.normalize(values, min_std, out=values)
+    if morph:
+        values = metrics.apply_morph(values, morph)
     return values
 
 
@@ -444,7 +447,7 @@ def calibrate(model, loader: Iterable[dict], device, map: str = "mse", sigma=Non
 
 
 def pixel_auroc(model, loader: Iterable[dict], device, map: str = "mse", mantissa_bits: int = 11, hist=None, sigma=None,
-                truncate: float = 4.0, calibration=None, min_std: Optional[float] = None):
+                truncate: float = 4.0, calibration=None, min_std: Optional[float] = None, morph=None):
     """Pixel-level AUROC of an image model's anomaly map against the ground-truth masks - the localisation metric of MVTec-style
     datasets; the reference loads `sample['mask']` and only plots it beside the map (evaluate.py:142-171).  Batches are
     {'image', 'mask', ...} as `MVTecDataset` yields them (utils/dataset.py:150-156): mask float `[B,1,H,W]` (ToTensor: a pixel is
@@ -462,10 +465,15 @@ def pixel_auroc(model, loader: Iterable[dict], device, map: str = "mse", mantiss
     and `truncate` (`ValueError` otherwise, or for another frame shape) - the map is turned into its per-pixel z-score
     (`MapStatistics.normalize`, floor `min_std`, default `metrics.DEFAULT_MIN_STD`) after the smoothing and before the histogram, in
     place, still on the device.  The histogram bins values >= 0: z-scores below 0 - pixels less anomalous than on the normal frames'
-    average - are counted in `hist.rejected()`, so the curve and its thresholds are those of the z-scores above 0."""
+    average - are counted in `hist.rejected()`, so the curve and its thresholds are those of the z-scores above 0.
+    `morph` (None = no morphology, as before): a `metrics.morph_steps` spec - one step `("open", 3)` / `("close", (3, 5))` or a list of
+    at most four, e.g. `[("open", 2), ("close", 5)]` - applied with `metrics.morph_maps` after the smoothing and the calibration (in
+    z-score units when calibrated) and before the histogram.  `calibrate` takes none: statistics are those of the un-morphed map.
+    Grey morphology commutes with a threshold, so a threshold read from this histogram is the one `localize(morph=...)` takes."""
     from . import metrics
     if map not in ("mse", "ssim"):
         raise hip.VadError(f"pixel_auroc: map must be 'mse' or 'ssim', got {map!r}")
+    morph = metrics.morph_steps(morph)
     if calibration is not None:
         min_std = _check_calibration(calibration, "pixel_auroc", map, sigma, truncate, min_std)
     if hist is None:
@@ -474,13 +482,13 @@ def pixel_auroc(model, loader: Iterable[dict], device, map: str = "mse", mantiss
         for batch in loader:
             images = batch["image"].to(device)
             masks = torch.as_tensor(batch["mask"]).to(device)
-            hist.accumulate(_anomaly_maps(model, images, map, sigma, truncate, calibration, min_std), masks)
+            hist.accumulate(_anomaly_maps(model, images, map, sigma, truncate, calibration, min_std, morph), masks)
     auroc, tie_bound = hist.auroc()
     return auroc, tie_bound, hist
 
 
 def pixel_aupro(model, loader: Iterable[dict], device, map: str = "mse", fpr_limit: float = 0.3, mantissa_bits: int = 11, hist=None,
-                connectivity: int = 8, sigma=None, truncate: float = 4.0, calibration=None, min_std: Optional[float] = None):
+                connectivity: int = 8, sigma=None, truncate: float = 4.0, calibration=None, min_std: Optional[float] = None, morph=None):
     """Per-region overlap (AUPRO) of an image model's anomaly map against the ground-truth masks: every connected anomalous region
     of the masks weighs the same, and the curve is integrated up to a false-positive rate of `fpr_limit` - the localisation metric
     of the MVTec evaluation, where pixel AUROC is dominated by the large defects.  The loop of `pixel_auroc` (same batches, same
@@ -489,10 +497,11 @@ def pixel_aupro(model, loader: Iterable[dict], device, map: str = "mse", fpr_lim
     on the device; the only host read is the counters, once, at the end.  Returns (aupro, quant_bound, weight_bound, hist)
     (`metrics.aupro_from_counts`); pass `hist` to continue an earlier evaluation or to all-reduce before reading, in which case
     its own mantissa_bits and connectivity apply.  `hist.auroc()` is the pixel AUROC of the same evaluation.  `calibration`,
-    `min_std` as in `pixel_auroc`."""
+    `min_std`, `morph` as in `pixel_auroc`."""
     from . import metrics
     if map not in ("mse", "ssim"):
         raise hip.VadError(f"pixel_aupro: map must be 'mse' or 'ssim', got {map!r}")
+    morph = metrics.morph_steps(morph)
     if calibration is not None:
         min_std = _check_calibration(calibration, "pixel_aupro", map, sigma, truncate, min_std)
     if hist is None:
@@ -501,7 +510,7 @@ def pixel_aupro(model, loader: Iterable[dict], device, map: str = "mse", fpr_lim
         for batch in loader:
             images = batch["image"].to(device)
             masks = torch.as_tensor(batch["mask"]).to(device)
-            hist.accumulate(_anomaly_maps(model, images, map, sigma, truncate, calibration, min_std), masks)
+            hist.accumulate(_anomaly_maps(model, images, map, sigma, truncate, calibration, min_std, morph), masks)
     aupro, quant_bound, weight_bound = hist.aupro(fpr_limit)
     return aupro, quant_bound, weight_bound, hist
 
@@ -524,7 +533,7 @@ def frame_auroc(model, loader: Iterable[dict], device, hist=None, mantissa_bits:
 
 
 def localize(model, images, threshold: float, map: str = "mse", sigma=None, truncate: float = 4.0, connectivity: int = 8,
-             min_area: int = 1, max_regions: int = 64, calibration=None, min_std: Optional[float] = None):
+             min_area: int = 1, max_regions: int = 64, calibration=None, min_std: Optional[float] = None, morph=None):
     """Detections of one batch: the model's anomaly maps and the connected regions of `map >= threshold` in them - where the
     reference paints the map (evaluate.py:142-171, main.py:231-250) and compares one scalar with a constant (main.py:282-283).
     `images`: `[B,C,H,W]` frames for the image model, `[B,T,C,H,W]` clips for the video model (map "mse" only; every frame of a
@@ -533,43 +542,49 @@ def localize(model, images, threshold: float, map: str = "mse", sigma=None, trun
     and ONE `metrics.detect_regions` call; nothing but the flag word is read by the host.  Returns (`metrics.Regions`, maps): the
     table with the leading shape `[B]` / `[B,T]`, and the maps it was made from, `[B,1,H,W]` / `[B,T,1,H,W]`, still on the device.
     `calibration`, `min_std` as in `pixel_auroc`: `threshold` is then a z-score (3.0 = three standard deviations of that pixel over
-    the normal frames), the regions are those of `z >= threshold`, and the maps returned are the z-score maps."""
+    the normal frames), the regions are those of `z >= threshold`, and the maps returned are the z-score maps.
+    `morph` as in `pixel_auroc` (one `metrics.morph_maps` launch per step, last in the chain): the regions are those of the morphed
+    maps - `("open", 2)` drops single-pixel speckle before it is labelled, where `min_area` drops it after and cannot cut a
+    one-pixel bridge between two defects - and the maps returned are the morphed maps."""
     from . import metrics
     if map not in ("mse", "ssim"):
         raise hip.VadError(f"localize: map must be 'mse' or 'ssim', got {map!r}")
+    morph = metrics.morph_steps(morph)
     if images.dim() == 5 and map != "mse":
         raise hip.VadError(f"localize: clips [B,T,C,H,W] are localised on the error map only (map='mse'), got {map!r}")
     if calibration is not None:
         min_std = _check_calibration(calibration, "localize", map, sigma, truncate, min_std)
     with torch.no_grad():
-        maps = _anomaly_maps(model, images, map, sigma, truncate, calibration, min_std)
+        maps = _anomaly_maps(model, images, map, sigma, truncate, calibration, min_std, morph)
         return metrics.detect_regions(maps, threshold, connectivity, min_area, max_regions), maps
 
 
 def localize_events(model, images, threshold: float, map: str = "mse", sigma=None, truncate: float = 4.0, calibration=None,
                     min_std: Optional[float] = None, connectivity: int = 8, temporal: int = 9, min_duration: int = 1, min_volume: int = 1,
-                    max_events: int = 64):
+                    max_events: int = 64, morph=None):
     """`localize` with the event table: the model's anomaly maps and the events of `map >= threshold` in them - regions linked
     across consecutive frames (`metrics.detect_events`), so that a line alarms on what persists (`min_duration`) and not on one
     noisy map.  `images`: `[B,T,C,H,W]` clips for the video model (map "mse" only), every clip its own volume; `[N,C,H,W]` frames
     for the image model, the batch in order being N consecutive frames of one camera: one volume.  `map`, `sigma`, `truncate`,
-    `calibration`, `min_std` as in `localize`.  Per batch ONE scoring call, the optional smoothing and calibration calls and ONE
+    `calibration`, `min_std`, `morph` as in `localize`.  Per batch ONE scoring call, the optional smoothing and calibration calls and ONE
     `detect_events` call; nothing but the flag word is read by the host.  Returns (`metrics.Events`, maps): the table with the
     leading shape `[B]` (video) or `()` (image), and the maps it was made from, `[B,T,1,H,W]` / `[N,1,H,W]`, still on the device."""
     from . import metrics
     if map not in ("mse", "ssim"):
         raise hip.VadError(f"localize_events: map must be 'mse' or 'ssim', got {map!r}")
+    morph = metrics.morph_steps(morph)
     if images.dim() == 5 and map != "mse":
         raise hip.VadError(f"localize_events: clips [B,T,C,H,W] are localised on the error map only (map='mse'), got {map!r}")
     if calibration is not None:
         min_std = _check_calibration(calibration, "localize_events", map, sigma, truncate, min_std)
     with torch.no_grad():
-        maps = _anomaly_maps(model, images, map, sigma, truncate, calibration, min_std)
+        maps = _anomaly_maps(model, images, map, sigma, truncate, calibration, min_std, morph)
         volumes = maps if maps.dim() == 5 else maps[:, 0]                 # [B,T,1,H,W], or the image batch as one clip [N,H,W]
         return metrics.detect_events(volumes, threshold, connectivity, temporal, min_duration, min_volume, max_events), maps
 
 
-def localize_stream(model, frames, tracker, state=None, sigma=None, truncate: float = 4.0, calibration=None, min_std: Optional[float] = None):
+def localize_stream(model, frames, tracker, state=None, sigma=None, truncate: float = 4.0, calibration=None, min_std: Optional[float] = None,
+                    morph=None):
     """One step of a live stream with events carried between calls (`metrics.EventTracker`): the newest
     frames are scored, their error maps smoothed and calibrated as in `localize_events`, and handed to `tracker.update`.
     Video model: `frames` `[B,T,C,H,W]` (or the uint8 layouts `score_stateful` takes) are the next T frames of B streams; ONE
@@ -577,8 +592,10 @@ def localize_stream(model, frames, tracker, state=None, sigma=None, truncate: fl
     is the newest frame of B cameras; ONE `score_all`; `state` must be None and None is returned.  The error map only ("mse").
     Returns (`metrics.TrackUpdate`, maps, state): the events that closed in this step and the causal alarms of its frames, the maps
     they were made from (`[B,T,1,H,W]` / `[B,1,H,W]`, on the device), and the scoring state for the next call.  The tracker's
-    threshold applies to the maps as made here: with a `calibration` it is a z-score."""
+    threshold applies to the maps as made here: with a `calibration` it is a z-score.  `morph` as in `localize`: every frame is
+    morphed on its own, so the result does not depend on how the frames are split over calls."""
     from . import metrics
+    morph = metrics.morph_steps(morph)
     if not isinstance(tracker, metrics.EventTracker):
         raise hip.VadError(f"localize_stream: tracker must be a metrics.EventTracker, got {type(tracker).__name__}")
     if calibration is not None:
@@ -596,5 +613,7 @@ def localize_stream(model, frames, tracker, state=None, sigma=None, truncate: fl
             maps = metrics.smooth_maps(maps, sigma, truncate)
         if calibration is not None:
             maps = calibration.normalize(maps, min_std, out=maps)
+        if morph:
+            maps = metrics.apply_morph(maps, morph)
         update = tracker.update(maps if video else maps[:, 0])
     return update, maps, state
