@@ -913,6 +913,63 @@ int vad_detect_regions(const float* maps, long long n, int h, int w, float thres
                        int max_regions, int32_t* labels_or_null, uint32_t* records /* [n, max_regions, 12] */,
                        uint32_t* counts /* [n, 4] */, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ Detections against ground-truth masks (csrc/map_match.hip)
+ * What an operating point is accepted on: how many of the labelled defects it finds, how many false alarms it raises, which pixel
+ * IoU it reaches.  The regions of vad_detect_regions joined with the regions of the frame's mask; maps, masks and both labellings
+ * stay on the device.  Everything is an integer, per frame.
+ *
+ * vad_match_regions: maps = n frames of h x w fp32, contiguous, 4-byte aligned; masks = n x h x w elements in mask_format -
+ * VAD_LBL_U8_ELEM (anomalous iff >= 128) or VAD_LBL_F32_ELEM (iff > 0.5; 4-byte aligned) - with the limits of vad_label_regions.
+ * Predicted foreground is v >= threshold exactly as in vad_detect_regions (a NaN pixel never is and is counted, +Inf always is, a
+ * NaN threshold is refused); its connected regions (connectivity 8 or 4) with area >= min_area (>= 1) are KEPT, and P is the set of
+ * their pixels: a region dropped for its area contributes nothing, its pixels count as background everywhere below.  G is the set
+ * of the mask's anomalous pixels; its connected regions under the same connectivity all count.
+ *     a mask region g       hit(g) = |g & P|;      DETECTED iff hit >= 1     and (double)hit     >= gt_fraction   * (double)area
+ *     a kept prediction p   overlap(p) = |p & G|;  MATCHED  iff overlap >= 1 and (double)overlap >= pred_fraction * (double)area
+ * - one IEEE double multiply and one compare, no fused multiply-add, no division: numpy float64 restates it bit for bit.  Both
+ * fractions are doubles in [0, 1]; 0 means "any shared pixel".  Overlap is shared pixels: adjacency, diagonal too, is none.  A
+ * kept prediction that is not matched is a false alarm.
+ * gt_records, pred_records uint32 [n, max_regions, VAD_MATCH_WORDS], 16-byte aligned; one region is
+ *     word 0   root: the smallest y * w + x of the region
+ *     word 1   area in pixels
+ *     word 2   hit (gt_records) or overlap (pred_records)
+ *     word 3   flags: bit 0 = detected (gt_records) or matched (pred_records)
+ * gt_records holds the frame's mask regions, pred_records its kept predictions, both in ascending order of their roots - raster
+ * order of their first pixel, scipy.ndimage.label's numbering; the first min(count, max_regions) are written (max_regions in
+ * 1 .. 65536), every other record is all-zero.  pred_records words 0-1 are vad_detect_regions' words 0-1 for the same arguments,
+ * gt_records words 0-1 the roots and sizes of vad_label_regions.
+ * counts uint64 [n, VAD_MATCH_COUNTS], 8-byte aligned, per frame:
+ *     words 0-1    mask regions; detected mask regions
+ *     words 2-4    kept predictions; matched predictions; false alarms (word 2 - word 3)
+ *     word 5       predictions dropped for their area
+ *     words 6-9    pixels of P & G (true positives), of P \ G (false positives), of G \ P (false negatives), of neither
+ *     word 10      NaN pixels of the map (they fall into words 8 or 9 by their mask)
+ *     word 11      |G|
+ *     words 12-15  the frame's class, one-hot: mask regions and kept predictions; no mask region but kept predictions; mask regions
+ *                  but no kept prediction; neither
+ * The region counters are the full numbers, which may exceed max_regions: truncation is visible.  Every word sums over frames; the
+ * sum of words 12-15 is the number of frames.  Integer atomics only: all three outputs are the same words for any batching, launch
+ * order or tiling.
+ * ws: caller-provided, 16-byte aligned, vad_match_workspace_bytes(n, h, w) bytes (0 for arguments out of range; no device is
+ * needed): 16 bytes for the flag word - the first uint32; the second uint32 is what the labelling of the masks reported, folded
+ * into the first -, 8 bytes per chunk of 1024 pixels of every frame (two chunk counters; padded to 16), then 24 bytes per pixel:
+ * 4 each for the two label planes, the two size planes and the per-root hit and overlap planes.  Every walk of the union-find is
+ * bounded as in vad_label_regions; one that runs out of its budget sets bit 0 of the flag word.
+ * vad_match_plan reports the pixels of a frame that one grid round of each pass covers (the labeller, the join, the count / slot
+ * scan) and the threads of a work-group - what a test needs to build a frame larger than one round of every pass.
+ * VAD_ERR_ARG for a NULL or misaligned pointer, an unknown mask_format, n, h, w out of range, a connectivity other than 4 or 8,
+ * min_area == 0, max_regions out of range, a NaN threshold and a fraction that is NaN or outside [0, 1]; VAD_ERR_WS for a short
+ * workspace.  n == 0 clears the flag word only.  Every launch is asynchronous on `stream`; nothing is allocated, the host never
+ * waits, the call can be captured into a graph. */
+#define VAD_MATCH_WORDS 4
+#define VAD_MATCH_COUNTS 16
+size_t vad_match_workspace_bytes(long long n, int h, int w);
+int vad_match_regions(const float* maps, const void* masks, int mask_format, long long n, int h, int w, float threshold,
+                      int connectivity, unsigned min_area, double gt_fraction, double pred_fraction, int max_regions,
+                      uint32_t* gt_records /* [n, max_regions, 4] */, uint32_t* pred_records /* [n, max_regions, 4] */,
+                      uint64_t* counts /* [n, 16] */, void* ws, size_t ws_bytes, void* stream);
+int vad_match_plan(int* label_round, int* join_round, int* scan_round, int* threads);
+
 /* ------------------------------------------------------------------ Anomaly events of a clip (csrc/map_events.hip)
  * Regions linked across the frames of a clip: an event is a connected component of {v >= threshold} in the volume [t, h, w] of one
  * clip.  The predicate is the one of vad_detect_regions (a NaN pixel never is foreground and is counted, +Inf always is, a NaN

@@ -16,7 +16,7 @@ PKG_DIR = Path(__file__).resolve().parent
 REPO_DIR = PKG_DIR.parent
 CSRC = PKG_DIR / "csrc"
 LIB_PATH = Path(os.environ.get("VAD_LIB", PKG_DIR / "libvad_hip.so"))
-SOURCES = ["conv_mfma.hip", "conv_wino.hip", "dec4_fused.hip", "tail.hip", "wide_io.hip", "state_io.hip", "resize_u8.hip", "frame_gather.hip", "score_hist.hip", "region_overlap.hip", "map_regions.hip", "map_events.hip", "map_track.hip", "map_smooth.hip", "map_morph.hip", "map_stats.hip", "ssim.hip", "train_ops.hip", "wgrad.hip", "train_step.hip", "train_step_img.hip", "vad_api.hip", "pack.cpp"]
+SOURCES = ["conv_mfma.hip", "conv_wino.hip", "dec4_fused.hip", "tail.hip", "wide_io.hip", "state_io.hip", "resize_u8.hip", "frame_gather.hip", "score_hist.hip", "region_overlap.hip", "map_regions.hip", "map_match.hip", "map_events.hip", "map_track.hip", "map_smooth.hip", "map_morph.hip", "map_stats.hip", "ssim.hip", "train_ops.hip", "wgrad.hip", "train_step.hip", "train_step_img.hip", "vad_api.hip", "pack.cpp"]
 
 VAD_OK = 0
 ABI_VERSION = 3
@@ -52,6 +52,8 @@ MAX_WIDTH = 4096          # VAD_MAX_WIDTH: largest latent_dim / lstm_hidden_dim
 SMOOTH_MAX_RADIUS = 32    # VAD_SMOOTH_MAX_RADIUS: largest Gaussian radius of vad_smooth_maps (sigma 8 at truncate 4)
 REGION_WORDS = 12         # VAD_REGION_WORDS: uint32 words of one record of vad_detect_regions
 MAX_REGIONS = 65536       # largest max_regions of vad_detect_regions
+MATCH_WORDS = 4           # VAD_MATCH_WORDS: uint32 words of one record of vad_match_regions
+MATCH_COUNTS = 16         # VAD_MATCH_COUNTS: uint64 counters per frame of vad_match_regions
 EVENT_WORDS = 16          # VAD_EVENT_WORDS: uint32 words of one record of vad_detect_events
 MAX_EVENTS = 65536        # largest max_events of vad_detect_events
 TRACK_WORDS = 20          # VAD_TRACK_WORDS: uint32 words of one record of vad_track_events
@@ -87,7 +89,9 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     # pack.cpp: the resize planner's doubles must round operation by operation (its function-level pragma says the same)
     # map_smooth.hip: every product and sum of the smoothing rounds on its own, so numpy float32 restates it bit for bit
     # map_stats.hip: the float64 sums of the per-pixel statistics and the fp32 z-score likewise (tests/map_stats_ref.py)
-    extra = {"pack.cpp": ["-ffp-contract=off"], "map_smooth.hip": ["-ffp-contract=off"], "map_stats.hip": ["-ffp-contract=off"]}
+    # map_match.hip: the fraction tests are one double multiply and one compare (tests/match_ref.py)
+    extra = {"pack.cpp": ["-ffp-contract=off"], "map_smooth.hip": ["-ffp-contract=off"], "map_stats.hip": ["-ffp-contract=off"],
+             "map_match.hip": ["-ffp-contract=off"]}
 
     def compile_one(src: Path) -> Path:
         obj = objdir / (src.name + ".o")
@@ -313,6 +317,10 @@ SIGNATURES = {
     # defect regions of an anomaly map: boxes, areas, peaks (csrc/map_regions.hip)
     "vad_regions_workspace_bytes": (_sz, [_ll, _i, _i, _i]),
     "vad_detect_regions": (_i, [_vp, _ll, _i, _i, _f, _i, C.c_uint, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # detections against ground-truth masks: matched regions, pixel classes (csrc/map_match.hip)
+    "vad_match_workspace_bytes": (_sz, [_ll, _i, _i]),
+    "vad_match_regions": (_i, [_vp, _vp, _i, _ll, _i, _i, _f, _i, C.c_uint, C.c_double, C.c_double, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "vad_match_plan": (_i, [C.POINTER(_i)] * 4),
     # anomaly events of a clip: regions linked across frames (csrc/map_events.hip)
     "vad_events_workspace_bytes": (_sz, [_ll, _i, _i, _i, _i]),
     "vad_detect_events": (_i, [_vp, _ll, _i, _i, _i, _f, _i, _i, C.c_uint, C.c_uint, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -24,6 +24,9 @@ scipy's Gaussian on the device and give the per-frame maximum of the smoothed ma
 The last part is what comes behind them on a deployed line: `detect_regions` (csrc/map_regions.hip) turns a map and an operating
 threshold into a table of connected regions per frame - box, area, peak, centroid sums - without a map leaving the device; `detect_events` (csrc/map_events.hip) links those regions across the frames of a
 clip into events - first and last frame, union box, peak, volume - and counts per frame the pixels of the events that persist.
+`match_regions` (csrc/map_match.hip) joins the detections of `detect_regions` with the masks' regions of `label_regions` - which
+labelled defects an operating point finds, which detections are false alarms, the pixel classes - and `DetectionCounts` sums its
+sixteen counters per frame into the report a line is accepted on.
 
 Across all of them sits the calibration: `MapStatistics` (csrc/map_stats.hip) holds the per-pixel mean and standard deviation of the
 map over normal frames and turns a map into its z-score, which is then smoothed-and-ranked, thresholded and labelled like a raw map.
@@ -1044,6 +1047,229 @@ def detect_regions(maps: torch.Tensor, threshold: float, connectivity: int = 8, 
     _raise_on_flags(int(ws[:4].view(torch.int32).item()), what)
     return Regions(records.view(*lead, max_regions, REGION_WORDS), counts.view(*lead, 4),
                    labels.view(*lead, h, w) if return_labels else None, (h, w), float(np.float32(threshold)), connectivity, min_area)
+
+
+# ====================================================================== detections against ground-truth masks
+# The link between the operating point and the ranking metrics: with a threshold, a min_area, a morph list
+# and a calibration chosen, how many of the labelled defects are found, how many false alarms are raised per frame, which pixel IoU
+# is reached.  AUROC and AUPRO rank pixels over all thresholds and know nothing of min_area or of regions as units; the host route
+# copies every map and mask and runs scipy.ndimage label / sum_labels of one labelling under the other.
+MATCH_WORDS = hip.MATCH_WORDS
+MATCH_COUNTS = hip.MATCH_COUNTS
+COUNT_NAMES = ("gt_regions", "gt_detected", "pred_regions", "pred_matched", "false_alarms", "pred_dropped", "pixel_tp", "pixel_fp",
+               "pixel_fn", "pixel_tn", "nan_pixels", "gt_pixels", "frames_gt_pred", "frames_pred_only", "frames_gt_only", "frames_neither")
+
+
+class Matches:
+    """What `match_regions` returns, as device tensors with the leading shape of the maps (`[B]`, or `[B,T]` for clips):
+
+      gt_records    int32 [..., R, 4]: the mask's regions of a frame - root, area, hit = pixels shared with kept predictions, flags
+                    (bit 0: detected) - in raster order of their first pixel, R = max_regions, all-zero records behind them
+      pred_records  int32 [..., R, 4]: the kept predicted regions - root, area, overlap = pixels shared with the mask, flags (bit 0:
+                    matched; a kept prediction that is not matched is a false alarm) - in the same order
+      counts        int64 [..., 16]: the words of `vad_match_regions` (include/vad_hip.h), named by `COUNT_NAMES`; the region
+                    counters are the full numbers, so a truncated table is visible
+
+    Views of the records (no copies): `gt_area`, `gt_hit`, `pred_area`, `pred_overlap` int32 [..., R]; `gt_detected`, `pred_matched`
+    bool [..., R]."""
+
+    def __init__(self, gt_records: torch.Tensor, pred_records: torch.Tensor, counts: torch.Tensor, frame_shape: Tuple[int, int], params: dict):
+        self.gt_records, self.pred_records, self.counts = gt_records, pred_records, counts
+        self.frame_shape, self.params = frame_shape, dict(params)
+        self.max_regions = int(gt_records.shape[-2])
+
+    gt_area = property(lambda self: self.gt_records[..., 1])
+    gt_hit = property(lambda self: self.gt_records[..., 2])
+    gt_detected = property(lambda self: (self.gt_records[..., 3] & 1) != 0)
+    pred_area = property(lambda self: self.pred_records[..., 1])
+    pred_overlap = property(lambda self: self.pred_records[..., 2])
+    pred_matched = property(lambda self: (self.pred_records[..., 3] & 1) != 0)
+
+    def truncated(self) -> torch.Tensor:
+        """bool [...]: the frame has more mask regions or more kept predictions than a table has records."""
+        return (self.counts[..., 0] > self.max_regions) | (self.counts[..., 2] > self.max_regions)
+
+    def to_list(self) -> list:
+        """A host copy of the tables - 16 bytes per record, never a map -: one dict per frame (frames in row-major order of the
+        leading shape) {'gt': [{'root', 'area', 'hit', 'detected'}], 'pred': [{'root', 'area', 'overlap', 'matched'}], 'counts':
+        {name: int}} in table order."""
+        gt = self.gt_records.reshape(-1, self.max_regions, MATCH_WORDS).cpu().numpy()
+        pred = self.pred_records.reshape(-1, self.max_regions, MATCH_WORDS).cpu().numpy()
+        counts = self.counts.reshape(-1, MATCH_COUNTS).cpu().numpy()
+        out = []
+        for f in range(counts.shape[0]):
+            out.append({"gt": [{"root": int(r[0]), "area": int(r[1]), "hit": int(r[2]), "detected": bool(r[3] & 1)}
+                               for r in gt[f, :min(int(counts[f, 0]), self.max_regions)]],
+                        "pred": [{"root": int(r[0]), "area": int(r[1]), "overlap": int(r[2]), "matched": bool(r[3] & 1)}
+                                 for r in pred[f, :min(int(counts[f, 2]), self.max_regions)]],
+                        "counts": {name: int(v) for name, v in zip(COUNT_NAMES, counts[f])}})
+        return out
+
+
+def _check_fraction(v, name: str, what: str) -> float:
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) <= 1.0:   # false for NaN
+        raise hip.VadError(f"{what}: {name} must be a number in [0, 1], got {v!r}")
+    return float(v)
+
+
+def _match_params(what: str, threshold, connectivity, min_area, gt_fraction, pred_fraction) -> dict:
+    """The checked operating point of `match_regions` / `DetectionCounts`: what two sets of counters must share to be added."""
+    connectivity = _check_connectivity(connectivity, what)
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)) or np.isnan(threshold):
+        raise hip.VadError(f"{what}: threshold must be a number that is not NaN, got {threshold!r}")
+    if isinstance(min_area, bool) or not isinstance(min_area, (int, np.integer)) or not 1 <= int(min_area) <= 2 ** 32 - 1:
+        raise hip.VadError(f"{what}: min_area must be an int in 1..{2 ** 32 - 1}, got {min_area!r}")
+    return {"threshold": float(np.float32(threshold)), "connectivity": connectivity, "min_area": int(min_area),
+            "gt_fraction": _check_fraction(gt_fraction, "gt_fraction", what), "pred_fraction": _check_fraction(pred_fraction, "pred_fraction", what)}
+
+
+def match_regions(maps: torch.Tensor, masks: torch.Tensor, threshold: float, connectivity: int = 8, min_area: int = 1,
+                  gt_fraction: float = 0.0, pred_fraction: float = 0.0, max_regions: int = 64) -> Matches:
+    """The detections of `maps >= threshold` held against the ground-truth `masks`, on the GPU (`vad_match_regions`,
+    csrc/map_match.hip).  `maps`: float32 GPU tensor `[B,H,W]`, `[B,1,H,W]` or `[B,T,1,H,W]` as in `detect_regions`; `masks`: a GPU
+    tensor of a matching shape in the formats of `label_regions` (float: anomalous iff > 0.5; uint8: iff >= 128; bool and other
+    integers: iff non-zero).  The predicted regions are those of `detect_regions` with the same `threshold`, `connectivity` and
+    `min_area`; a region dropped for its area counts as background.  A mask region is DETECTED iff it shares at least one pixel, and
+    at least `gt_fraction` of its area, with the kept predictions; a kept prediction is MATCHED iff it shares at least one pixel, and
+    at least `pred_fraction` of its area, with the mask - otherwise it is a false alarm.  Both fractions lie in [0, 1]; 0 = any
+    shared pixel.  Touching, diagonally too, is no overlap.  Returns a `Matches`; like `detect_regions` it reads the kernels' flag
+    word (one 4-byte copy, which waits for the call) and raises VadError if it is set.  No CPU fallback."""
+    what = "match_regions"
+    params = _match_params(what, threshold, connectivity, min_area, gt_fraction, pred_fraction)
+    if not isinstance(maps, torch.Tensor) or not isinstance(masks, torch.Tensor):
+        raise hip.VadError(f"{what}: maps and masks must be torch tensors")
+    if maps.dtype != torch.float32:
+        raise hip.VadError(f"{what}: maps must be float32, got {maps.dtype}")
+    if masks.is_complex():
+        raise hip.VadError(f"{what}: masks must be float, uint8, bool or integer, got {masks.dtype}")
+    if isinstance(max_regions, bool) or not isinstance(max_regions, (int, np.integer)) or not 1 <= int(max_regions) <= MAX_REGIONS:
+        raise hip.VadError(f"{what}: max_regions must be an int in 1..{MAX_REGIONS}, got {max_regions!r}")
+    max_regions = int(max_regions)
+    if maps.dim() not in (3, 4, 5) or masks.dim() not in (3, 4, 5) or masks.numel() != maps.numel() or masks.shape[-2:] != maps.shape[-2:] \
+            or masks.shape[0] != maps.shape[0]:
+        raise hip.VadError(f"{what}: masks {tuple(masks.shape)} do not match maps {tuple(maps.shape)}")
+    if not maps.is_cuda or not masks.is_cuda:
+        raise hip.VadError(f"{what}: maps ({maps.device}) and masks ({masks.device}) must be on the GPU (regions are matched on the "
+                           "device; there is no CPU fallback)")
+    if maps.device != masks.device:
+        raise hip.VadError(f"{what}: maps ({maps.device}) and masks ({masks.device}) must be on the same device")
+    frames, lead = _region_frames(maps, what)
+    n, h, w = frames.shape
+    m, fmt, _, _, _ = _mask_planes(masks.reshape(-1, h, w), what)
+    dev = frames.device
+    if n == 0:                                                            # nothing to match, nothing to launch
+        return Matches(torch.zeros((*lead, max_regions, MATCH_WORDS), dtype=torch.int32, device=dev),
+                       torch.zeros((*lead, max_regions, MATCH_WORDS), dtype=torch.int32, device=dev),
+                       torch.zeros((*lead, MATCH_COUNTS), dtype=torch.int64, device=dev), (h, w), params)
+    with torch.cuda.device(dev):
+        l = hip.lib()
+        size = l.vad_match_workspace_bytes(n, h, w)
+        if size == 0:
+            raise hip.VadError(f"{what}: {n} frames of {h} x {w} are out of range (h * w < 2^31 - 1, n * h * w <= 2^38)")
+        ws = torch.empty(size, dtype=torch.uint8, device=dev)
+        gt_records = torch.empty((n, max_regions, MATCH_WORDS), dtype=torch.int32, device=dev)
+        pred_records = torch.empty((n, max_regions, MATCH_WORDS), dtype=torch.int32, device=dev)
+        counts = torch.empty((n, MATCH_COUNTS), dtype=torch.int64, device=dev)
+        hip.check(l.vad_match_regions(frames.data_ptr(), m.data_ptr(), fmt, n, h, w, params["threshold"], params["connectivity"],
+                                      params["min_area"], params["gt_fraction"], params["pred_fraction"], max_regions,
+                                      gt_records.data_ptr(), pred_records.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(),
+                                      hip.current_stream()), "vad_match_regions")
+    hip.calls["match_regions"] = hip.calls.get("match_regions", 0) + 1
+    _raise_on_flags(int(ws[:4].view(torch.int32).item()), what)
+    return Matches(gt_records.view(*lead, max_regions, MATCH_WORDS), pred_records.view(*lead, max_regions, MATCH_WORDS),
+                   counts.view(*lead, MATCH_COUNTS), (h, w), params)
+
+
+def _ratio(num: int, den: int) -> float:
+    """num / den in float64; nan - never 0 or 1 - when there is nothing to divide by."""
+    return float(num) / float(den) if den else float("nan")
+
+
+def report_from_counts(counts) -> dict:
+    """The operating-point report from the 16 sums of `vad_match_regions`' counters (`COUNT_NAMES`), on the host - usable on a
+    machine without a GPU.  Region level: recall = detected / mask regions, precision = matched / kept predictions, F1 their
+    harmonic mean, false alarms per frame.  Pixel level: precision, recall, IoU = TP / (TP + FP + FN), Dice.  Image level (a frame is
+    positive with a mask region, alarmed with a kept prediction): precision, recall, F1.  A ratio whose denominator is 0 is nan."""
+    c = [int(v) for v in np.asarray(counts).reshape(-1)]
+    if len(c) != MATCH_COUNTS or min(c) < 0:
+        raise hip.VadError(f"report_from_counts: counts must be {MATCH_COUNTS} non-negative integers, got {counts!r}")
+    gt, det, pred, matched, fa, _, tp, fp, fn, _, _, _, both, pred_only, gt_only, neither = c
+    frames = both + pred_only + gt_only + neither
+    recall, precision = _ratio(det, gt), _ratio(matched, pred)
+    out = {name: v for name, v in zip(COUNT_NAMES, c)}
+    out.update({"frames": frames, "region_recall": recall, "region_precision": precision,
+                "region_f1": 2.0 * precision * recall / (precision + recall) if precision + recall > 0 else float("nan"),
+                "false_alarms_per_frame": _ratio(fa, frames),
+                "pixel_precision": _ratio(tp, tp + fp), "pixel_recall": _ratio(tp, tp + fn), "pixel_iou": _ratio(tp, tp + fp + fn),
+                "pixel_dice": _ratio(2 * tp, 2 * tp + fp + fn),
+                "image_precision": _ratio(both, both + pred_only), "image_recall": _ratio(both, both + gt_only),
+                "image_f1": _ratio(2 * both, 2 * both + pred_only + gt_only)})
+    return out
+
+
+class DetectionCounts:
+    """The 16 counters of `match_regions` summed over frames: an int64 `[16]` device tensor (`COUNT_NAMES`) and the operating point
+    they were gathered at - `params` = {threshold, connectivity, min_area, gt_fraction, pred_fraction} plus whatever `meta` the
+    caller adds (`scoring.detection_report`: map, sigma, truncate, morph, calibrated).  Counters gathered at another operating point
+    are refused with `ValueError`, as a calibration gathered on other maps is: their sum would describe no setting at all.  Integer
+    sums: the result does not depend on batching or sharding, and ranks combine with ONE all-reduce."""
+
+    def __init__(self, device="cuda", params: Optional[dict] = None):
+        self.counts = torch.zeros(MATCH_COUNTS, dtype=torch.int64, device=device)
+        self.params = dict(params) if params else None
+
+    def _adopt(self, params, what: str) -> None:
+        if params is None:
+            return
+        if self.params is None:
+            self.params = dict(params)
+        elif self.params != dict(params):
+            raise ValueError(f"{what}: these counters were gathered with {self.params}, the others with {dict(params)}")
+
+    def update(self, matches: Matches, meta: Optional[dict] = None) -> "DetectionCounts":
+        """Add the frames of one `match_regions` result (one reduction on the device; nothing is read by the host)."""
+        if not isinstance(matches, Matches):
+            raise hip.VadError(f"DetectionCounts.update: matches must be a metrics.Matches, got {type(matches).__name__}")
+        if matches.counts.device != self.counts.device:
+            raise hip.VadError(f"DetectionCounts.update: the matches are on {matches.counts.device}, the counters on {self.counts.device}")
+        self._adopt({**matches.params, **(meta or {})}, "DetectionCounts.update")
+        self.counts += matches.counts.reshape(-1, MATCH_COUNTS).sum(dim=0)
+        return self
+
+    def merge(self, other: "DetectionCounts") -> "DetectionCounts":
+        """self += other (two streams, two halves of a dataset, or the states of several ranks after a gather)."""
+        if not isinstance(other, DetectionCounts):
+            raise hip.VadError(f"DetectionCounts.merge: other must be a DetectionCounts, got {type(other).__name__}")
+        self._adopt(other.params, "DetectionCounts.merge")
+        self.counts += other.counts.to(self.counts.device)
+        return self
+
+    def all_reduce(self, group=None, force_collective: bool = False) -> int:
+        """Sum the counters over the ranks of `group` (`allreduce_counters_`: one all_reduce).  Every rank must hold counters of the
+        same operating point: this call does NOT check it - the collective carries the 16 words only, and `params` stay this
+        rank's -, so ranks compare their `params` themselves (e.g. `all_gather_object`) where they may differ.  Returns the world
+        size."""
+        return allreduce_counters_(self.counts, group, force_collective)
+
+    def state_dict(self) -> dict:
+        return {"counts": self.counts.cpu().clone(), "params": None if self.params is None else dict(self.params)}
+
+    def load_state_dict(self, state: dict) -> "DetectionCounts":
+        """Replace the counters by a saved state.  An object that already has an operating point takes only a state of the same
+        one (`ValueError` otherwise, nothing changed), like `merge` and `update`; a fresh one adopts the state's."""
+        counts = torch.as_tensor(state["counts"])
+        if counts.dtype != torch.int64 or tuple(counts.shape) != (MATCH_COUNTS,) or bool((counts < 0).any()):
+            raise hip.VadError(f"DetectionCounts.load_state_dict: counts must be {MATCH_COUNTS} non-negative int64 words, got "
+                               f"{counts.dtype} {tuple(counts.shape)}")
+        self._adopt(state.get("params"), "DetectionCounts.load_state_dict")
+        self.counts.copy_(counts)
+        return self
+
+    def report(self) -> dict:
+        """`report_from_counts` of the sums (one 128-byte copy to the host) with the operating point under 'params'."""
+        out = report_from_counts(self.counts.cpu().numpy())
+        out["params"] = None if self.params is None else dict(self.params)
+        return out
 
 
 # ====================================================================== anomaly events of a clip

@@ -515,6 +515,47 @@ def pixel_aupro(model, loader: Iterable[dict], device, map: str = "mse", fpr_lim
     return aupro, quant_bound, weight_bound, hist
 
 
+def detection_report(model, loader: Iterable[dict], device, threshold: float, map: str = "mse", sigma=None, truncate: float = 4.0,
+                     calibration=None, min_std: Optional[float] = None, morph=(), connectivity: int = 8, min_area: int = 1,
+                     gt_fraction: float = 0.0, pred_fraction: float = 0.0, counts=None):
+    """What an operating point does against the ground-truth masks: how many of the labelled defects it finds, how many false
+    alarms per frame it raises, which pixel IoU it reaches - the questions AUROC and AUPRO, which rank pixels over all thresholds and
+    know nothing of `min_area` or of regions as units, do not answer.  The loop of `pixel_aupro`, over the same batches: {'image'
+    [B,C,H,W], 'mask' [B,1,H,W]} for the image model, {'frames' [B,T,C,H,W], 'mask' [B,T,1,H,W]} for the video model (map "mse" only;
+    every frame is matched on its own).  The maps come from the chain `localize` thresholds (`map`, `sigma`, `truncate`,
+    `calibration`, `min_std`, `morph` as there), so the report is of exactly the detections `localize(threshold, connectivity,
+    min_area)` returns.  Each batch is ONE scoring call, the optional smoothing / calibration / morphology calls and ONE
+    `metrics.match_regions`, whose 16 counters per frame are summed on the device; no map or mask is copied to the host.
+    `gt_fraction`, `pred_fraction` as in `metrics.match_regions`.  Returns (report dict of `metrics.report_from_counts`, the
+    `metrics.DetectionCounts`); pass `counts` to continue an earlier evaluation or to all-reduce before reading
+    (`counts.all_reduce()`, then `counts.report()`) - counters gathered at another operating point are refused with `ValueError`."""
+    from . import metrics
+    what = "detection_report"
+    if map not in ("mse", "ssim"):
+        raise hip.VadError(f"{what}: map must be 'mse' or 'ssim', got {map!r}")
+    morph = metrics.morph_steps(None if morph == () else morph)          # () = no morphology, like None elsewhere
+    if calibration is not None:
+        min_std = _check_calibration(calibration, what, map, sigma, truncate, min_std)
+    params = metrics._match_params(what, threshold, connectivity, min_area, gt_fraction, pred_fraction)
+    meta = dict(_map_meta(map, sigma, truncate), morph=tuple(morph), calibrated=calibration is not None,
+                min_std=None if calibration is None else float(min_std))
+    if counts is None:
+        counts = metrics.DetectionCounts(device)
+    elif not isinstance(counts, metrics.DetectionCounts):
+        raise hip.VadError(f"{what}: counts must be a metrics.DetectionCounts, got {type(counts).__name__}")
+    counts._adopt({**params, **meta}, what)
+    with torch.no_grad():
+        for batch in loader:
+            video = "frames" in batch
+            if video and map != "mse":
+                raise hip.VadError(f"{what}: clips [B,T,C,H,W] are reported on the error map only (map='mse'), got {map!r}")
+            images = batch["frames" if video else "image"].to(device)
+            masks = torch.as_tensor(batch["mask"]).to(device)
+            maps = _anomaly_maps(model, images, map, sigma, truncate, calibration, min_std, morph)
+            counts.update(metrics.match_regions(maps, masks, threshold, connectivity, min_area, gt_fraction, pred_fraction, max_regions=1), meta)
+    return counts.report(), counts
+
+
 def frame_auroc(model, loader: Iterable[dict], device, hist=None, mantissa_bits: int = 11):
     """Frame-level AUROC of a video model (evaluate_video.py:171-176) without gathering the scores: the clip loop of
     `score_clips(per_frame=True)` - batches {'frames' [B,T,C,H,W], 'frame_labels' [B,T], ...} -, each batch's frame scores and
