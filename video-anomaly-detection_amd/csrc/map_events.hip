@@ -14,9 +14,11 @@
 //            once per distinct pair of a wave: a blob over a blob costs a union per wave, not per pixel.
 //   flatten  labels[p] = 1 + root (the smallest volume index of the event: canonical), sizes[root] += 1, last[root] = max t; a lane
 //            gathers its pixels of one root over a run of EV_RUN pixels, equal roots of a wave are combined before the atomics
+//            (wave_each_key of region_table.h, as in every flush below)
 //   count    a volume is cut into chunks of EV_CHUNK pixels; chunk c of clip b counts its kept roots (last - t0 + 1 >= min_duration
 //            and sizes >= min_volume; t0 is the root's own frame) and its dropped roots into chunk_kept[b][c]
-//   slot     the rank of a kept root = the kept roots of the chunks before it + those in front of it inside its chunk: ascending
+//   slot     the rank of a kept root = the kept roots of the chunks before it + those in front of it inside its chunk (block_sum,
+//            chunk_rank_row of region_table.h): ascending
 //            roots across the whole volume.  A root of rank r < max_events gets slot r + 1 and its record's first words and the
 //            identities of the reductions; a kept root behind the table gets EV_SLOT_NO_RECORD (its pixels still count as kept);
 //            any other root gets 0.  The slot takes the place of the root's last frame, which its record now holds.  The
@@ -28,30 +30,20 @@
 // asynchronous on the caller's stream, nothing is allocated, the host never waits.  No loop without a bound known at launch.
 #include <hip/hip_runtime.h>
 
-#include "region_label.h"
+#include "region_table.h"
 #include "vad_common.h"
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int EV_THREADS = 256;
-constexpr unsigned EV_CHUNK = 1024;              // pixels of one chunk of the count / slot passes
-constexpr unsigned EV_RUN = 4096;                // pixels a work-group of the link, flatten and reduce passes takes at a time
+constexpr int EV_THREADS = REGION_THREADS;
+constexpr unsigned EV_CHUNK = REGION_CHUNK;
+constexpr unsigned EV_RUN = 4096;               // pixels a work-group of the link, flatten and reduce passes takes at a time
 constexpr unsigned EV_VOLUME_BLOCKS_X = 4096;    // rebase: 2^20 pixels of a clip per grid round
 constexpr unsigned EV_SCAN_BLOCKS_X = 1024;      // count, slot: 2^20 pixels per round
 constexpr unsigned EV_REDUCE_BLOCKS_X = 256;     // link, flatten, reduce: 2^20 pixels per round; the clips of a call fill the device
 static_assert(EV_VOLUME_BLOCKS_X * EV_THREADS == EV_REDUCE_BLOCKS_X * EV_RUN, "vad_events_plan reports one round for the passes over a volume");
 constexpr int EV_MAX_EVENTS = 65536;
 constexpr unsigned EV_SLOT_NO_RECORD = 0xffffffffu;
-
-__device__ __forceinline__ unsigned order_key(unsigned bits) { return (bits & 0x80000000u) ? ~bits : bits | 0x80000000u; }
-__device__ __forceinline__ unsigned order_key_inv(unsigned key) { return (key & 0x80000000u) ? key & 0x7fffffffu : ~key; }
-
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-    for (int m = 32; m >= 1; m >>= 1) v += (unsigned)__shfl_xor((int)v, m);
-    return v;
-}
 
 struct EventP {
     const float* maps;
@@ -104,26 +96,16 @@ __global__ __launch_bounds__(EV_THREADS) void events_link_kernel(EventP p) {
             const bool direct = fg && L[q] != 0;
             // Uniting the two pixels' parents unites the pixels.  After the labelling a parent is the frame's root of the region, so
             // the lanes of a wave that sit in one region over one region hold the same pair: one union for the pair, by its first
-            // lane.  The loop only elects those lanes (wave-uniform, every round retires at least the leading lane); the unions
-            // then run side by side.  A lane that meets the pair of its previous pixel again - 256 pixels on in the same run, the
-            // same blob - skips it: that union was made, by this lane or by the one elected for it, before the wave went on.
+            // lane.  wave_elect_pair only elects those lanes; the unions then run side by side.  A lane that meets the pair of its
+            // previous pixel again - 256 pixels on in the same run, the same blob - skips it: that union was made, by this lane or
+            // by the one elected for it, before the wave went on.
             const unsigned pa = direct ? (unsigned)label_load(L + i) - 1u : 0u, pb = direct ? (unsigned)label_load(L + q) - 1u : 0u;
-            bool pending = direct && (pa != seen_a || pb != seen_b), elected = false;
+            const bool pending = direct && (pa != seen_a || pb != seen_b);
             if (direct) {
                 seen_a = pa;
                 seen_b = pb;
             }
-            u64 left = __ballot(pending);
-            while (left != 0) {
-                const int lead = __builtin_ctzll(left);
-                const unsigned a0 = (unsigned)__builtin_amdgcn_readlane((int)pa, lead), b0 = (unsigned)__builtin_amdgcn_readlane((int)pb, lead);
-                const bool mine = pending && pa == a0 && pb == b0;
-                const u64 same = __ballot(mine);
-                if (lane == (unsigned)lead) elected = true;
-                if (mine) pending = false;
-                left &= ~same;
-            }
-            if (elected) {
+            if (wave_elect_pair(pending, pa, pb, lane)) {
                 // the wave before may have made this union already: the same parent, or pb itself as pa's parent
                 const unsigned ga = (unsigned)label_load(L + pa) - 1u, gb = (unsigned)label_load(L + pb) - 1u;
                 if (ga != gb && ga != pb) failed |= !label_union(L, pa, pb, budget);
@@ -131,53 +113,36 @@ __global__ __launch_bounds__(EV_THREADS) void events_link_kernel(EventP p) {
             if (!fg || direct || p.temporal != 9) continue;
             const unsigned pix = i % npix;
             const unsigned y = pix / w, x = pix - y * w;
-            // the ring of the 3 x 3 around q, clockwise from above-left: consecutive ring pixels are neighbours in their frame
+            // the set pixels of the ring of the 3 x 3 around q
             unsigned ring = 0u;
 #pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int dy = k < 3 ? -1 : (k == 3 || k == 7) ? 0 : 1;
-                const int dx = (k == 0 || k >= 6) ? -1 : (k == 1 || k == 5) ? 0 : 1;
-                const bool inside = (dy >= 0 || y > 0u) && (dy <= 0 || y + 1u < h) && (dx >= 0 || x > 0u) && (dx <= 0 || x + 1u < w);
-                if (inside && L[(int)q + dy * (int)w + dx] != 0) ring |= 1u << k;
-            }
+            for (int k = 0; k < 8; ++k)
+                if (ring_inside(y, x, h, w, k) && L[(int)q + ring_dy(k) * (int)w + ring_dx(k)] != 0) ring |= 1u << k;
             if (ring == 0xffu) ring = 1u;                    // a closed ring is one run
             else ring &= ~((ring << 1) | (ring >> 7));       // the first pixel of every run
 #pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int dy = k < 3 ? -1 : (k == 3 || k == 7) ? 0 : 1;
-                const int dx = (k == 0 || k >= 6) ? -1 : (k == 1 || k == 5) ? 0 : 1;
-                if (ring & (1u << k)) failed |= !label_union(L, i, (unsigned)((int)q + dy * (int)w + dx), budget);
-            }
+            for (int k = 0; k < 8; ++k)
+                if (ring & (1u << k)) failed |= !label_union(L, i, (unsigned)((int)q + ring_dy(k) * (int)w + ring_dx(k)), budget);
         }
     }
     if (failed) atomicOr(p.flags, VAD_LABEL_FLAG_WALK);
 }
 
-// Adds the lanes' gathered pixel counts and last frames to their roots.  `pending` lanes hold a root; equal roots of the wave are
-// combined first.  Called in converged control flow (the loop is wave-uniform; every round retires at least the leading lane).
+// Adds the lanes' gathered pixel counts and last frames to their roots: `pending` lanes hold a root, equal roots of the wave are
+// combined first.
 __device__ __forceinline__ void events_sizes_flush(bool pending, unsigned root, unsigned n, unsigned t, unsigned* S, unsigned* last,
                                                    unsigned lane) {
-    u64 left = __ballot(pending);
-    while (left != 0) {
-        const int lead = __builtin_ctzll(left);
-        const unsigned first = (unsigned)__builtin_amdgcn_readlane((int)root, lead);
-        const bool mine = pending && root == first;
-        const u64 same = __ballot(mine);
+    wave_each_key(pending, root, lane, [&](unsigned first, bool mine, bool many, bool lead) {
         unsigned sum = mine ? n : 0u, latest = mine ? t : 0u;
-        if ((same & (same - 1ull)) != 0) {                               // wave-uniform: more than one lane holds this root
+        if (many) {
             sum = wave_sum(sum);
-            for (int m = 32; m >= 1; m >>= 1) {
-                const unsigned other = (unsigned)__shfl_xor((int)latest, m);
-                latest = other > latest ? other : latest;
-            }
+            latest = wave_max(latest);
         }
-        if (lane == (unsigned)lead) {
+        if (lead) {
             atomicAdd(S + first, sum);
             atomicMax(last + first, latest);
         }
-        if (mine) pending = false;
-        left &= ~same;
-    }
+    });
 }
 
 __global__ __launch_bounds__(EV_THREADS) void events_flatten_kernel(EventP p) {
@@ -229,39 +194,31 @@ __device__ __forceinline__ bool events_kept(const EventP& p, unsigned i, unsigne
 // kept / dropped roots per chunk, packed into one word (a chunk holds at most EV_CHUNK of either)
 static_assert(EV_CHUNK < 65536u, "kept and dropped roots of a chunk share a word");
 __global__ __launch_bounds__(EV_THREADS) void events_count_kernel(EventP p) {
-    __shared__ unsigned s_kept, s_dropped;
+    __shared__ unsigned s_n[2];
     for (long long clip = blockIdx.y; clip < p.b; clip += gridDim.y) {
         const int* L = p.labels + clip * (long long)p.vol;
         const unsigned* S = p.sizes + clip * (long long)p.vol;
         const unsigned* last = p.aux + clip * (long long)p.vol;
         for (unsigned c = blockIdx.x; c < p.nchunks; c += gridDim.x) {   // uniform over the work-group
-            if (threadIdx.x == 0) s_kept = s_dropped = 0u;
-            __syncthreads();
-            unsigned kept = 0u, dropped = 0u;
+            block_sum_clear<2>(s_n);
+            unsigned n[2] = {0u, 0u};                                    // kept, dropped
             for (unsigned j = 0; j < EV_CHUNK / EV_THREADS; ++j) {
                 const unsigned i = c * EV_CHUNK + j * EV_THREADS + threadIdx.x;        // < 2^31 + 1024: no wrap
                 if (i < p.vol && L[i] == (int)(i + 1u)) {
-                    if (events_kept(p, i, S[i], last[i])) ++kept;
-                    else ++dropped;
+                    if (events_kept(p, i, S[i], last[i])) ++n[0];
+                    else ++n[1];
                 }
             }
-            kept = wave_sum(kept);
-            dropped = wave_sum(dropped);
-            if ((threadIdx.x & 63u) == 0u) {
-                if (kept) atomicAdd(&s_kept, kept);
-                if (dropped) atomicAdd(&s_dropped, dropped);
-            }
-            __syncthreads();
-            if (threadIdx.x == 0) p.chunk_kept[clip * (long long)p.nchunks + c] = s_kept | (s_dropped << 16);
-            __syncthreads();
+            block_sum(n, s_n);
+            if (threadIdx.x == 0) p.chunk_kept[clip * (long long)p.nchunks + c] = n[0] | (n[1] << 16);
+            __syncthreads();                                             // s_n is cleared again for the next chunk
         }
     }
 }
 
 // ranks of the kept roots in ascending order; the records' first words and the identities of the reductions
 __global__ __launch_bounds__(EV_THREADS) void events_slot_kernel(EventP p) {
-    __shared__ unsigned s_before, s_dropped, s_wave[EV_THREADS / 64];
-    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    __shared__ unsigned s_sum[2], s_wave[1][REGION_WAVES];
     for (long long clip = blockIdx.y; clip < p.b; clip += gridDim.y) {
         const int* L = p.labels + clip * (long long)p.vol;
         const unsigned* S = p.sizes + clip * (long long)p.vol;
@@ -269,25 +226,20 @@ __global__ __launch_bounds__(EV_THREADS) void events_slot_kernel(EventP p) {
         const unsigned* kept_of = p.chunk_kept + clip * (long long)p.nchunks;
         unsigned* rec = p.records + (u64)clip * p.max_events * VAD_EVENT_WORDS;
         for (unsigned c = blockIdx.x; c < p.nchunks; c += gridDim.x) {   // uniform over the work-group
-            if (threadIdx.x == 0) s_before = s_dropped = 0u;
-            __syncthreads();
+            block_sum_clear<2>(s_sum);
             // the clip's last chunk also sums the whole clip: its work-group writes the clip's kept / dropped counts, no atomics
             const bool last_chunk = c + 1u == p.nchunks;
-            unsigned before = 0u, dropped = 0u;
+            unsigned sum[2] = {0u, 0u};                                  // the kept roots in front of the chunk; the dropped ones
             for (unsigned k = threadIdx.x; k < c + (last_chunk ? 1u : 0u); k += EV_THREADS) {
                 const unsigned v = kept_of[k];
-                before += k < c ? v & 0xffffu : 0u;
-                dropped += v >> 16;
+                sum[0] += k < c ? v & 0xffffu : 0u;
+                sum[1] += v >> 16;
             }
-            before = wave_sum(before);
-            dropped = wave_sum(dropped);
-            if (lane == 0u && before) atomicAdd(&s_before, before);
-            if (lane == 0u && dropped) atomicAdd(&s_dropped, dropped);
-            __syncthreads();
-            unsigned base = s_before;                                    // the kept roots of this clip in front of the chunk
+            block_sum(sum, s_sum);
+            unsigned base = sum[0];
             if (last_chunk && threadIdx.x == 0) {
-                p.counts[clip * 4] = s_before + (kept_of[c] & 0xffffu);
-                p.counts[clip * 4 + 1] = s_dropped;
+                p.counts[clip * 4] = base + (kept_of[c] & 0xffffu);
+                p.counts[clip * 4 + 1] = sum[1];
             }
             for (unsigned j = 0; j < EV_CHUNK / EV_THREADS; ++j) {
                 const unsigned i = c * EV_CHUNK + j * EV_THREADS + threadIdx.x;
@@ -295,17 +247,7 @@ __global__ __launch_bounds__(EV_THREADS) void events_slot_kernel(EventP p) {
                 const unsigned volume = root ? S[i] : 0u;
                 const unsigned t1 = root ? aux[i] : 0u;
                 const bool kept = root && events_kept(p, i, volume, t1);
-                const u64 b = __ballot(kept);
-                if (lane == 0u) s_wave[wave] = (unsigned)__builtin_popcountll(b);
-                __syncthreads();
-                unsigned rank = base + (unsigned)__builtin_popcountll(b & ((1ull << lane) - 1ull));
-                unsigned row = 0u;
-                for (unsigned k = 0; k < EV_THREADS / 64; ++k) {
-                    if (k < wave) rank += s_wave[k];
-                    row += s_wave[k];
-                }
-                base += row;
-                __syncthreads();                                         // s_wave is written again in the next row
+                const unsigned rank = chunk_rank_row(kept, base, s_wave);
                 if (kept && rank < p.max_events) {
                     aux[i] = rank + 1u;
                     unsigned* r = rec + (u64)rank * VAD_EVENT_WORDS;
@@ -321,74 +263,32 @@ __global__ __launch_bounds__(EV_THREADS) void events_slot_kernel(EventP p) {
     }
 }
 
-struct EventAcc {
-    unsigned slot;           // 0 = nothing gathered
-    unsigned x0, y0, x1, y1;
-    u64 peak, sx, sy, st;
-};
-
-// Adds the lanes' gathered values to their records.  `pending` lanes hold a slot in 1 .. max_events; equal slots of the wave are
-// combined first.  Called in converged control flow (the loop is wave-uniform; every round retires at least the leading lane).
-__device__ __forceinline__ void events_flush(bool pending, const EventAcc& a, unsigned* rec, unsigned lane) {
-    u64 left = __ballot(pending);
-    while (left != 0) {
-        const int lead = __builtin_ctzll(left);
-        const unsigned first = (unsigned)__builtin_amdgcn_readlane((int)a.slot, lead);
-        const bool mine = pending && a.slot == first;
-        const u64 same = __ballot(mine);
-        unsigned x0 = mine ? a.x0 : 0xffffffffu, y0 = mine ? a.y0 : 0xffffffffu, x1 = mine ? a.x1 : 0u, y1 = mine ? a.y1 : 0u;
-        u64 peak = mine ? a.peak : 0ull, sx = mine ? a.sx : 0ull, sy = mine ? a.sy : 0ull, st = mine ? a.st : 0ull;
-        if ((same & (same - 1ull)) != 0) {                               // wave-uniform: more than one lane holds this slot
-            for (int m = 32; m >= 1; m >>= 1) {
-                const unsigned ox0 = (unsigned)__shfl_xor((int)x0, m), oy0 = (unsigned)__shfl_xor((int)y0, m);
-                const unsigned ox1 = (unsigned)__shfl_xor((int)x1, m), oy1 = (unsigned)__shfl_xor((int)y1, m);
-                const u64 opeak = __shfl_xor(peak, m);
-                x0 = ox0 < x0 ? ox0 : x0;
-                y0 = oy0 < y0 ? oy0 : y0;
-                x1 = ox1 > x1 ? ox1 : x1;
-                y1 = oy1 > y1 ? oy1 : y1;
-                peak = opeak > peak ? opeak : peak;
-                sx += __shfl_xor(sx, m);
-                sy += __shfl_xor(sy, m);
-                st += __shfl_xor(st, m);
-            }
-        }
-        if (lane == (unsigned)lead) {
+// Adds the lanes' gathered values (sw: the sum of the frames) to their records: `pending` lanes hold a slot in 1 .. max_events,
+// equal slots of the wave are combined first.
+__device__ __forceinline__ void events_flush(bool pending, const RegionAcc<u64>& a, unsigned* rec, unsigned lane) {
+    wave_each_key(pending, a.slot, lane, [&](unsigned first, bool mine, bool many, bool lead) {
+        const RegionAcc<u64> c = a.combined(mine, many);
+        if (lead) {
             unsigned* r = rec + (u64)(first - 1u) * VAD_EVENT_WORDS;
-            atomicMin(r + 4, x0);
-            atomicMin(r + 5, y0);
-            atomicMax(r + 6, x1);
-            atomicMax(r + 7, y1);
-            atomicMax((u64*)(r + 8), peak);
-            atomicAdd((u64*)(r + 10), sx);
-            atomicAdd((u64*)(r + 12), sy);
-            atomicAdd((u64*)(r + 14), st);
+            c.commit(r, 4, 8, 10);
+            atomicAdd((u64*)(r + 14), c.sw);
         }
-        if (mine) pending = false;
-        left &= ~same;
-    }
+    });
 }
 
 // Adds the lanes' counts of one frame each (`pending` lanes: frame < p.t) to frame_counts; equal frames of the wave are combined
-// first.  Converged control flow, as above.
+// first.
 __device__ __forceinline__ void events_frames_flush(bool pending, unsigned frame, unsigned nfg, unsigned nkept, unsigned nnan, unsigned* fc,
                                                     unsigned lane) {
-    u64 left = __ballot(pending);
-    while (left != 0) {
-        const int lead = __builtin_ctzll(left);
-        const unsigned first = (unsigned)__builtin_amdgcn_readlane((int)frame, lead);
-        const bool mine = pending && frame == first;
-        const u64 same = __ballot(mine);
+    wave_each_key(pending, frame, lane, [&](unsigned first, bool mine, bool, bool lead) {
         const unsigned f = wave_sum(mine ? nfg : 0u), k = wave_sum(mine ? nkept : 0u), n = wave_sum(mine ? nnan : 0u);
-        if (lane == (unsigned)lead) {
+        if (lead) {
             unsigned* r = fc + (u64)first * 3u;
             if (f) atomicAdd(r, f);
             if (k) atomicAdd(r + 1, k);
             if (n) atomicAdd(r + 2, n);
         }
-        if (mine) pending = false;
-        left &= ~same;
-    }
+    });
 }
 
 __global__ __launch_bounds__(EV_THREADS) void events_reduce_kernel(EventP p) {
@@ -400,11 +300,8 @@ __global__ __launch_bounds__(EV_THREADS) void events_reduce_kernel(EventP p) {
         const unsigned* slots = p.aux + clip * (long long)p.vol;
         unsigned* rec = p.records + (u64)clip * p.max_events * VAD_EVENT_WORDS;
         unsigned* fc = p.frame_counts + (u64)clip * p.t * 3u;
-        EventAcc acc;
-        acc.slot = 0u;
-        acc.x0 = acc.y0 = 0xffffffffu;
-        acc.x1 = acc.y1 = 0u;
-        acc.peak = acc.sx = acc.sy = acc.st = 0ull;
+        RegionAcc<u64> acc;                                              // sw: the sum of the frames
+        acc.clear();
         unsigned nfg = 0u, nnan = 0u;                                    // of the clip
         unsigned frame = 0u, ffg = 0u, fkept = 0u, fnan = 0u;            // of the frame this lane is in
         for (unsigned run = blockIdx.x; run < nruns; run += gridDim.x) {  // uniform over the work-group
@@ -439,25 +336,7 @@ __global__ __launch_bounds__(EV_THREADS) void events_reduce_kernel(EventP p) {
                 if (slot != 0u) {
                     const unsigned pix = i - t * p.npix;
                     const unsigned y = pix / p.w, x = pix - y * p.w;
-                    const u64 peak = ((u64)order_key(bits) << 32) | (u64)(~i);
-                    if (slot != acc.slot) {
-                        acc.slot = slot;
-                        acc.x0 = acc.x1 = x;
-                        acc.y0 = acc.y1 = y;
-                        acc.peak = peak;
-                        acc.sx = x;
-                        acc.sy = y;
-                        acc.st = t;
-                    } else {
-                        acc.x0 = x < acc.x0 ? x : acc.x0;
-                        acc.y0 = y < acc.y0 ? y : acc.y0;
-                        acc.x1 = x > acc.x1 ? x : acc.x1;
-                        acc.y1 = y > acc.y1 ? y : acc.y1;
-                        acc.peak = peak > acc.peak ? peak : acc.peak;
-                        acc.sx += x;
-                        acc.sy += y;
-                        acc.st += t;
-                    }
+                    acc.add(slot, x, y, ((u64)order_key(bits) << 32) | (u64)(~i), (u64)t);
                 }
             }
         }
@@ -499,14 +378,6 @@ bool events_dims_ok(long long b, int t, int h, int w, long long* vol, long long*
     return !__builtin_mul_overflow(b, *vol, total) && *total <= (1ll << 38);
 }
 
-unsigned events_chunks(long long vol) { return (unsigned)((vol + EV_CHUNK - 1) / EV_CHUNK); }
-
-// the bytes in front of the planes: the flag word's 16, then chunk_kept [b][nchunks], padded to 16
-size_t events_head_bytes(long long b, long long vol) {
-    const size_t words = (size_t)b * events_chunks(vol);
-    return VAD_LABEL_WS_HEAD_BYTES + ((words * 4 + 15) & ~(size_t)15);
-}
-
 unsigned events_grid_x(unsigned long long items, unsigned cap) { return (unsigned)(items < cap ? items : cap); }
 
 }  // namespace
@@ -514,7 +385,7 @@ unsigned events_grid_x(unsigned long long items, unsigned cap) { return (unsigne
 size_t vad_events_workspace_bytes(long long b, int t, int h, int w, int labels_given) {
     long long vol = 0, total = 0;
     if (!events_dims_ok(b, t, h, w, &vol, &total) || (labels_given != 0 && labels_given != 1)) return 0;
-    return events_head_bytes(b, vol) + (size_t)(labels_given ? 8 : 12) * (size_t)total;   // [labels,] sizes, last / slots: 4 bytes each
+    return region_head_bytes(b, vol, 1) + (size_t)(labels_given ? 8 : 12) * (size_t)total;   // [labels,] sizes, last / slots: 4 bytes each
 }
 
 int vad_events_plan(int* label_round, int* volume_round, int* scan_round, int* reduce_round, int* threads) {
@@ -567,7 +438,7 @@ int vad_detect_events(const float* maps, long long b, int t, int h, int w, float
         return VAD_OK;
     }
     unsigned* flags = (unsigned*)ws;
-    unsigned* planes = (unsigned*)((char*)ws + events_head_bytes(b, vol));
+    unsigned* planes = (unsigned*)((char*)ws + region_head_bytes(b, vol, 1));
     int* labels = given ? labels_or_null : (int*)planes;
     unsigned* sizes = given ? planes : planes + total;
     // inside the frames: the labeller as it stands, on b * t frames (its flatten pass leaves every pixel directly under its root)
@@ -586,7 +457,7 @@ int vad_detect_events(const float* maps, long long b, int t, int h, int w, float
     p.b = b;
     p.vol = (unsigned)vol;
     p.npix = (unsigned)h * (unsigned)w;
-    p.nchunks = events_chunks(vol);
+    p.nchunks = region_chunks(vol);
     p.w = (unsigned)w;
     p.t = (unsigned)t;
     p.min_duration = min_duration;

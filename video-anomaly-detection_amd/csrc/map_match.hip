@@ -9,14 +9,14 @@
 //            flag word it is given, so the masks' run reports into the second word of the head and the join folds it into the first.
 //   join     one pass over the pixels.  P = the pixels of predicted regions with sizes_p[root] >= min_area, G = the mask's pixels.
 //            A pixel of both adds 1 to hit[root_g] and 1 to overlap[root_p]: a lane first gathers its own pixels of one region in
-//            registers, equal roots of a wave are then combined by a butterfly and one lane issues the integer atomic - a frame that
+//            registers, equal roots of a wave are then combined (wave_each_key of region_table.h) and one lane issues the integer atomic - a frame that
 //            is one region under one mask costs 8 atomics per work-group.  The classes P&G, P\G, G\P, the rest and the NaN pixels are
 //            counted by ballot and popcount in wave-uniform registers, summed in LDS, and leave as one 64-bit atomic per class and
 //            work-group.
 //   count    a frame is cut into chunks of MT_CHUNK pixels; chunk c of frame f counts its kept predicted roots and its mask roots
 //            into chunk_cnt[f][c][0 / 1], and adds regions, detected, kept, matched, false alarms and dropped to the frame's counters.
-//   slot     the rank of a root = the roots of its table in the chunks before it + those in front of it inside its chunk (ballots,
-//            wave totals through LDS): raster order across the frame, scipy.ndimage.label's numbering.  A root of rank r <
+//   slot     the rank of a root = the roots of its table in the chunks before it + those in front of it inside its chunk (chunk_before,
+//            chunk_rank_row of region_table.h): raster order across the frame, scipy.ndimage.label's numbering.  A root of rank r <
 //            max_regions writes its record - root, area, hit or overlap, flag - which is final: nothing is reduced afterwards.
 //   finish   one thread per frame: the one-hot frame class from the frame's two region counters.
 // The tables are zeroed in front of the kernels, so every record that is not written is all-zero.  Integer atomics only, and one
@@ -24,25 +24,18 @@
 // or tiling.  Every launch is asynchronous on the caller's stream, nothing is allocated, the host never waits.
 #include <hip/hip_runtime.h>
 
-#include "region_label.h"
+#include "region_table.h"
 #include "vad_common.h"
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int MT_THREADS = 256;
-constexpr unsigned MT_CHUNK = 1024;             // pixels of one chunk of the count / slot passes: four rows of the work-group
-constexpr unsigned MT_RUN = 4096;               // pixels a work-group of the join pass takes at a time
+constexpr int MT_THREADS = REGION_THREADS;
+constexpr unsigned MT_CHUNK = REGION_CHUNK;
+constexpr unsigned MT_RUN = 4096;              // pixels a work-group of the join pass takes at a time
 constexpr unsigned MT_SCAN_BLOCKS_X = 1024;     // count, slot: 2^20 pixels of a frame per grid round
 constexpr unsigned MT_JOIN_BLOCKS_X = 256;      // join: 2^20 pixels of a frame per grid round; the frames of a call fill the device
 constexpr int MT_MAX_REGIONS = 65536;
 constexpr int MT_PLANES = 6;                    // labels_p, sizes_p, labels_g, sizes_g, hit, overlap: 4 bytes per pixel each
-
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-    for (int m = 32; m >= 1; m >>= 1) v += (unsigned)__shfl_xor((int)v, m);
-    return v;
-}
 
 struct MatchP {
     const float* maps;
@@ -67,21 +60,13 @@ __device__ __forceinline__ bool match_passes(unsigned shared, unsigned area, dou
     return shared >= 1u && (double)shared >= fraction * (double)area;
 }
 
-// Adds the lanes' gathered counts to table[key - 1].  `pending` lanes hold a key != 0; equal keys of the wave are combined first.
-// Called in converged control flow (the loop is wave-uniform; every round retires at least the leading lane).
+// Adds the lanes' gathered counts to table[key - 1]: `pending` lanes hold a key != 0, equal keys of the wave are combined first.
 __device__ __forceinline__ void match_flush(bool pending, unsigned key, unsigned cnt, unsigned* table, unsigned lane) {
-    u64 left = __ballot(pending);
-    while (left != 0) {
-        const int lead = __builtin_ctzll(left);
-        const unsigned first = (unsigned)__builtin_amdgcn_readlane((int)key, lead);
-        const bool mine = pending && key == first;
-        const u64 same = __ballot(mine);
+    wave_each_key(pending, key, lane, [&](unsigned first, bool mine, bool many, bool lead) {
         unsigned c = mine ? cnt : 0u;
-        if ((same & (same - 1ull)) != 0) c = wave_sum(c);                // wave-uniform: more than one lane holds this key
-        if (lane == (unsigned)lead) atomicAdd(table + (first - 1u), c);
-        if (mine) pending = false;
-        left &= ~same;
-    }
+        if (many) c = wave_sum(c);
+        if (lead) atomicAdd(table + (first - 1u), c);
+    });
 }
 
 __global__ __launch_bounds__(MT_THREADS) void match_join_kernel(MatchP p) {
@@ -191,100 +176,53 @@ __global__ __launch_bounds__(MT_THREADS) void match_count_kernel(MatchP p) {
     for (long long img = blockIdx.y; img < p.n; img += gridDim.y) {
         const long long off = img * (long long)p.npix;
         for (unsigned c = blockIdx.x; c < p.nchunks; c += gridDim.x) {   // uniform over the work-group
-            if (threadIdx.x < 5) s_n[threadIdx.x] = 0u;
-            __syncthreads();
-            unsigned kept = 0u, dropped = 0u, matched = 0u, gt = 0u, detected = 0u;
+            block_sum_clear<5>(s_n);
+            unsigned n[5] = {0u, 0u, 0u, 0u, 0u};
             for (unsigned j = 0; j < MT_CHUNK / MT_THREADS; ++j) {
                 const MatchRoots r = match_roots(p, off, c * MT_CHUNK + j * MT_THREADS + threadIdx.x);   // < 2^31 + 1024: no wrap
-                kept += r.kept ? 1u : 0u;
-                dropped += r.dropped ? 1u : 0u;
-                matched += r.matched ? 1u : 0u;
-                gt += r.gt ? 1u : 0u;
-                detected += r.detected ? 1u : 0u;
+                n[0] += r.kept ? 1u : 0u;
+                n[1] += r.dropped ? 1u : 0u;
+                n[2] += r.matched ? 1u : 0u;
+                n[3] += r.gt ? 1u : 0u;
+                n[4] += r.detected ? 1u : 0u;
             }
-            kept = wave_sum(kept);
-            dropped = wave_sum(dropped);
-            matched = wave_sum(matched);
-            gt = wave_sum(gt);
-            detected = wave_sum(detected);
-            if ((threadIdx.x & 63u) == 0u) {
-                if (kept) atomicAdd(&s_n[0], kept);
-                if (dropped) atomicAdd(&s_n[1], dropped);
-                if (matched) atomicAdd(&s_n[2], matched);
-                if (gt) atomicAdd(&s_n[3], gt);
-                if (detected) atomicAdd(&s_n[4], detected);
-            }
-            __syncthreads();
+            block_sum(n, s_n);
             if (threadIdx.x == 0) {
                 unsigned* cc = p.chunk_cnt + (img * (long long)p.nchunks + c) * 2;
-                cc[0] = s_n[0];
-                cc[1] = s_n[3];
+                cc[0] = n[0];
+                cc[1] = n[3];
                 u64* cnt = p.counts + img * VAD_MATCH_COUNTS;
-                if (s_n[3]) atomicAdd(cnt + 0, (u64)s_n[3]);
-                if (s_n[4]) atomicAdd(cnt + 1, (u64)s_n[4]);
-                if (s_n[0]) atomicAdd(cnt + 2, (u64)s_n[0]);
-                if (s_n[2]) atomicAdd(cnt + 3, (u64)s_n[2]);
-                if (s_n[0] - s_n[2]) atomicAdd(cnt + 4, (u64)(s_n[0] - s_n[2]));   // matched is a subset of kept
-                if (s_n[1]) atomicAdd(cnt + 5, (u64)s_n[1]);
+                if (n[3]) atomicAdd(cnt + 0, (u64)n[3]);
+                if (n[4]) atomicAdd(cnt + 1, (u64)n[4]);
+                if (n[0]) atomicAdd(cnt + 2, (u64)n[0]);
+                if (n[2]) atomicAdd(cnt + 3, (u64)n[2]);
+                if (n[0] - n[2]) atomicAdd(cnt + 4, (u64)(n[0] - n[2]));   // matched is a subset of kept
+                if (n[1]) atomicAdd(cnt + 5, (u64)n[1]);
             }
-            __syncthreads();
+            __syncthreads();                                             // s_n is cleared again for the next chunk
         }
     }
 }
 
 // ranks of the roots of both tables in raster order, and their records
 __global__ __launch_bounds__(MT_THREADS) void match_slot_kernel(MatchP p) {
-    __shared__ unsigned s_before[2], s_wave[2][MT_THREADS / 64];
-    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    __shared__ unsigned s_before[2], s_wave[2][REGION_WAVES];
     for (long long img = blockIdx.y; img < p.n; img += gridDim.y) {
         const long long off = img * (long long)p.npix;
-        const unsigned* cnt_of = p.chunk_cnt + img * (long long)p.nchunks * 2;
         unsigned* rec_p = p.pred_rec + (u64)img * p.max_regions * VAD_MATCH_WORDS;
         unsigned* rec_g = p.gt_rec + (u64)img * p.max_regions * VAD_MATCH_WORDS;
         for (unsigned c = blockIdx.x; c < p.nchunks; c += gridDim.x) {   // uniform over the work-group
-            if (threadIdx.x < 2) s_before[threadIdx.x] = 0u;
-            __syncthreads();
-            unsigned before_p = 0u, before_g = 0u;
-            for (unsigned k = threadIdx.x; k < c; k += MT_THREADS) {
-                before_p += cnt_of[2 * k];
-                before_g += cnt_of[2 * k + 1];
-            }
-            before_p = wave_sum(before_p);
-            before_g = wave_sum(before_g);
-            if (lane == 0u) {
-                if (before_p) atomicAdd(&s_before[0], before_p);
-                if (before_g) atomicAdd(&s_before[1], before_g);
-            }
-            __syncthreads();
-            unsigned base_p = s_before[0], base_g = s_before[1];         // the roots of this frame in front of the chunk
+            unsigned base[2], rank[2];                                   // [0] kept predicted roots, [1] mask roots
+            chunk_before(p.chunk_cnt + img * (long long)p.nchunks * 2, c, base, s_before);
             for (unsigned j = 0; j < MT_CHUNK / MT_THREADS; ++j) {
                 const unsigned i = c * MT_CHUNK + j * MT_THREADS + threadIdx.x;
                 const MatchRoots r = match_roots(p, off, i);
-                const u64 bp = __ballot(r.kept), bg = __ballot(r.gt);
-                if (lane == 0u) {
-                    s_wave[0][wave] = (unsigned)__builtin_popcountll(bp);
-                    s_wave[1][wave] = (unsigned)__builtin_popcountll(bg);
-                }
-                __syncthreads();
-                const u64 below = (1ull << lane) - 1ull;
-                unsigned rank_p = base_p + (unsigned)__builtin_popcountll(bp & below);
-                unsigned rank_g = base_g + (unsigned)__builtin_popcountll(bg & below);
-                unsigned row_p = 0u, row_g = 0u;
-                for (unsigned k = 0; k < MT_THREADS / 64; ++k) {
-                    if (k < wave) {
-                        rank_p += s_wave[0][k];
-                        rank_g += s_wave[1][k];
-                    }
-                    row_p += s_wave[0][k];
-                    row_g += s_wave[1][k];
-                }
-                base_p += row_p;
-                base_g += row_g;
-                __syncthreads();                                         // s_wave is written again in the next row
-                if (r.kept && rank_p < p.max_regions)
-                    *(u32x4*)(rec_p + (u64)rank_p * VAD_MATCH_WORDS) = u32x4{i, r.area_p, r.overlap, r.matched ? 1u : 0u};
-                if (r.gt && rank_g < p.max_regions)
-                    *(u32x4*)(rec_g + (u64)rank_g * VAD_MATCH_WORDS) = u32x4{i, r.area_g, r.hit, r.detected ? 1u : 0u};
+                const bool roots[2] = {r.kept, r.gt};
+                chunk_rank_row(roots, base, rank, s_wave);
+                if (r.kept && rank[0] < p.max_regions)
+                    *(u32x4*)(rec_p + (u64)rank[0] * VAD_MATCH_WORDS) = u32x4{i, r.area_p, r.overlap, r.matched ? 1u : 0u};
+                if (r.gt && rank[1] < p.max_regions)
+                    *(u32x4*)(rec_g + (u64)rank[1] * VAD_MATCH_WORDS) = u32x4{i, r.area_g, r.hit, r.detected ? 1u : 0u};
             }
         }
     }
@@ -299,13 +237,8 @@ __global__ __launch_bounds__(MT_THREADS) void match_finish_kernel(MatchP p) {
     }
 }
 
-unsigned match_chunks(int h, int w) { return (unsigned)(((long long)h * w + MT_CHUNK - 1) / MT_CHUNK); }
-
 // the bytes in front of the planes: the flag words' 16, then chunk_cnt [n][nchunks][2], padded to 16
-size_t match_head_bytes(long long n, int h, int w) {
-    const size_t words = (size_t)n * match_chunks(h, w) * 2;
-    return VAD_LABEL_WS_HEAD_BYTES + ((words * 4 + 15) & ~(size_t)15);
-}
+size_t match_head_bytes(long long n, int h, int w) { return region_head_bytes(n, (long long)h * w, 2); }
 
 }  // namespace
 
@@ -381,7 +314,7 @@ int vad_match_regions(const float* maps, const void* masks, int mask_format, lon
     p.pred_fraction = pred_fraction;
     p.n = n;
     p.npix = (unsigned)h * (unsigned)w;
-    p.nchunks = match_chunks(h, w);
+    p.nchunks = region_chunks((long long)h * w);
     p.min_area = min_area;
     p.max_regions = (unsigned)max_regions;
 

@@ -9,40 +9,29 @@
 //   count    a frame is cut into chunks of REG_CHUNK pixels; chunk c of frame f counts its kept roots (sizes[root] >= min_area)
 //            into chunk_kept[f][c], and adds kept / dropped roots to counts[f][0 / 1]
 //   slot     the rank of a kept root = the kept roots of the chunks before it (a sum over chunk_kept[f][0 .. c)) + the kept roots in
-//            front of it inside its chunk (ballots, wave totals through LDS): raster order across the whole frame.  A root of rank
+//            front of it inside its chunk (chunk_before, chunk_rank_row of region_table.h): raster order across the whole frame.  A root of rank
 //            r < max_regions gets slots[root] = r + 1 and its record's root, area and the identities of the reductions; any other
 //            root gets slots[root] = 0.  Only roots' slots are ever written or read.
 //   reduce   every foreground pixel whose root has a slot contributes x, y, (key(v) << 32 | ~index) to its record: min / max of
 //            the box, max of the 64-bit peak word (the largest key and, among equals, the smallest index), sums of x and y.  A lane
-//            first gathers its own pixels of one region in registers, then equal slots of a wave are combined by a butterfly, and
-//            one lane issues the seven integer atomics: a frame that is one region costs 28 atomics per 4096 pixels.  The same
+//            first gathers its own pixels of one region in registers, then equal slots of a wave are combined, and one lane issues
+//            the seven integer atomics (RegionAcc, wave_each_key of region_table.h): one region costs 28 atomics per 4096 pixels.  The same
 //            pass counts foreground and NaN pixels into counts[f][2 / 3].
 //   finish   the records in use get their peak word split into float bits and index; every other record of the table is zeroed.
 // Integer atomics, min and max only: the table is the same words for any batching, launch order or tiling.  Every launch is
 // asynchronous on the caller's stream, nothing is allocated, the host never waits.
 #include <hip/hip_runtime.h>
 
-#include "region_label.h"
+#include "region_table.h"
 #include "vad_common.h"
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int REG_THREADS = 256;
-constexpr unsigned REG_CHUNK = 1024;            // pixels of one chunk of the count / slot passes: four rows of the work-group
+constexpr int REG_THREADS = REGION_THREADS;
+constexpr unsigned REG_CHUNK = REGION_CHUNK;
 constexpr unsigned REG_RUN = 4096;              // pixels a work-group of the reduce pass takes at a time
 constexpr unsigned REG_MAX_BLOCKS_X = 4096;
 constexpr int REG_MAX_REGIONS = 65536;
-
-// The order-preserving key of a float's bits: a < b as floats (with -0.0 < +0.0) iff key(a) < key(b) as unsigned.
-__device__ __forceinline__ unsigned order_key(unsigned bits) { return (bits & 0x80000000u) ? ~bits : bits | 0x80000000u; }
-__device__ __forceinline__ unsigned order_key_inv(unsigned key) { return (key & 0x80000000u) ? key & 0x7fffffffu : ~key; }
-
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-    for (int m = 32; m >= 1; m >>= 1) v += (unsigned)__shfl_xor((int)v, m);
-    return v;
-}
 
 struct RegionP {
     const float* maps;
@@ -58,73 +47,48 @@ struct RegionP {
 
 // kept / dropped roots per chunk
 __global__ __launch_bounds__(REG_THREADS) void regions_count_kernel(RegionP p) {
-    __shared__ unsigned s_kept, s_dropped;
+    __shared__ unsigned s_n[2];
     for (long long img = blockIdx.y; img < p.n; img += gridDim.y) {
         const int* L = p.labels + img * (long long)p.npix;
         const unsigned* S = p.sizes + img * (long long)p.npix;
         for (unsigned c = blockIdx.x; c < p.nchunks; c += gridDim.x) {   // uniform over the work-group
-            if (threadIdx.x == 0) s_kept = s_dropped = 0u;
-            __syncthreads();
-            unsigned kept = 0u, dropped = 0u;
+            block_sum_clear<2>(s_n);
+            unsigned n[2] = {0u, 0u};                                    // kept, dropped
             for (unsigned j = 0; j < REG_CHUNK / REG_THREADS; ++j) {
                 const unsigned i = c * REG_CHUNK + j * REG_THREADS + threadIdx.x;      // < 2^31 + 1024: no wrap
                 if (i < p.npix && L[i] == (int)(i + 1u)) {
-                    if (S[i] >= p.min_area) ++kept;
-                    else ++dropped;
+                    if (S[i] >= p.min_area) ++n[0];
+                    else ++n[1];
                 }
             }
-            kept = wave_sum(kept);
-            dropped = wave_sum(dropped);
-            if ((threadIdx.x & 63u) == 0u) {
-                if (kept) atomicAdd(&s_kept, kept);
-                if (dropped) atomicAdd(&s_dropped, dropped);
-            }
-            __syncthreads();
+            block_sum(n, s_n);
             if (threadIdx.x == 0) {
-                p.chunk_kept[img * (long long)p.nchunks + c] = s_kept;
-                if (s_kept) atomicAdd(p.counts + img * 4, s_kept);
-                if (s_dropped) atomicAdd(p.counts + img * 4 + 1, s_dropped);
+                p.chunk_kept[img * (long long)p.nchunks + c] = n[0];
+                if (n[0]) atomicAdd(p.counts + img * 4, n[0]);
+                if (n[1]) atomicAdd(p.counts + img * 4 + 1, n[1]);
             }
-            __syncthreads();
+            __syncthreads();                                             // s_n is cleared again for the next chunk
         }
     }
 }
 
 // ranks of the kept roots in raster order; the records' first words and the identities of the reductions
 __global__ __launch_bounds__(REG_THREADS) void regions_slot_kernel(RegionP p) {
-    __shared__ unsigned s_before, s_wave[REG_THREADS / 64];
-    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    __shared__ unsigned s_before[1], s_wave[1][REGION_WAVES];
     for (long long img = blockIdx.y; img < p.n; img += gridDim.y) {
         const int* L = p.labels + img * (long long)p.npix;
         const unsigned* S = p.sizes + img * (long long)p.npix;
         unsigned* slots = p.slots + img * (long long)p.npix;
-        const unsigned* kept_of = p.chunk_kept + img * (long long)p.nchunks;
         unsigned* rec = p.records + (u64)img * p.max_regions * VAD_REGION_WORDS;
         for (unsigned c = blockIdx.x; c < p.nchunks; c += gridDim.x) {   // uniform over the work-group
-            if (threadIdx.x == 0) s_before = 0u;
-            __syncthreads();
-            unsigned before = 0u;
-            for (unsigned k = threadIdx.x; k < c; k += REG_THREADS) before += kept_of[k];
-            before = wave_sum(before);
-            if (lane == 0u && before) atomicAdd(&s_before, before);
-            __syncthreads();
-            unsigned base = s_before;                                    // the kept roots of this frame in front of the chunk
+            unsigned base[1];                                            // the kept roots of this frame in front of the chunk
+            chunk_before(p.chunk_kept + img * (long long)p.nchunks, c, base, s_before);
             for (unsigned j = 0; j < REG_CHUNK / REG_THREADS; ++j) {
                 const unsigned i = c * REG_CHUNK + j * REG_THREADS + threadIdx.x;
                 const bool root = i < p.npix && L[i] == (int)(i + 1u);
                 const unsigned area = root ? S[i] : 0u;
                 const bool kept = root && area >= p.min_area;
-                const u64 b = __ballot(kept);
-                if (lane == 0u) s_wave[wave] = (unsigned)__builtin_popcountll(b);
-                __syncthreads();
-                unsigned rank = base + (unsigned)__builtin_popcountll(b & ((1ull << lane) - 1ull));
-                unsigned row = 0u;
-                for (unsigned k = 0; k < REG_THREADS / 64; ++k) {
-                    if (k < wave) rank += s_wave[k];
-                    row += s_wave[k];
-                }
-                base += row;
-                __syncthreads();                                         // s_wave is written again in the next row
+                const unsigned rank = chunk_rank_row(kept, base[0], s_wave);
                 if (kept && rank < p.max_regions) {
                     slots[i] = rank + 1u;
                     unsigned* r = rec + (u64)rank * VAD_REGION_WORDS;
@@ -139,50 +103,12 @@ __global__ __launch_bounds__(REG_THREADS) void regions_slot_kernel(RegionP p) {
     }
 }
 
-struct RegionAcc {
-    unsigned slot;           // 0 = nothing gathered
-    unsigned x0, y0, x1, y1;
-    u64 peak, sx, sy;
-};
-
-// Adds the lanes' gathered values to their records.  `pending` lanes hold a slot != 0; equal slots of the wave are combined first.
-// Called in converged control flow (the loop is wave-uniform; every round retires at least the leading lane).
-__device__ __forceinline__ void regions_flush(bool pending, const RegionAcc& a, unsigned* rec, unsigned lane) {
-    u64 left = __ballot(pending);
-    while (left != 0) {
-        const int lead = __builtin_ctzll(left);
-        const unsigned first = (unsigned)__builtin_amdgcn_readlane((int)a.slot, lead);
-        const bool mine = pending && a.slot == first;
-        const u64 same = __ballot(mine);
-        unsigned x0 = mine ? a.x0 : 0xffffffffu, y0 = mine ? a.y0 : 0xffffffffu, x1 = mine ? a.x1 : 0u, y1 = mine ? a.y1 : 0u;
-        u64 peak = mine ? a.peak : 0ull, sx = mine ? a.sx : 0ull, sy = mine ? a.sy : 0ull;
-        if ((same & (same - 1ull)) != 0) {                               // wave-uniform: more than one lane holds this slot
-            for (int m = 32; m >= 1; m >>= 1) {
-                const unsigned ox0 = (unsigned)__shfl_xor((int)x0, m), oy0 = (unsigned)__shfl_xor((int)y0, m);
-                const unsigned ox1 = (unsigned)__shfl_xor((int)x1, m), oy1 = (unsigned)__shfl_xor((int)y1, m);
-                const u64 opeak = __shfl_xor(peak, m);
-                x0 = ox0 < x0 ? ox0 : x0;
-                y0 = oy0 < y0 ? oy0 : y0;
-                x1 = ox1 > x1 ? ox1 : x1;
-                y1 = oy1 > y1 ? oy1 : y1;
-                peak = opeak > peak ? opeak : peak;
-                sx += __shfl_xor(sx, m);
-                sy += __shfl_xor(sy, m);
-            }
-        }
-        if (lane == (unsigned)lead) {
-            unsigned* r = rec + (u64)(first - 1u) * VAD_REGION_WORDS;
-            atomicMin(r + 2, x0);
-            atomicMin(r + 3, y0);
-            atomicMax(r + 4, x1);
-            atomicMax(r + 5, y1);
-            atomicMax((u64*)(r + 6), peak);
-            atomicAdd((u64*)(r + 8), sx);
-            atomicAdd((u64*)(r + 10), sy);
-        }
-        if (mine) pending = false;
-        left &= ~same;
-    }
+// Adds the lanes' gathered values to their records: `pending` lanes hold a slot != 0, equal slots of the wave are combined first.
+__device__ __forceinline__ void regions_flush(bool pending, const RegionAcc<unsigned>& a, unsigned* rec, unsigned lane) {
+    wave_each_key(pending, a.slot, lane, [&](unsigned first, bool mine, bool many, bool lead) {
+        const RegionAcc<unsigned> c = a.combined(mine, many);
+        if (lead) c.commit(rec + (u64)(first - 1u) * VAD_REGION_WORDS, 2, 6, 8);
+    });
 }
 
 __global__ __launch_bounds__(REG_THREADS) void regions_reduce_kernel(RegionP p) {
@@ -193,11 +119,8 @@ __global__ __launch_bounds__(REG_THREADS) void regions_reduce_kernel(RegionP p) 
         const int* L = p.labels + img * (long long)p.npix;
         const unsigned* slots = p.slots + img * (long long)p.npix;
         unsigned* rec = p.records + (u64)img * p.max_regions * VAD_REGION_WORDS;
-        RegionAcc acc;
-        acc.slot = 0u;
-        acc.x0 = acc.y0 = 0xffffffffu;
-        acc.x1 = acc.y1 = 0u;
-        acc.peak = acc.sx = acc.sy = 0ull;
+        RegionAcc<unsigned> acc;                                         // no further sum
+        acc.clear();
         unsigned nfg = 0u, nnan = 0u;
         for (unsigned run = blockIdx.x; run < nruns; run += gridDim.x) {  // uniform over the work-group
             for (unsigned j = 0; j < REG_RUN / REG_THREADS; ++j) {       // the same trip count for every lane: converged ballots
@@ -218,23 +141,7 @@ __global__ __launch_bounds__(REG_THREADS) void regions_reduce_kernel(RegionP p) 
                 regions_flush(acc.slot != 0u && slot != 0u && slot != acc.slot, acc, rec, lane);
                 if (slot != 0u) {
                     const unsigned y = i / p.w, x = i - y * p.w;
-                    const u64 peak = ((u64)order_key(bits) << 32) | (u64)(~i);
-                    if (slot != acc.slot) {
-                        acc.slot = slot;
-                        acc.x0 = acc.x1 = x;
-                        acc.y0 = acc.y1 = y;
-                        acc.peak = peak;
-                        acc.sx = x;
-                        acc.sy = y;
-                    } else {
-                        acc.x0 = x < acc.x0 ? x : acc.x0;
-                        acc.y0 = y < acc.y0 ? y : acc.y0;
-                        acc.x1 = x > acc.x1 ? x : acc.x1;
-                        acc.y1 = y > acc.y1 ? y : acc.y1;
-                        acc.peak = peak > acc.peak ? peak : acc.peak;
-                        acc.sx += x;
-                        acc.sy += y;
-                    }
+                    acc.add(slot, x, y, ((u64)order_key(bits) << 32) | (u64)(~i), 0u);
                 }
             }
         }
@@ -267,20 +174,12 @@ __global__ __launch_bounds__(REG_THREADS) void regions_finish_kernel(RegionP p) 
     }
 }
 
-unsigned regions_chunks(int h, int w) { return (unsigned)(((long long)h * w + REG_CHUNK - 1) / REG_CHUNK); }
-
-// the bytes in front of the planes: the flag word's 16, then chunk_kept [n][nchunks], padded to 16
-size_t regions_head_bytes(long long n, int h, int w) {
-    const size_t words = (size_t)n * regions_chunks(h, w);
-    return VAD_LABEL_WS_HEAD_BYTES + ((words * 4 + 15) & ~(size_t)15);
-}
-
 }  // namespace
 
 size_t vad_regions_workspace_bytes(long long n, int h, int w, int labels_given) {
     long long total = 0;
     if (!vad_label_dims_ok(n, h, w, &total) || (labels_given != 0 && labels_given != 1)) return 0;
-    return regions_head_bytes(n, h, w) + (size_t)(labels_given ? 8 : 12) * (size_t)total;   // [labels,] sizes, slots: 4 bytes each
+    return region_head_bytes(n, (long long)h * w, 1) + (size_t)(labels_given ? 8 : 12) * (size_t)total;   // [labels,] sizes, slots: 4 bytes each
 }
 
 int vad_detect_regions(const float* maps, long long n, int h, int w, float threshold, int connectivity, unsigned min_area,
@@ -316,7 +215,7 @@ int vad_detect_regions(const float* maps, long long n, int h, int w, float thres
         return VAD_OK;
     }
     unsigned* flags = (unsigned*)ws;
-    unsigned* planes = (unsigned*)((char*)ws + regions_head_bytes(n, h, w));
+    unsigned* planes = (unsigned*)((char*)ws + region_head_bytes(n, (long long)h * w, 1));
     int* labels = given ? labels_or_null : (int*)planes;
     unsigned* sizes = given ? planes : planes + total;
     if (int rc = vad_label_launch(maps, VAD_LABEL_FMT_F32_GE, threshold, n, h, w, connectivity, labels, sizes, flags, s)) return rc;
@@ -331,7 +230,7 @@ int vad_detect_regions(const float* maps, long long n, int h, int w, float thres
     p.counts = counts;
     p.n = n;
     p.npix = (unsigned)h * (unsigned)w;
-    p.nchunks = regions_chunks(h, w);
+    p.nchunks = region_chunks((long long)h * w);
     p.w = (unsigned)w;
     p.min_area = min_area;
     p.max_regions = (unsigned)max_regions;

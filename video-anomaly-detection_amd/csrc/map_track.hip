@@ -14,13 +14,13 @@
 //   link-union the same walk unites the pixel's root with minroot[slot]: the regions that share an open event are one set, whose
 //              root - its smallest pixel - is the event's new handle
 //   flatten    every pixel directly under its handle; the handles of every chunk of TR_CHUNK pixels are counted
-//   slot       rank scan over the chunks: handle of rank r < max_open -> slot r + 1 and a cleared working record; behind the table
+//   slot       rank scan over the chunks (chunk_before, chunk_rank_row of region_table.h): handle of rank r < max_open -> slot r + 1 and a cleared working record; behind the table
 //              -> TR_NO_RECORD, counted as lost
 //   carry      one work-group per stream over the old table (in a call's first frame it zeroes the closed table first): an old
 //              event whose minroot leads to a handle merges its record into that handle's working record (64-bit adds, a 64-bit min on (t0, root pixel), box min / max, the peak as a max on the
 //              key followed - after a barrier - by a min on (frame, pixel) among the holders of that key); one without a link
 //              closed: it is ranked among the closed of this frame by a scan over the slots, filtered and appended
-//   reduce     the new frame's pixels into the working records (gathered per lane, combined per wave), the frame's foreground and
+//   reduce     the new frame's pixels into the working records (RegionAcc of region_table.h: gathered per lane, combined per wave), the frame's foreground and
 //              NaN counts, the new slot plane
 //   finish     working records -> the state's table (peak resolved: the new frame wins only with a larger key), unused records
 //              zeroed, the causal alarm word, the header's open count
@@ -29,15 +29,13 @@
 // cooperative launch, no loop without a bound known at launch.
 #include <hip/hip_runtime.h>
 
-#include "region_label.h"
+#include "region_table.h"
 #include "vad_common.h"
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int TR_THREADS = 256;
-constexpr unsigned TR_CHUNK = 1024;             // pixels of one chunk of the flatten / slot passes
+constexpr int TR_THREADS = REGION_THREADS;
+constexpr unsigned TR_CHUNK = REGION_CHUNK;
 constexpr unsigned TR_RUN = 1024;               // pixels a work-group of the link and reduce passes takes at a time
 constexpr unsigned TR_PIXEL_BLOCKS_X = 256;     // link-min, link-union, reduce: 2^18 pixels of a frame per grid round
 constexpr unsigned TR_SCAN_BLOCKS_X = 256;      // flatten, slot: 2^18 pixels per round
@@ -60,14 +58,6 @@ constexpr unsigned WK_NEWPEAK = 20;             // u64 max over the new frame: k
 constexpr unsigned RC_ROOT = 0, RC_T0 = 1, RC_T1 = 2, RC_HANDLE = 3, RC_X0 = 4, RC_PEAK = 8, RC_PEAK_PIXEL = 9, RC_PEAK_FRAME = 10;
 constexpr unsigned RC_VOLUME = 12, RC_SX = 14, RC_SY = 16, RC_ST = 18;
 static_assert(VAD_TRACK_WORDS == 20, "the record layout above");
-
-__device__ __forceinline__ unsigned order_key(unsigned bits) { return (bits & 0x80000000u) ? ~bits : bits | 0x80000000u; }
-__device__ __forceinline__ unsigned order_key_inv(unsigned key) { return (key & 0x80000000u) ? key & 0x7fffffffu : ~key; }
-
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-    for (int m = 32; m >= 1; m >>= 1) v += (unsigned)__shfl_xor((int)v, m);
-    return v;
-}
 
 struct TrackP {
     const float* maps;       // [b][t][npix]
@@ -142,29 +132,9 @@ __global__ __launch_bounds__(TR_THREADS) void track_begin_kernel(TrackP p) {
     }
 }
 
-// Elects one lane for every distinct pair (a, b) among the `pending` lanes of the wave.  Called in converged control flow; the loop
-// is wave-uniform and every round retires at least the leading lane.
-__device__ __forceinline__ bool track_elect(bool pending, unsigned a, unsigned b, unsigned lane) {
-    bool elected = false;
-    u64 left = __ballot(pending);
-    while (left != 0) {
-        const int lead = __builtin_ctzll(left);
-        const unsigned a0 = (unsigned)__builtin_amdgcn_readlane((int)a, lead), b0 = (unsigned)__builtin_amdgcn_readlane((int)b, lead);
-        const bool mine = pending && a == a0 && b == b0;
-        const u64 same = __ballot(mine);
-        if (lane == (unsigned)lead) elected = true;
-        if (mine) pending = false;
-        left &= ~same;
-    }
-    return elected;
-}
-
-// the slot of the 3 x 3's ring pixel k (clockwise from above-left) around (y, x) in the plane before, or 0
+// the slot of the 3 x 3's ring pixel k around (y, x) in the plane before, or 0
 __device__ __forceinline__ unsigned track_ring_slot(const unsigned* P, unsigned i, unsigned y, unsigned x, unsigned h, unsigned w, int k) {
-    const int dy = k < 3 ? -1 : (k == 3 || k == 7) ? 0 : 1;
-    const int dx = (k == 0 || k >= 6) ? -1 : (k == 1 || k == 5) ? 0 : 1;
-    const bool inside = (dy >= 0 || y > 0u) && (dy <= 0 || y + 1u < h) && (dx >= 0 || x > 0u) && (dx <= 0 || x + 1u < w);
-    return inside ? P[(int)i + dy * (int)w + dx] : 0u;
+    return ring_inside(y, x, h, w, k) ? P[(int)i + ring_dy(k) * (int)w + ring_dx(k)] : 0u;
 }
 
 // link-min (UNION = false) and link-union (UNION = true): the same walk over the new frame's foreground pixels
@@ -189,7 +159,7 @@ __global__ __launch_bounds__(TR_THREADS) void track_link_kernel(TrackP p) {
             const unsigned root = fg ? (unsigned)label_load(L + i) - 1u : 0u;
             const unsigned centre = fg ? P[i] : 0u;
             const bool direct = centre - 1u < p.max_open;                // a slot with a record (0 and TR_NO_RECORD are not)
-            if (track_elect(direct, centre, root, lane)) {
+            if (wave_elect_pair(direct, centre, root, lane)) {
                 if (!UNION) {
                     atomicMin(M + (centre - 1u), root);
                 } else {
@@ -222,14 +192,13 @@ __global__ __launch_bounds__(TR_THREADS) void track_link_kernel(TrackP p) {
 
 // every pixel directly under its handle; handles per chunk
 __global__ __launch_bounds__(TR_THREADS) void track_flatten_kernel(TrackP p) {
-    __shared__ unsigned s_n;
+    __shared__ unsigned s_n[1];
     for (long long s = blockIdx.y; s < p.b; s += gridDim.y) {
         int* L = tr_labels(p, s);
         bool failed = false;
         for (unsigned c = blockIdx.x; c < p.nchunks; c += gridDim.x) {   // uniform over the work-group
-            if (threadIdx.x == 0) s_n = 0u;
-            __syncthreads();
-            unsigned n = 0u;
+            block_sum_clear<1>(s_n);
+            unsigned n[1] = {0u};
             for (unsigned j = 0; j < TR_CHUNK / TR_THREADS; ++j) {
                 const unsigned i = c * TR_CHUNK + j * TR_THREADS + threadIdx.x;
                 if (i < p.npix && L[i] != 0) {
@@ -238,14 +207,12 @@ __global__ __launch_bounds__(TR_THREADS) void track_flatten_kernel(TrackP p) {
                     failed |= budget == 0u;
                     // a root keeps its value; any other pixel gets an ancestor of its old parent, so concurrent chases stay valid
                     if (root != i) __hip_atomic_store(L + i, (int)(root + 1u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    else ++n;
+                    else ++n[0];
                 }
             }
-            n = wave_sum(n);
-            if ((threadIdx.x & 63u) == 0u && n) atomicAdd(&s_n, n);
-            __syncthreads();
-            if (threadIdx.x == 0) p.chunk_n[(size_t)s * p.nchunks + c] = s_n;
-            __syncthreads();
+            block_sum(n, s_n);
+            if (threadIdx.x == 0) p.chunk_n[(size_t)s * p.nchunks + c] = n[0];
+            __syncthreads();                                             // s_n is cleared again for the next chunk
         }
         if (failed) tr_fail(p, s);
     }
@@ -253,8 +220,7 @@ __global__ __launch_bounds__(TR_THREADS) void track_flatten_kernel(TrackP p) {
 
 // ranks of the handles in raster order; the working records' identities
 __global__ __launch_bounds__(TR_THREADS) void track_slot_kernel(TrackP p) {
-    __shared__ unsigned s_before, s_wave[TR_THREADS / 64];
-    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    __shared__ unsigned s_before[1], s_wave[1][REGION_WAVES];
     for (long long s = blockIdx.y; s < p.b; s += gridDim.y) {
         const int* L = tr_labels(p, s);
         const unsigned* n_of = p.chunk_n + (size_t)s * p.nchunks;
@@ -263,17 +229,11 @@ __global__ __launch_bounds__(TR_THREADS) void track_slot_kernel(TrackP p) {
         unsigned* hd = tr_header(p, s);
         const unsigned f = hd[0] - 1u;                                   // the frame's number: begin advanced the counter
         for (unsigned c = blockIdx.x; c < p.nchunks; c += gridDim.x) {   // uniform over the work-group
-            if (threadIdx.x == 0) s_before = 0u;
-            __syncthreads();
-            unsigned before = 0u;
-            for (unsigned k = threadIdx.x; k < c; k += TR_THREADS) before += n_of[k];
-            before = wave_sum(before);
-            if (lane == 0u && before) atomicAdd(&s_before, before);
-            __syncthreads();
-            unsigned base = s_before;
+            unsigned base[1];                                            // the handles of this frame in front of the chunk
+            chunk_before(n_of, c, base, s_before);
             // the frame's last chunk has summed the whole frame: its work-group writes the open and the lost count
             if (c + 1u == p.nchunks && threadIdx.x == 0) {
-                const unsigned total = base + n_of[c];
+                const unsigned total = base[0] + n_of[c];
                 const unsigned open = total < p.max_open ? total : p.max_open;
                 p.nopen[s] = open;
                 if (total > open) {
@@ -284,17 +244,7 @@ __global__ __launch_bounds__(TR_THREADS) void track_slot_kernel(TrackP p) {
             for (unsigned j = 0; j < TR_CHUNK / TR_THREADS; ++j) {
                 const unsigned i = c * TR_CHUNK + j * TR_THREADS + threadIdx.x;
                 const bool handle = i < p.npix && L[i] == (int)(i + 1u);
-                const u64 b = __ballot(handle);
-                if (lane == 0u) s_wave[wave] = (unsigned)__builtin_popcountll(b);
-                __syncthreads();
-                unsigned rank = base + (unsigned)__builtin_popcountll(b & ((1ull << lane) - 1ull));
-                unsigned row = 0u;
-                for (unsigned k = 0; k < TR_THREADS / 64; ++k) {
-                    if (k < wave) rank += s_wave[k];
-                    row += s_wave[k];
-                }
-                base += row;
-                __syncthreads();                                         // s_wave is written again in the next row
+                const unsigned rank = chunk_rank_row(handle, base[0], s_wave);
                 if (handle && rank < p.max_open) {
                     S[i] = rank + 1u;
                     unsigned* r = work + (size_t)rank * TR_WORK_WORDS;
@@ -371,6 +321,9 @@ __global__ __launch_bounds__(TR_THREADS) void track_carry_kernel(TrackP p) {
             }
         }
         // phase C: the closed events in slot order - the order of their handles in their last frame -, filtered, appended
+        // The ballot scan is written out here, not through chunk_rank_row of region_table.h: this is the one work-group of the
+        // stream and every round of the scan is on its critical path; through the helper the kernel measured 8 - 18 % slower on
+        // frames of many small events (profiles/region_table_ab.json), so this call site keeps the form it had.
         unsigned kept_base = p.counts[s * 6], dropped_n = 0u;            // read by every thread before thread 0 writes it (barriers below)
         for (unsigned r0 = 0; r0 < nold; r0 += TR_THREADS) {             // uniform over the work-group
             const unsigned r = r0 + threadIdx.x;
@@ -403,55 +356,21 @@ __global__ __launch_bounds__(TR_THREADS) void track_carry_kernel(TrackP p) {
     }
 }
 
-struct TrackAcc {
-    unsigned slot;           // 0 = nothing gathered
-    unsigned n, x0, y0, x1, y1;
-    u64 peak, sx, sy;
-};
+static_assert(WK_Y0 == WK_X0 + 1 && WK_X1 == WK_X0 + 2 && WK_Y1 == WK_X0 + 3 && WK_SY == WK_SX + 2, "the words RegionAcc::commit writes");
 
-// Adds the lanes' gathered values to their working records.  `pending` lanes hold a slot in 1 .. max_open; equal slots of the wave
-// are combined first.  Called in converged control flow (the loop is wave-uniform; every round retires at least the leading lane).
-__device__ __forceinline__ void track_flush(bool pending, const TrackAcc& a, unsigned* work, unsigned f, unsigned lane) {
-    u64 left = __ballot(pending);
-    while (left != 0) {
-        const int lead = __builtin_ctzll(left);
-        const unsigned first = (unsigned)__builtin_amdgcn_readlane((int)a.slot, lead);
-        const bool mine = pending && a.slot == first;
-        const u64 same = __ballot(mine);
-        unsigned x0 = mine ? a.x0 : 0xffffffffu, y0 = mine ? a.y0 : 0xffffffffu, x1 = mine ? a.x1 : 0u, y1 = mine ? a.y1 : 0u;
-        unsigned n = mine ? a.n : 0u;
-        u64 peak = mine ? a.peak : 0ull, sx = mine ? a.sx : 0ull, sy = mine ? a.sy : 0ull;
-        if ((same & (same - 1ull)) != 0) {                               // wave-uniform: more than one lane holds this slot
-            for (int m = 32; m >= 1; m >>= 1) {
-                const unsigned ox0 = (unsigned)__shfl_xor((int)x0, m), oy0 = (unsigned)__shfl_xor((int)y0, m);
-                const unsigned ox1 = (unsigned)__shfl_xor((int)x1, m), oy1 = (unsigned)__shfl_xor((int)y1, m);
-                const u64 opeak = __shfl_xor(peak, m);
-                x0 = ox0 < x0 ? ox0 : x0;
-                y0 = oy0 < y0 ? oy0 : y0;
-                x1 = ox1 > x1 ? ox1 : x1;
-                y1 = oy1 > y1 ? oy1 : y1;
-                peak = opeak > peak ? opeak : peak;
-                n += (unsigned)__shfl_xor((int)n, m);
-                sx += __shfl_xor(sx, m);
-                sy += __shfl_xor(sy, m);
-            }
-        }
-        if (lane == (unsigned)lead) {
+// Adds the lanes' gathered values (sw: the pixel count) to their working records: `pending` lanes hold a slot in 1 .. max_open,
+// equal slots of the wave are combined first.
+__device__ __forceinline__ void track_flush(bool pending, const RegionAcc<unsigned>& a, unsigned* work, unsigned f, unsigned lane) {
+    wave_each_key(pending, a.slot, lane, [&](unsigned first, bool mine, bool many, bool lead) {
+        const RegionAcc<unsigned> c = a.combined(mine, many);
+        if (lead) {
             unsigned* r = work + (size_t)(first - 1u) * TR_WORK_WORDS;
-            atomicMin(r + WK_X0, x0);
-            atomicMin(r + WK_Y0, y0);
-            atomicMax(r + WK_X1, x1);
-            atomicMax(r + WK_Y1, y1);
-            atomicAdd(r + WK_NFRAME, n);
-            atomicMax((u64*)(r + WK_NEWPEAK), peak);
-            atomicAdd((u64*)(r + WK_VOLUME), (u64)n);
-            atomicAdd((u64*)(r + WK_SX), sx);
-            atomicAdd((u64*)(r + WK_SY), sy);
-            atomicAdd((u64*)(r + WK_ST), (u64)n * f);
+            c.commit(r, WK_X0, WK_NEWPEAK, WK_SX);
+            atomicAdd(r + WK_NFRAME, c.sw);
+            atomicAdd((u64*)(r + WK_VOLUME), (u64)c.sw);
+            atomicAdd((u64*)(r + WK_ST), (u64)c.sw * f);
         }
-        if (mine) pending = false;
-        left &= ~same;
-    }
+    });
 }
 
 __global__ __launch_bounds__(TR_THREADS) void track_reduce_kernel(TrackP p) {
@@ -464,12 +383,8 @@ __global__ __launch_bounds__(TR_THREADS) void track_reduce_kernel(TrackP p) {
         unsigned* P = tr_plane(p, s);
         unsigned* work = p.work + (size_t)s * p.max_open * TR_WORK_WORDS;
         const unsigned f = tr_header(p, s)[0] - 1u;
-        TrackAcc acc;
-        acc.slot = 0u;
-        acc.n = 0u;
-        acc.x0 = acc.y0 = 0xffffffffu;
-        acc.x1 = acc.y1 = 0u;
-        acc.peak = acc.sx = acc.sy = 0ull;
+        RegionAcc<unsigned> acc;                                         // sw: the pixel count
+        acc.clear();
         unsigned nfg = 0u, nnan = 0u;
         for (unsigned run = blockIdx.x; run < nruns; run += gridDim.x) {  // uniform over the work-group
             for (unsigned j = 0; j < TR_RUN / TR_THREADS; ++j) {         // the same trip count for every lane: converged ballots
@@ -490,25 +405,7 @@ __global__ __launch_bounds__(TR_THREADS) void track_reduce_kernel(TrackP p) {
                 track_flush(acc.slot != 0u && slot != 0u && slot != acc.slot, acc, work, f, lane);
                 if (slot != 0u) {
                     const unsigned y = i / p.w, x = i - y * p.w;
-                    const u64 peak = ((u64)order_key(bits) << 32) | (u64)(~i);
-                    if (slot != acc.slot) {
-                        acc.slot = slot;
-                        acc.n = 1u;
-                        acc.x0 = acc.x1 = x;
-                        acc.y0 = acc.y1 = y;
-                        acc.peak = peak;
-                        acc.sx = x;
-                        acc.sy = y;
-                    } else {
-                        ++acc.n;
-                        acc.x0 = x < acc.x0 ? x : acc.x0;
-                        acc.y0 = y < acc.y0 ? y : acc.y0;
-                        acc.x1 = x > acc.x1 ? x : acc.x1;
-                        acc.y1 = y > acc.y1 ? y : acc.y1;
-                        acc.peak = peak > acc.peak ? peak : acc.peak;
-                        acc.sx += x;
-                        acc.sy += y;
-                    }
+                    acc.add(slot, x, y, ((u64)order_key(bits) << 32) | (u64)(~i), 1u);
                 }
             }
         }
@@ -576,8 +473,6 @@ size_t track_state_words(int h, int w, int max_open) {
 
 size_t track_pad16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
 
-unsigned track_chunks(long long npix) { return (unsigned)((npix + TR_CHUNK - 1) / TR_CHUNK); }
-
 unsigned track_grid_x(unsigned long long items, unsigned cap) { return (unsigned)(items < cap ? (items ? items : 1) : cap); }
 
 struct TrackWs {
@@ -594,7 +489,7 @@ TrackWs track_carve(long long b, int t, int h, int w, int max_open) {
     c.minroot = at;
     at += track_pad16((size_t)b * max_open * 4);
     c.chunk_n = at;
-    at += track_pad16((size_t)b * track_chunks((long long)npix) * 4);
+    at += region_chunk_bytes(b, (long long)npix, 1);
     c.newslot = at;
     at += track_pad16((size_t)b * npix * 4);
     c.work = at;
@@ -664,7 +559,7 @@ int track_run(const char* who, const float* maps, long long b, int t, int h, int
     p.npix = (unsigned)h * (unsigned)w;
     p.w = (unsigned)w;
     p.h = (unsigned)h;
-    p.nchunks = track_chunks(p.npix);
+    p.nchunks = region_chunks(p.npix);
     p.max_open = (unsigned)max_open;
     p.max_closed = (unsigned)max_closed;
     p.min_duration = min_duration;
