@@ -41,14 +41,109 @@ import torch
 from . import hip
 
 MIN_MANTISSA_BITS, MAX_MANTISSA_BITS = hip.HIST_MIN_M, hip.HIST_MAX_M
-_MAGIC = 0x48444156           # "VADH", csrc/score_hist.hip
+_HIST_MAGIC = 0x48444156      # "VADH", csrc/score_hist.hip
 _HEADER_BYTES = 16
 
 
+# ---------------------------------------------------------------------- argument checks, each written once
+# Every entry point below refuses a bad argument with `VadError` before it launches anything, and says which argument of which
+# call it was (`what`).  The wording is part of the interface (tests/test_metrics_messages_plan.py holds every message in full).
+def _is_int(v) -> bool:
+    """A plain integer: True and False are no sizes, counts or choices."""
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def _check_int(v, name: str, what: str, lo: int, hi: int) -> int:
+    if not _is_int(v) or not lo <= int(v) <= hi:
+        raise hip.VadError(f"{what}: {name} must be an int in {lo}..{hi}, got {v!r}")
+    return int(v)
+
+
+def _check_choice(v, name: str, what: str, a: int, b: int) -> int:
+    if not _is_int(v) or int(v) not in (a, b):
+        raise hip.VadError(f"{what}: {name} must be {a} or {b}, got {v!r}")
+    return int(v)
+
+
+def _check_number(v, name: str, what: str, ok, rule: str, error=hip.VadError) -> float:
+    """A real number - no bool, no string - that `ok` accepts; `rule` is what the message says it must be."""
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not ok(v):
+        raise error(f"{what}: {name} must be {rule}, got {v!r}")
+    return float(v)
+
+
 def _check_m(m, what: str) -> int:
-    if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not MIN_MANTISSA_BITS <= int(m) <= MAX_MANTISSA_BITS:
-        raise hip.VadError(f"{what}: mantissa_bits must be an int in {MIN_MANTISSA_BITS}..{MAX_MANTISSA_BITS}, got {m!r}")
-    return int(m)
+    return _check_int(m, "mantissa_bits", what, MIN_MANTISSA_BITS, MAX_MANTISSA_BITS)
+
+
+def _check_connectivity(c, what: str) -> int:
+    return _check_choice(c, "connectivity", what, 4, 8)
+
+
+def _check_structure(connectivity, temporal, what: str) -> Tuple[int, int]:
+    """(connectivity, temporal) of the event volumes: (4, 1), (8, 1) or (8, 9)."""
+    connectivity = _check_connectivity(connectivity, what)
+    temporal = _check_choice(temporal, "temporal", what, 1, 9)
+    if temporal == 9 and connectivity != 8:
+        raise hip.VadError(f"{what}: temporal=9 (the 3 x 3 of the frame before) needs connectivity=8, got connectivity={connectivity}")
+    return connectivity, temporal
+
+
+def _check_threshold(threshold, what: str) -> float:
+    """-> the threshold as the float32 value the kernels compare with."""
+    _check_number(threshold, "threshold", what, lambda v: not np.isnan(v), "a number that is not NaN")
+    return float(np.float32(threshold))
+
+
+def _check_fraction(v, name: str, what: str) -> float:
+    return _check_number(v, name, what, lambda v: 0.0 <= float(v) <= 1.0, "a number in [0, 1]")   # false for NaN
+
+
+# The check of a map batch that `detect_regions`, `detect_events`, `EventTracker.update` and `MapStatistics` share, in the order they
+# keep; each goes on with a layout step of its own.  `smooth_maps` and `morph_maps` spell their checks out, and `gaussian_taps` its
+# two: on a small frame they are calls of 13 us that the host paces, and the helpers' own calls showed in them, beyond what a second
+# copy of the parent shows against the parent (profiles/metrics_args_ab.json); `MapStatistics.normalize` is written like them.
+def _check_maps(maps, what: str, where: str, device=None) -> None:
+    """A map batch is a tensor, on the GPU (`where`: what the message says runs there; "" = nothing) - on `device`, for the
+    statistics, which have one -, and float32."""
+    if not isinstance(maps, torch.Tensor):
+        raise hip.VadError(f"{what}: maps must be a torch tensor")
+    if not maps.is_cuda:
+        raise hip.VadError(f"{what}: maps ({maps.device}) must be on the GPU ({where}{'; ' if where else ''}there is no CPU fallback)")
+    if device is not None and maps.device != device:
+        raise hip.VadError(f"{what}: maps ({maps.device}) must be on the statistics' device {device}")
+    if maps.dtype != torch.float32:
+        raise hip.VadError(f"{what}: maps must be float32, got {maps.dtype}")
+
+
+# ---------------------------------------------------------------------- the launch epilogue
+def _count(name: str) -> None:
+    """One more call of a native entry point: `hip.calls` is how tests see that the device path really ran."""
+    hip.calls[name] = hip.calls.get(name, 0) + 1
+
+
+def _workspace(nbytes: int, device, what: str, out_of_range: str) -> torch.Tensor:
+    """A workspace of the size the library asked for; a size of 0 is its answer to shapes it does not take."""
+    if nbytes == 0:
+        raise hip.VadError(f"{what}: {out_of_range}")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _flag_word(ws: torch.Tensor) -> int:
+    """The labelling kernels' flag word, the first four bytes of their workspace: one 4-byte copy, which waits for the call."""
+    return int(ws[:4].view(torch.int32).item())
+
+
+def _raise_on_flags(flags: int, what: str) -> None:
+    if flags:
+        raise hip.VadError(f"{what}: flags {flags:#x} are set - a walk of the labelling kernels ran out of its step bound (bit 0) or a "
+                           "region has no size (bit 1); the labels and counters of this evaluation are not to be trusted")
+
+
+def _launched(ws: torch.Tensor, what: str) -> None:
+    """After a labelling launch of the entry point `what`: count it, read its flag word, raise if a bit is set."""
+    _count(what)
+    _raise_on_flags(_flag_word(ws), what)
 
 
 def num_bins(mantissa_bits: int) -> int:
@@ -81,43 +176,78 @@ def allreduce_counters_(counters: torch.Tensor, group=None, force_collective: bo
     return world
 
 
-class ScoreHistogram:
-    """Counters of (score bin, class) in one device blob (include/vad_hip.h `vad_hist_*`).
+class _CounterBlob:
+    """What `ScoreHistogram` and `ProHistogram` share: one blob - a 16-byte header (magic, ABI version and mantissa_bits), then
+    uint64 counters - on a GPU, where the library writes it, or on the host as a container.  A subclass sets `mantissa_bits`, names
+    its magic, the library's functions (`_LIB`_state_bytes / _reset) and its kind for the messages, and lays out the words."""
+    _MAGIC, _LIB, _NAME, _KIND = 0, "", "", ""
 
-    `accumulate(values, labels)` adds a batch on the GPU; `counts()` / `rejected()` are int64 device tensors, `counts_host()` is the
-    one host read (16 * (255 << m) bytes: 8 MB at the default m = 11); `merge`, `all_reduce`, `state_dict` / `load_state_dict`
-    combine and carry states.  With `device="cpu"` the object is a container for counters (load, merge, all-reduce, read):
-    accumulating runs on the GPU only and there is no CPU fallback."""
-
-    def __init__(self, mantissa_bits: int = 11, device="cuda"):
-        self.mantissa_bits = _check_m(mantissa_bits, "ScoreHistogram")
+    def _allocate(self, device, nbytes: int) -> None:
         self.nbins = 255 << self.mantissa_bits
         self.device = torch.device(device)
         if self.device.type == "cuda" and self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
-        self._state = torch.empty(state_bytes(self.mantissa_bits), dtype=torch.uint8, device=self.device)
+        self._state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         if self.device.type == "cuda":
-            assert hip.lib().vad_hist_state_bytes(self.mantissa_bits) == self._state.numel()
+            assert getattr(hip.lib(), f"{self._LIB}_state_bytes")(self.mantissa_bits) == self._state.numel()
         self.reset()
 
-    # ------------------------------------------------------------------ state
     def _words(self) -> torch.Tensor:
-        """counts[2][nbins] then rejected[2] as one int64 view of the blob (the uint64 counters stay below 2^63)."""
+        """Everything behind the header as one int64 view of the blob (the uint64 counters stay below 2^63)."""
         return self._state[_HEADER_BYTES:].view(torch.int64)
 
     def _header(self) -> np.ndarray:
         m = self.mantissa_bits
-        return np.array([_MAGIC, (hip.ABI_VERSION << 16) | m, m, 0], np.uint32)
+        return np.array([self._MAGIC, (hip.ABI_VERSION << 16) | m, m, 0], np.uint32)
 
-    def reset(self) -> "ScoreHistogram":
+    def reset(self):
         if self.device.type == "cuda":
             with torch.cuda.device(self.device):
-                hip.check(hip.lib().vad_hist_reset(self._state.data_ptr(), self.mantissa_bits, hip.current_stream()), "vad_hist_reset")
+                hip.check(getattr(hip.lib(), f"{self._LIB}_reset")(self._state.data_ptr(), self.mantissa_bits, hip.current_stream()),
+                          f"{self._LIB}_reset")
         else:
             self._state.zero_()
             self._state[:_HEADER_BYTES] = torch.from_numpy(self._header().view(np.uint8).copy())
         return self
 
+    def _host_words(self) -> np.ndarray:
+        """The words behind the header as numpy int64: the one device -> host read.  The header travels with them and is checked."""
+        blob = self._state.cpu().numpy()
+        if not np.array_equal(blob[:_HEADER_BYTES].view(np.uint32), self._header()):
+            raise hip.VadError(f"{self._NAME}: the state's header is not that of {self._KIND} with mantissa_bits "
+                               f"{self.mantissa_bits} (the blob was overwritten)")
+        return blob[_HEADER_BYTES:].view(np.int64)
+
+    def _check_saved_m(self, state: dict) -> None:
+        if state.get("mantissa_bits") != self.mantissa_bits:
+            raise hip.VadError(f"{self._NAME}.load_state_dict: mantissa_bits {state.get('mantissa_bits')!r} of the saved state differs "
+                               f"from this histogram's {self.mantissa_bits}")
+
+    def _check_merge(self, other, cls) -> None:
+        name = self._NAME
+        if not isinstance(other, cls):
+            raise hip.VadError(f"{name}.merge: other must be a {name}, got {type(other).__name__}")
+        if other.mantissa_bits != self.mantissa_bits:
+            raise hip.VadError(f"{name}.merge: mantissa_bits differ ({self.mantissa_bits} and {other.mantissa_bits}); bins of "
+                               "different widths cannot be added")
+        if other is self:
+            raise hip.VadError(f"{name}.merge: other is this histogram")
+
+
+class ScoreHistogram(_CounterBlob):
+    """Counters of (score bin, class) in one device blob (include/vad_hip.h `vad_hist_*`): counts[2][nbins], then rejected[2].
+
+    `accumulate(values, labels)` adds a batch on the GPU; `counts()` / `rejected()` are int64 device tensors, `counts_host()` is the
+    one host read (16 * (255 << m) bytes: 8 MB at the default m = 11); `merge`, `all_reduce`, `state_dict` / `load_state_dict`
+    combine and carry states.  With `device="cpu"` the object is a container for counters (load, merge, all-reduce, read):
+    accumulating runs on the GPU only and there is no CPU fallback."""
+    _MAGIC, _LIB, _NAME, _KIND = _HIST_MAGIC, "vad_hist", "ScoreHistogram", "a histogram"
+
+    def __init__(self, mantissa_bits: int = 11, device="cuda"):
+        self.mantissa_bits = _check_m(mantissa_bits, "ScoreHistogram")
+        self._allocate(device, state_bytes(self.mantissa_bits))
+
+    # ------------------------------------------------------------------ state
     def counts(self) -> torch.Tensor:
         """int64 [2, nbins] on the histogram's device (a copy): row 0 = normal, row 1 = anomalous."""
         return self._words()[:2 * self.nbins].view(2, self.nbins).clone()
@@ -129,21 +259,14 @@ class ScoreHistogram:
     def counts_host(self) -> np.ndarray:
         """The counters as numpy int64 [2, nbins]: the one device -> host read of an evaluation.  The blob's header travels with
         them and is checked."""
-        blob = self._state.cpu().numpy()
-        if not np.array_equal(blob[:_HEADER_BYTES].view(np.uint32), self._header()):
-            raise hip.VadError("ScoreHistogram: the state's header is not that of a histogram with mantissa_bits "
-                               f"{self.mantissa_bits} (the blob was overwritten)")
-        return blob[_HEADER_BYTES:_HEADER_BYTES + 16 * self.nbins].view(np.int64).reshape(2, self.nbins).copy()
+        return self._host_words()[:2 * self.nbins].reshape(2, self.nbins).copy()
 
     def state_dict(self) -> dict:
         """{'mantissa_bits', 'counts' int64 [2, nbins], 'rejected' int64 [2]} on the host: resume a long evaluation later."""
         return {"mantissa_bits": self.mantissa_bits, "counts": self.counts().cpu(), "rejected": self.rejected().cpu()}
 
     def load_state_dict(self, state: dict) -> "ScoreHistogram":
-        m = state.get("mantissa_bits")
-        if m != self.mantissa_bits:
-            raise hip.VadError(f"ScoreHistogram.load_state_dict: mantissa_bits {m!r} of the saved state differs from this histogram's "
-                               f"{self.mantissa_bits}")
+        self._check_saved_m(state)
         counts = torch.as_tensor(np.asarray(state["counts"]))
         rejected = torch.as_tensor(np.asarray(state["rejected"]))
         if tuple(counts.shape) != (2, self.nbins) or tuple(rejected.shape) != (2,) or counts.dtype != torch.int64 or rejected.dtype != torch.int64:
@@ -161,7 +284,7 @@ class ScoreHistogram:
             hip.check(hip.lib().vad_hist_accumulate(values.data_ptr(), n_groups, group_elems, labels.data_ptr(), label_format,
                                                     self._state.data_ptr(), self.mantissa_bits, hip.current_stream()),
                       "vad_hist_accumulate")
-        hip.calls["hist_accumulate"] = hip.calls.get("hist_accumulate", 0) + 1
+        _count("hist_accumulate")
 
     def accumulate(self, values: torch.Tensor, labels: torch.Tensor) -> "ScoreHistogram":
         """Add a batch.  `values`: float32 GPU tensor of any shape (an error map [B,1,H,W], frame scores [B,T], ...).  `labels`:
@@ -206,13 +329,7 @@ class ScoreHistogram:
     # ------------------------------------------------------------------ combine
     def merge(self, other: "ScoreHistogram") -> "ScoreHistogram":
         """self += other (counts and rejected): two streams, or states gathered from elsewhere."""
-        if not isinstance(other, ScoreHistogram):
-            raise hip.VadError(f"ScoreHistogram.merge: other must be a ScoreHistogram, got {type(other).__name__}")
-        if other.mantissa_bits != self.mantissa_bits:
-            raise hip.VadError(f"ScoreHistogram.merge: mantissa_bits differ ({self.mantissa_bits} and {other.mantissa_bits}); bins of "
-                               "different widths cannot be added")
-        if other is self:
-            raise hip.VadError("ScoreHistogram.merge: other is this histogram")
+        self._check_merge(other, ScoreHistogram)
         if self.device.type == "cuda" and other.device == self.device:
             with torch.cuda.device(self.device):
                 hip.check(hip.lib().vad_hist_merge(self._state.data_ptr(), other._state.data_ptr(), self.mantissa_bits,
@@ -232,6 +349,11 @@ class ScoreHistogram:
 
 
 # ====================================================================== host half: numpy, float64 from integer counts
+def _mantissa_bits_of(nbins: int) -> Optional[int]:
+    """The m with 255 << m == nbins, or None."""
+    return next((k for k in range(MIN_MANTISSA_BITS, MAX_MANTISSA_BITS + 1) if 255 << k == nbins), None)
+
+
 def _as_counts(counts) -> Tuple[np.ndarray, np.ndarray, int]:
     """-> (neg int64 [nbins], pos int64 [nbins], mantissa_bits)."""
     if isinstance(counts, torch.Tensor):
@@ -239,7 +361,7 @@ def _as_counts(counts) -> Tuple[np.ndarray, np.ndarray, int]:
     c = np.asarray(counts)
     if c.ndim != 2 or c.shape[0] != 2 or not np.issubdtype(c.dtype, np.integer):
         raise ValueError(f"counts must be an integer array [2, nbins], got {c.dtype} {c.shape}")
-    m = next((k for k in range(MIN_MANTISSA_BITS, MAX_MANTISSA_BITS + 1) if 255 << k == c.shape[1]), None)
+    m = _mantissa_bits_of(c.shape[1])
     if m is None:
         raise ValueError(f"counts has {c.shape[1]} bins: not 255 << m for a mantissa_bits m in {MIN_MANTISSA_BITS}..{MAX_MANTISSA_BITS}")
     c = c.astype(np.int64, copy=False)
@@ -259,6 +381,18 @@ def _total(c: np.ndarray) -> int:
     if len(c) == 0:
         return 0
     return int(c.sum()) if float(c.max()) * len(c) < 2.0 ** 62 else sum(c.tolist())
+
+
+def _exact_cumsum(c: np.ndarray) -> np.ndarray:
+    """Running sums of non-negative int64 / uint64 counters as float64, each rounded once: in int64 while the total stays below
+    2^62, in Python integers near 2^63."""
+    if len(c) and float(c.max()) * len(c) < 2.0 ** 62:
+        return np.cumsum(c.astype(np.int64)).astype(np.float64)
+    sums, run = [], 0
+    for v in c.tolist():
+        run += v
+        sums.append(float(run))
+    return np.array(sums, np.float64)
 
 
 def _populated(counts, what: str):
@@ -380,7 +514,7 @@ def _pro_points(wpos, neg, regions, what: str):
     q = np.asarray(neg.detach().cpu().numpy() if isinstance(neg, torch.Tensor) else neg)
     if w.ndim != 1 or q.shape != w.shape or not np.issubdtype(w.dtype, np.integer) or not np.issubdtype(q.dtype, np.integer):
         raise ValueError(f"{what}: wpos and neg must be integer arrays [nbins] of one length, got {w.dtype} {w.shape} and {q.dtype} {q.shape}")
-    m = next((k for k in range(MIN_MANTISSA_BITS, MAX_MANTISSA_BITS + 1) if 255 << k == w.shape[0]), None)
+    m = _mantissa_bits_of(w.shape[0])
     if m is None:
         raise ValueError(f"{what}: {w.shape[0]} bins are not 255 << m for a mantissa_bits m in {MIN_MANTISSA_BITS}..{MAX_MANTISSA_BITS}")
     if w.dtype == np.int64:
@@ -397,25 +531,8 @@ def _pro_points(wpos, neg, regions, what: str):
     n_neg = _total(q)
     if n_neg == 0:
         raise ValueError(f"{what}: no normal pixel")
-    if len(w) and float(w.max()) * len(w) < 2.0 ** 62:
-        cw = np.cumsum(w.astype(np.int64)).astype(np.float64)
-    else:                                                              # near 2^63: Python integers, each rounded once
-        cw, run = [], 0
-        for v in w.tolist():
-            run += v
-            cw.append(run)
-        cw = np.array([float(v) for v in cw], np.float64)
-    denom = float(regions << PRO_WEIGHT_BITS)
-    if float(q.max()) * len(q) < 2.0 ** 62:
-        cq = np.cumsum(q).astype(np.float64)
-    else:
-        cq, run = [], 0
-        for v in q.tolist():
-            run += v
-            cq.append(run)
-        cq = np.array([float(v) for v in cq], np.float64)
-    fpr = np.concatenate([[0.0], cq / float(n_neg)])
-    pro = np.concatenate([[0.0], cw / denom])
+    fpr = np.concatenate([[0.0], _exact_cumsum(q) / float(n_neg)])
+    pro = np.concatenate([[0.0], _exact_cumsum(w) / float(regions << PRO_WEIGHT_BITS)])
     return keys, fpr, pro, m
 
 
@@ -438,9 +555,7 @@ def aupro_from_counts(wpos, neg, regions, max_region, fpr_limit: float = 0.3) ->
     a vertex of the exact curve, which is monotone between two of them: the areas differ by at most 0.5 * dFPR * dPRO per whole
     segment and (fpr_limit - FPR_0) * dPRO on the cut one, all divided by `fpr_limit`.
     |aupro - AUPRO of the unquantised scores| <= quant_bound + weight_bound."""
-    if isinstance(fpr_limit, bool) or not isinstance(fpr_limit, (int, float, np.floating, np.integer)) or not 0.0 < float(fpr_limit) <= 1.0:
-        raise ValueError(f"aupro_from_counts: fpr_limit must be in (0, 1], got {fpr_limit!r}")
-    limit = float(fpr_limit)
+    limit = _check_number(fpr_limit, "fpr_limit", "aupro_from_counts", lambda v: 0.0 < float(v) <= 1.0, "in (0, 1]", ValueError)
     _, fpr, pro, _ = _pro_points(wpos, neg, regions, "aupro_from_counts")
     max_region = int(max_region)
     if max_region <= 0:
@@ -455,12 +570,6 @@ def aupro_from_counts(wpos, neg, regions, max_region, fpr_limit: float = 0.3) ->
         area += float((limit - f0) * (p0 + p_cut) * 0.5)
         bound += float((limit - f0) * (p1 - p0))
     return area / limit, bound / limit, max_region / float(1 << (PRO_WEIGHT_BITS + 1))
-
-
-def _check_connectivity(c, what: str) -> int:
-    if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or int(c) not in (4, 8):
-        raise hip.VadError(f"{what}: connectivity must be 4 or 8, got {c!r}")
-    return int(c)
 
 
 def _mask_planes(masks: torch.Tensor, what: str):
@@ -478,16 +587,8 @@ def _mask_planes(masks: torch.Tensor, what: str):
 
 
 def _pro_workspace(n: int, h: int, w: int, device, what: str) -> torch.Tensor:
-    size = hip.lib().vad_pro_workspace_bytes(n, h, w)
-    if size == 0:
-        raise hip.VadError(f"{what}: {n} masks of {h} x {w} are out of range (h * w < 2^31 - 1, n * h * w <= 2^38)")
-    return torch.empty(size, dtype=torch.uint8, device=device)
-
-
-def _raise_on_flags(flags: int, what: str) -> None:
-    if flags:
-        raise hip.VadError(f"{what}: flags {flags:#x} are set - a walk of the labelling kernels ran out of its step bound (bit 0) or a "
-                           "region has no size (bit 1); the labels and counters of this evaluation are not to be trusted")
+    return _workspace(hip.lib().vad_pro_workspace_bytes(n, h, w), device, what,
+                      f"{n} masks of {h} x {w} are out of range (h * w < 2^31 - 1, n * h * w <= 2^38)")
 
 
 def label_regions(masks: torch.Tensor, connectivity: int = 8) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -508,12 +609,11 @@ def label_regions(masks: torch.Tensor, connectivity: int = 8) -> Tuple[torch.Ten
         ws = _pro_workspace(b, h, w, m.device, "label_regions")
         hip.check(hip.lib().vad_label_regions(m.data_ptr(), fmt, b, h, w, connectivity, labels.data_ptr(), sizes.data_ptr(),
                                               ws.data_ptr(), ws.numel(), hip.current_stream()), "vad_label_regions")
-    hip.calls["label_regions"] = hip.calls.get("label_regions", 0) + 1
-    _raise_on_flags(int(ws[:4].view(torch.int32).item()), "label_regions")
+    _launched(ws, "label_regions")
     return labels, sizes
 
 
-class ProHistogram:
+class ProHistogram(_CounterBlob):
     """The counters of the per-region overlap in one device blob (include/vad_hip.h `vad_pro_*`): the weighted histogram `wpos`
     of the anomalous pixels, their plain histogram `pos` and the normal pixels' `neg` - `counts()` is what a `ScoreHistogram` of
     the same batches would hold, so `auroc()` comes with it -, the number of regions, the largest region, rejected values per
@@ -521,39 +621,17 @@ class ProHistogram:
 
     `accumulate(values, masks)` labels the masks and adds the batch on the GPU, asynchronously; `aupro()` is the one host read
     (24 * (255 << m) bytes: 12 MB at the default m = 11).  With `device="cpu"` the object is a container for counters (load,
-    merge, all-reduce, read): accumulating runs on the GPU only and there is no CPU fallback."""
+    merge, all-reduce, read): accumulating runs on the GPU only and there is no CPU fallback.  The words behind the header: wpos,
+    pos, neg [nbins] each, then regions, max_region, rejected[2], flags."""
+    _MAGIC, _LIB, _NAME, _KIND = _PRO_MAGIC, "vad_pro", "ProHistogram", "a per-region histogram"
 
     def __init__(self, mantissa_bits: int = 11, device="cuda", connectivity: int = 8):
         self.mantissa_bits = _check_m(mantissa_bits, "ProHistogram")
         self.connectivity = _check_connectivity(connectivity, "ProHistogram")
-        self.nbins = 255 << self.mantissa_bits
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self._state = torch.empty(pro_state_bytes(self.mantissa_bits), dtype=torch.uint8, device=self.device)
         self._ws = None
-        if self.device.type == "cuda":
-            assert hip.lib().vad_pro_state_bytes(self.mantissa_bits) == self._state.numel()
-        self.reset()
+        self._allocate(device, pro_state_bytes(self.mantissa_bits))
 
     # ------------------------------------------------------------------ state
-    def _words(self) -> torch.Tensor:
-        """wpos, pos, neg [nbins] each, then regions, max_region, rejected[2], flags: one int64 view of the blob."""
-        return self._state[_HEADER_BYTES:].view(torch.int64)
-
-    def _header(self) -> np.ndarray:
-        m = self.mantissa_bits
-        return np.array([_PRO_MAGIC, (hip.ABI_VERSION << 16) | m, m, 0], np.uint32)
-
-    def reset(self) -> "ProHistogram":
-        if self.device.type == "cuda":
-            with torch.cuda.device(self.device):
-                hip.check(hip.lib().vad_pro_reset(self._state.data_ptr(), self.mantissa_bits, hip.current_stream()), "vad_pro_reset")
-        else:
-            self._state.zero_()
-            self._state[:_HEADER_BYTES] = torch.from_numpy(self._header().view(np.uint8).copy())
-        return self
-
     def weighted(self) -> torch.Tensor:
         """int64 [nbins] on the histogram's device (a copy): the bits of the uint64 sums of W(r) per bin."""
         return self._words()[:self.nbins].clone()
@@ -584,11 +662,7 @@ class ProHistogram:
 
     def _host(self):
         """(wpos uint64 [nbins], pos, neg int64 [nbins], tail): the one device -> host read; header and flags are checked."""
-        blob = self._state.cpu().numpy()
-        if not np.array_equal(blob[:_HEADER_BYTES].view(np.uint32), self._header()):
-            raise hip.VadError("ProHistogram: the state's header is not that of a per-region histogram with mantissa_bits "
-                               f"{self.mantissa_bits} (the blob was overwritten)")
-        words = blob[_HEADER_BYTES:].view(np.int64)
+        words = self._host_words()
         tail = words[3 * self.nbins:].tolist()
         _raise_on_flags(tail[4], "ProHistogram")
         nb = self.nbins
@@ -603,9 +677,7 @@ class ProHistogram:
                 "rejected": w[3 * nb + 2:3 * nb + 4].clone(), "flags": int(w[3 * nb + 4])}
 
     def load_state_dict(self, state: dict) -> "ProHistogram":
-        if state.get("mantissa_bits") != self.mantissa_bits:
-            raise hip.VadError(f"ProHistogram.load_state_dict: mantissa_bits {state.get('mantissa_bits')!r} of the saved state differs "
-                               f"from this histogram's {self.mantissa_bits}")
+        self._check_saved_m(state)
         if state.get("connectivity") != self.connectivity:
             raise hip.VadError(f"ProHistogram.load_state_dict: connectivity {state.get('connectivity')!r} of the saved state differs "
                                f"from this histogram's {self.connectivity}")
@@ -659,22 +731,16 @@ class ProHistogram:
             hip.check(hip.lib().vad_pro_accumulate(values.data_ptr(), m.data_ptr(), fmt, b, h, w, self.connectivity,
                                                    self._state.data_ptr(), self.mantissa_bits, self._ws.data_ptr(), self._ws.numel(),
                                                    hip.current_stream()), "vad_pro_accumulate")
-        hip.calls["pro_accumulate"] = hip.calls.get("pro_accumulate", 0) + 1
+        _count("pro_accumulate")
         return self
 
     # ------------------------------------------------------------------ combine
     def merge(self, other: "ProHistogram") -> "ProHistogram":
         """self += other: sums of the counters, the larger max_region, the union of the flags."""
-        if not isinstance(other, ProHistogram):
-            raise hip.VadError(f"ProHistogram.merge: other must be a ProHistogram, got {type(other).__name__}")
-        if other.mantissa_bits != self.mantissa_bits:
-            raise hip.VadError(f"ProHistogram.merge: mantissa_bits differ ({self.mantissa_bits} and {other.mantissa_bits}); bins of "
-                               "different widths cannot be added")
+        self._check_merge(other, ProHistogram)
         if other.connectivity != self.connectivity:
             raise hip.VadError(f"ProHistogram.merge: connectivity differs ({self.connectivity} and {other.connectivity}); regions "
                                "of different definitions cannot be averaged")
-        if other is self:
-            raise hip.VadError("ProHistogram.merge: other is this histogram")
         if self.device.type == "cuda" and other.device == self.device:
             with torch.cuda.device(self.device):
                 hip.check(hip.lib().vad_pro_merge(self._state.data_ptr(), other._state.data_ptr(), self.mantissa_bits,
@@ -815,7 +881,7 @@ def smooth_maps(maps: torch.Tensor, sigma: float = 4.0, truncate: float = 4.0, o
             ws = torch.empty(need, dtype=torch.uint8, device=maps.device) if need else None
             hip.check(l.vad_smooth_maps(maps.data_ptr(), n, h, w, taps.data_ptr(), r, hip.ptr(out), hip.ptr(fmax), hip.ptr(ws), need,
                                         hip.current_stream()), "vad_smooth_maps")
-            hip.calls["smooth_maps"] = hip.calls.get("smooth_maps", 0) + 1
+            _count("smooth_maps")
     if only:
         return fmax
     return (out, fmax) if return_max else out
@@ -832,10 +898,9 @@ MORPH_MAX_STEPS = 4
 
 def _morph_size(size, what: str) -> Tuple[int, int]:
     """An int or (size_h, size_w), each in 1..31 -> (size_h, size_w)."""
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
-    if is_int(size):
+    if _is_int(size):
         size = (size, size)
-    if not isinstance(size, (tuple, list)) or len(size) != 2 or not all(is_int(v) for v in size):
+    if not isinstance(size, (tuple, list)) or len(size) != 2 or not all(_is_int(v) for v in size):
         raise hip.VadError(f"{what}: size must be an int or (size_h, size_w), got {size!r}")
     sh, sw = int(size[0]), int(size[1])
     if not (1 <= sh <= MORPH_MAX_SIZE and 1 <= sw <= MORPH_MAX_SIZE):
@@ -905,7 +970,7 @@ def morph_maps(maps: torch.Tensor, op: str, size, out: Optional[torch.Tensor] = 
             out = torch.empty_like(maps)
         if n > 0:
             hip.check(hip.lib().vad_morph_maps(maps.data_ptr(), n, h, w, code, sh, sw, out.data_ptr(), hip.current_stream()), "vad_morph_maps")
-            hip.calls["morph_maps"] = hip.calls.get("morph_maps", 0) + 1
+            _count("morph_maps")
     return out
 
 
@@ -1012,41 +1077,30 @@ def detect_regions(maps: torch.Tensor, threshold: float, connectivity: int = 8, 
     reads the kernels' flag word (one 4-byte copy, which waits for the call) and raises VadError if it is set.  No CPU fallback."""
     what = "detect_regions"
     connectivity = _check_connectivity(connectivity, what)
-    if not isinstance(maps, torch.Tensor):
-        raise hip.VadError(f"{what}: maps must be a torch tensor")
-    if not maps.is_cuda:
-        raise hip.VadError(f"{what}: maps ({maps.device}) must be on the GPU (regions are detected on the device; there is no CPU fallback)")
-    if maps.dtype != torch.float32:
-        raise hip.VadError(f"{what}: maps must be float32, got {maps.dtype}")
-    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)) or np.isnan(threshold):
-        raise hip.VadError(f"{what}: threshold must be a number that is not NaN, got {threshold!r}")
-    for name, v, hi in (("min_area", min_area, 2 ** 32 - 1), ("max_regions", max_regions, MAX_REGIONS)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= hi:
-            raise hip.VadError(f"{what}: {name} must be an int in 1..{hi}, got {v!r}")
-    min_area, max_regions = int(min_area), int(max_regions)
+    _check_maps(maps, what, "regions are detected on the device")
+    threshold = _check_threshold(threshold, what)
+    min_area = _check_int(min_area, "min_area", what, 1, 2 ** 32 - 1)
+    max_regions = _check_int(max_regions, "max_regions", what, 1, MAX_REGIONS)
     frames, lead = _region_frames(maps, what)
     n, h, w = frames.shape
     if n == 0:                                                            # nothing to detect, nothing to launch
         return Regions(torch.zeros((*lead, max_regions, REGION_WORDS), dtype=torch.int32, device=frames.device),
                        torch.zeros((*lead, 4), dtype=torch.int32, device=frames.device),
                        torch.zeros((*lead, h, w), dtype=torch.int32, device=frames.device) if return_labels else None, (h, w),
-                       float(np.float32(threshold)), connectivity, min_area)
+                       threshold, connectivity, min_area)
     with torch.cuda.device(frames.device):
         l = hip.lib()
-        size = l.vad_regions_workspace_bytes(n, h, w, 1 if return_labels else 0)
-        if size == 0:
-            raise hip.VadError(f"{what}: {n} frames of {h} x {w} are out of range (h * w < 2^31 - 1, n * h * w <= 2^38)")
-        ws = torch.empty(size, dtype=torch.uint8, device=frames.device)
+        ws = _workspace(l.vad_regions_workspace_bytes(n, h, w, 1 if return_labels else 0), frames.device, what,
+                        f"{n} frames of {h} x {w} are out of range (h * w < 2^31 - 1, n * h * w <= 2^38)")
         records = torch.empty((n, max_regions, REGION_WORDS), dtype=torch.int32, device=frames.device)
         counts = torch.empty((n, 4), dtype=torch.int32, device=frames.device)
         labels = torch.empty((n, h, w), dtype=torch.int32, device=frames.device) if return_labels else None
-        hip.check(l.vad_detect_regions(frames.data_ptr(), n, h, w, float(np.float32(threshold)), connectivity, min_area, max_regions,
+        hip.check(l.vad_detect_regions(frames.data_ptr(), n, h, w, threshold, connectivity, min_area, max_regions,
                                        hip.ptr(labels), records.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(),
                                        hip.current_stream()), "vad_detect_regions")
-    hip.calls["detect_regions"] = hip.calls.get("detect_regions", 0) + 1
-    _raise_on_flags(int(ws[:4].view(torch.int32).item()), what)
+    _launched(ws, what)
     return Regions(records.view(*lead, max_regions, REGION_WORDS), counts.view(*lead, 4),
-                   labels.view(*lead, h, w) if return_labels else None, (h, w), float(np.float32(threshold)), connectivity, min_area)
+                   labels.view(*lead, h, w) if return_labels else None, (h, w), threshold, connectivity, min_area)
 
 
 # ====================================================================== detections against ground-truth masks
@@ -1106,20 +1160,11 @@ class Matches:
         return out
 
 
-def _check_fraction(v, name: str, what: str) -> float:
-    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) <= 1.0:   # false for NaN
-        raise hip.VadError(f"{what}: {name} must be a number in [0, 1], got {v!r}")
-    return float(v)
-
-
 def _match_params(what: str, threshold, connectivity, min_area, gt_fraction, pred_fraction) -> dict:
     """The checked operating point of `match_regions` / `DetectionCounts`: what two sets of counters must share to be added."""
     connectivity = _check_connectivity(connectivity, what)
-    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)) or np.isnan(threshold):
-        raise hip.VadError(f"{what}: threshold must be a number that is not NaN, got {threshold!r}")
-    if isinstance(min_area, bool) or not isinstance(min_area, (int, np.integer)) or not 1 <= int(min_area) <= 2 ** 32 - 1:
-        raise hip.VadError(f"{what}: min_area must be an int in 1..{2 ** 32 - 1}, got {min_area!r}")
-    return {"threshold": float(np.float32(threshold)), "connectivity": connectivity, "min_area": int(min_area),
+    return {"threshold": _check_threshold(threshold, what), "connectivity": connectivity,
+            "min_area": _check_int(min_area, "min_area", what, 1, 2 ** 32 - 1),
             "gt_fraction": _check_fraction(gt_fraction, "gt_fraction", what), "pred_fraction": _check_fraction(pred_fraction, "pred_fraction", what)}
 
 
@@ -1136,15 +1181,15 @@ def match_regions(maps: torch.Tensor, masks: torch.Tensor, threshold: float, con
     word (one 4-byte copy, which waits for the call) and raises VadError if it is set.  No CPU fallback."""
     what = "match_regions"
     params = _match_params(what, threshold, connectivity, min_area, gt_fraction, pred_fraction)
+    # maps and masks are refused together, in words of their own, and the device comes after the shapes: of `_check_maps` only the
+    # float32 line has a counterpart here, and it is written out
     if not isinstance(maps, torch.Tensor) or not isinstance(masks, torch.Tensor):
         raise hip.VadError(f"{what}: maps and masks must be torch tensors")
     if maps.dtype != torch.float32:
         raise hip.VadError(f"{what}: maps must be float32, got {maps.dtype}")
     if masks.is_complex():
         raise hip.VadError(f"{what}: masks must be float, uint8, bool or integer, got {masks.dtype}")
-    if isinstance(max_regions, bool) or not isinstance(max_regions, (int, np.integer)) or not 1 <= int(max_regions) <= MAX_REGIONS:
-        raise hip.VadError(f"{what}: max_regions must be an int in 1..{MAX_REGIONS}, got {max_regions!r}")
-    max_regions = int(max_regions)
+    max_regions = _check_int(max_regions, "max_regions", what, 1, MAX_REGIONS)
     if maps.dim() not in (3, 4, 5) or masks.dim() not in (3, 4, 5) or masks.numel() != maps.numel() or masks.shape[-2:] != maps.shape[-2:] \
             or masks.shape[0] != maps.shape[0]:
         raise hip.VadError(f"{what}: masks {tuple(masks.shape)} do not match maps {tuple(maps.shape)}")
@@ -1163,10 +1208,8 @@ def match_regions(maps: torch.Tensor, masks: torch.Tensor, threshold: float, con
                        torch.zeros((*lead, MATCH_COUNTS), dtype=torch.int64, device=dev), (h, w), params)
     with torch.cuda.device(dev):
         l = hip.lib()
-        size = l.vad_match_workspace_bytes(n, h, w)
-        if size == 0:
-            raise hip.VadError(f"{what}: {n} frames of {h} x {w} are out of range (h * w < 2^31 - 1, n * h * w <= 2^38)")
-        ws = torch.empty(size, dtype=torch.uint8, device=dev)
+        ws = _workspace(l.vad_match_workspace_bytes(n, h, w), dev, what,
+                        f"{n} frames of {h} x {w} are out of range (h * w < 2^31 - 1, n * h * w <= 2^38)")
         gt_records = torch.empty((n, max_regions, MATCH_WORDS), dtype=torch.int32, device=dev)
         pred_records = torch.empty((n, max_regions, MATCH_WORDS), dtype=torch.int32, device=dev)
         counts = torch.empty((n, MATCH_COUNTS), dtype=torch.int64, device=dev)
@@ -1174,8 +1217,7 @@ def match_regions(maps: torch.Tensor, masks: torch.Tensor, threshold: float, con
                                       params["min_area"], params["gt_fraction"], params["pred_fraction"], max_regions,
                                       gt_records.data_ptr(), pred_records.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(),
                                       hip.current_stream()), "vad_match_regions")
-    hip.calls["match_regions"] = hip.calls.get("match_regions", 0) + 1
-    _raise_on_flags(int(ws[:4].view(torch.int32).item()), what)
+    _launched(ws, what)
     return Matches(gt_records.view(*lead, max_regions, MATCH_WORDS), pred_records.view(*lead, max_regions, MATCH_WORDS),
                    counts.view(*lead, MATCH_COUNTS), (h, w), params)
 
@@ -1362,24 +1404,12 @@ def detect_events(maps: torch.Tensor, threshold: float, connectivity: int = 8, t
     first voxel (scipy's numbering), the first `max_events` (1..65536) written.  Returns an `Events`; like `detect_regions` it reads
     the kernels' flag word (one 4-byte copy, which waits for the call) and raises VadError if it is set.  No CPU fallback."""
     what = "detect_events"
-    connectivity = _check_connectivity(connectivity, what)
-    if isinstance(temporal, bool) or not isinstance(temporal, (int, np.integer)) or int(temporal) not in (1, 9):
-        raise hip.VadError(f"{what}: temporal must be 1 or 9, got {temporal!r}")
-    temporal = int(temporal)
-    if temporal == 9 and connectivity != 8:
-        raise hip.VadError(f"{what}: temporal=9 (the 3 x 3 of the frame before) needs connectivity=8, got connectivity={connectivity}")
-    if not isinstance(maps, torch.Tensor):
-        raise hip.VadError(f"{what}: maps must be a torch tensor")
-    if not maps.is_cuda:
-        raise hip.VadError(f"{what}: maps ({maps.device}) must be on the GPU (events are detected on the device; there is no CPU fallback)")
-    if maps.dtype != torch.float32:
-        raise hip.VadError(f"{what}: maps must be float32, got {maps.dtype}")
-    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)) or np.isnan(threshold):
-        raise hip.VadError(f"{what}: threshold must be a number that is not NaN, got {threshold!r}")
-    for name, v, hi in (("min_duration", min_duration, 2 ** 32 - 1), ("min_volume", min_volume, 2 ** 32 - 1), ("max_events", max_events, MAX_EVENTS)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= hi:
-            raise hip.VadError(f"{what}: {name} must be an int in 1..{hi}, got {v!r}")
-    min_duration, min_volume, max_events = int(min_duration), int(min_volume), int(max_events)
+    connectivity, temporal = _check_structure(connectivity, temporal, what)
+    _check_maps(maps, what, "events are detected on the device")
+    thr = _check_threshold(threshold, what)
+    min_duration = _check_int(min_duration, "min_duration", what, 1, 2 ** 32 - 1)
+    min_volume = _check_int(min_volume, "min_volume", what, 1, 2 ** 32 - 1)
+    max_events = _check_int(max_events, "max_events", what, 1, MAX_EVENTS)
     if maps.dim() == 3:
         lead = ()
     elif maps.dim() == 4 or (maps.dim() == 5 and maps.shape[2] == 1):
@@ -1391,7 +1421,6 @@ def detect_events(maps: torch.Tensor, threshold: float, connectivity: int = 8, t
         raise hip.VadError(f"{what}: clips of {t} x {h} x {w} are out of range (T, H, W >= 1)")
     clips = maps.reshape(-1, t, h, w).contiguous()
     b = int(clips.shape[0])
-    thr = float(np.float32(threshold))
     dev = clips.device
 
     def result(records, counts, frame_counts, labels):
@@ -1405,10 +1434,8 @@ def detect_events(maps: torch.Tensor, threshold: float, connectivity: int = 8, t
                       torch.zeros((0, t, h, w), dtype=torch.int32, device=dev) if return_labels else None)
     with torch.cuda.device(dev):
         l = hip.lib()
-        size = l.vad_events_workspace_bytes(b, t, h, w, 1 if return_labels else 0)
-        if size == 0:
-            raise hip.VadError(f"{what}: {b} clips of {t} x {h} x {w} are out of range (t * h * w < 2^31 - 1, b * t * h * w <= 2^38)")
-        ws = torch.empty(size, dtype=torch.uint8, device=dev)
+        ws = _workspace(l.vad_events_workspace_bytes(b, t, h, w, 1 if return_labels else 0), dev, what,
+                        f"{b} clips of {t} x {h} x {w} are out of range (t * h * w < 2^31 - 1, b * t * h * w <= 2^38)")
         records = torch.empty((b, max_events, EVENT_WORDS), dtype=torch.int32, device=dev)
         counts = torch.empty((b, 4), dtype=torch.int32, device=dev)
         frame_counts = torch.empty((b, t, 3), dtype=torch.int32, device=dev)
@@ -1416,8 +1443,7 @@ def detect_events(maps: torch.Tensor, threshold: float, connectivity: int = 8, t
         hip.check(l.vad_detect_events(clips.data_ptr(), b, t, h, w, thr, connectivity, temporal, min_duration, min_volume, max_events,
                                       hip.ptr(labels), records.data_ptr(), counts.data_ptr(), frame_counts.data_ptr(), ws.data_ptr(),
                                       ws.numel(), hip.current_stream()), "vad_detect_events")
-    hip.calls["detect_events"] = hip.calls.get("detect_events", 0) + 1
-    _raise_on_flags(int(ws[:4].view(torch.int32).item()), what)
+    _launched(ws, what)
     return result(records, counts, frame_counts, labels)
 
 
@@ -1531,22 +1557,14 @@ class EventTracker:
     def __init__(self, streams: int, h: int, w: int, threshold: float, connectivity: int = 8, temporal: int = 9, min_duration: int = 1,
                  min_volume: int = 1, max_open: int = 1024, max_closed: int = 64, device=None):
         what = "EventTracker"
-        self.connectivity = _check_connectivity(connectivity, what)
-        if isinstance(temporal, bool) or not isinstance(temporal, (int, np.integer)) or int(temporal) not in (1, 9):
-            raise hip.VadError(f"{what}: temporal must be 1 or 9, got {temporal!r}")
-        self.temporal = int(temporal)
-        if self.temporal == 9 and self.connectivity != 8:
-            raise hip.VadError(f"{what}: temporal=9 (the 3 x 3 of the frame before) needs connectivity=8, got connectivity={connectivity}")
-        if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)) or np.isnan(threshold):
-            raise hip.VadError(f"{what}: threshold must be a number that is not NaN, got {threshold!r}")
-        for name, v, lo, hi in (("streams", streams, 0, 2 ** 20), ("h", h, 1, 2 ** 24), ("w", w, 1, 2 ** 24), ("min_duration", min_duration, 1, 2 ** 32 - 1),
-                                ("min_volume", min_volume, 1, 2 ** 32 - 1), ("max_open", max_open, 1, TRACK_MAX_OPEN),
-                                ("max_closed", max_closed, 1, TRACK_MAX_OPEN)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
-                raise hip.VadError(f"{what}: {name} must be an int in {lo}..{hi}, got {v!r}")
-        self.streams, self.h, self.w = int(streams), int(h), int(w)
-        self.min_duration, self.min_volume, self.max_open, self.max_closed = int(min_duration), int(min_volume), int(max_open), int(max_closed)
-        self.threshold = float(np.float32(threshold))
+        self.connectivity, self.temporal = _check_structure(connectivity, temporal, what)
+        self.threshold = _check_threshold(threshold, what)
+        self.streams = _check_int(streams, "streams", what, 0, 2 ** 20)
+        self.h, self.w = _check_int(h, "h", what, 1, 2 ** 24), _check_int(w, "w", what, 1, 2 ** 24)
+        self.min_duration = _check_int(min_duration, "min_duration", what, 1, 2 ** 32 - 1)
+        self.min_volume = _check_int(min_volume, "min_volume", what, 1, 2 ** 32 - 1)
+        self.max_open = _check_int(max_open, "max_open", what, 1, TRACK_MAX_OPEN)
+        self.max_closed = _check_int(max_closed, "max_closed", what, 1, TRACK_MAX_OPEN)
         if self.h * self.w > 2 ** 24:
             raise hip.VadError(f"{what}: frames of {h} x {w} are out of range (h * w <= 2^24)")
         dev = torch.device("cuda" if device is None else device)
@@ -1610,17 +1628,16 @@ class EventTracker:
 
     def _workspace(self, t: int) -> torch.Tensor:
         size = hip.lib().vad_track_workspace_bytes(self.streams, t, self.h, self.w, self.max_open)
-        if size == 0:
-            raise hip.VadError(f"EventTracker: {self.streams} streams of {t} x {self.h} x {self.w} are out of range (b * t * h * w <= 2^38)")
-        if self._ws is None or self._ws.numel() < size:
-            self._ws = torch.empty(size, dtype=torch.uint8, device=self.device)
+        if size == 0 or self._ws is None or self._ws.numel() < size:      # kept and grown as needed
+            self._ws = _workspace(size, self.device, "EventTracker",
+                                  f"{self.streams} streams of {t} x {self.h} x {self.w} are out of range (b * t * h * w <= 2^38)")
         return self._ws
 
     def _done(self, ws, what):
-        hip.calls["track_events"] = hip.calls.get("track_events", 0) + 1
-        if torch.cuda.is_current_stream_capturing():
+        _count("track_events")
+        if torch.cuda.is_current_stream_capturing():                      # no host read inside a capture: see `flags()`
             return
-        flags = int(ws[:4].view(torch.int32).item())
+        flags = _flag_word(ws)
         if flags & ~3:
             raise hip.VadError(f"{what}: flags {flags:#x} are set - a stream's frame counter stands at 2^32 - 1; reset the tracker")
         _raise_on_flags(flags, what)
@@ -1628,12 +1645,7 @@ class EventTracker:
     def update(self, maps: torch.Tensor) -> TrackUpdate:
         """maps: float32 GPU tensor `[B,H,W]` (one new map per stream), `[B,T,H,W]` or `[B,T,1,H,W]`."""
         what = "EventTracker.update"
-        if not isinstance(maps, torch.Tensor):
-            raise hip.VadError(f"{what}: maps must be a torch tensor")
-        if not maps.is_cuda:
-            raise hip.VadError(f"{what}: maps ({maps.device}) must be on the GPU (events are tracked on the device; there is no CPU fallback)")
-        if maps.dtype != torch.float32:
-            raise hip.VadError(f"{what}: maps must be float32, got {maps.dtype}")
+        _check_maps(maps, what, "events are tracked on the device")
         if maps.dim() == 3:
             maps = maps[:, None]
         elif maps.dim() == 5 and maps.shape[2] == 1:
@@ -1717,8 +1729,7 @@ class MapStatistics:
     compare it with their own arguments).  GPU only: there is no CPU fallback."""
 
     def __init__(self, frame_shape, device="cuda"):
-        if not isinstance(frame_shape, (tuple, list)) or len(frame_shape) != 2 or any(
-                isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in frame_shape):
+        if not isinstance(frame_shape, (tuple, list)) or len(frame_shape) != 2 or not all(_is_int(v) for v in frame_shape):
             raise hip.VadError(f"MapStatistics: frame_shape must be (H, W), got {frame_shape!r}")
         h, w = int(frame_shape[0]), int(frame_shape[1])
         if h < 1 or w < 1 or h * w > hip.MAX_FRAME_PIXELS:
@@ -1777,15 +1788,9 @@ class MapStatistics:
 
     # ------------------------------------------------------------------ accumulate / combine
     def _frames(self, maps: torch.Tensor, what: str) -> int:
-        """Checks a map batch [..., H, W]; -> the number of frames."""
-        if not isinstance(maps, torch.Tensor):
-            raise hip.VadError(f"{what}: maps must be a torch tensor")
-        if not maps.is_cuda:
-            raise hip.VadError(f"{what}: maps ({maps.device}) must be on the GPU (there is no CPU fallback)")
-        if maps.device != self.device:
-            raise hip.VadError(f"{what}: maps ({maps.device}) must be on the statistics' device {self.device}")
-        if maps.dtype != torch.float32:
-            raise hip.VadError(f"{what}: maps must be float32, got {maps.dtype}")
+        """Checks a map batch [..., H, W]; -> the number of frames.  Between the two common parts, `ValueError` for another frame
+        shape: statistics of other maps, as in `merge`."""
+        _check_maps(maps, what, "", self.device)
         if maps.dim() < 2 or tuple(maps.shape[-2:]) != self.frame_shape:
             raise ValueError(f"{what}: maps {tuple(maps.shape)} do not end in the frame shape {self.frame_shape} of the statistics")
         if not maps.is_contiguous():
@@ -1803,7 +1808,7 @@ class MapStatistics:
         with torch.cuda.device(self.device):
             hip.check(hip.lib().vad_mapstat_accumulate(maps.data_ptr(), n, h, w, self._state.data_ptr(), hip.current_stream()),
                       "vad_mapstat_accumulate")
-        hip.calls["mapstat_accumulate"] = hip.calls.get("mapstat_accumulate", 0) + 1
+        _count("mapstat_accumulate")
         self.count += n
         self._final = {}
         return self
@@ -1843,11 +1848,10 @@ class MapStatistics:
         return self._final[ddof]
 
     def _check_ddof(self, ddof, what: str) -> int:
-        if isinstance(ddof, bool) or not isinstance(ddof, (int, np.integer)) or int(ddof) not in (0, 1):
-            raise hip.VadError(f"{what}: ddof must be 0 or 1, got {ddof!r}")
-        if self.count - int(ddof) <= 0:
-            raise ValueError(f"{what}: {self.count} frames are not enough for a standard deviation with ddof={int(ddof)}")
-        return int(ddof)
+        ddof = _check_choice(ddof, "ddof", what, 0, 1)
+        if self.count - ddof <= 0:
+            raise ValueError(f"{what}: {self.count} frames are not enough for a standard deviation with ddof={ddof}")
+        return ddof
 
     def mean(self) -> torch.Tensor:
         """float32 [H, W]: fl32(K + S1 / n); NaN everywhere before the first frame.  Do not write to it (it is kept)."""
@@ -1889,7 +1893,7 @@ class MapStatistics:
                 ws = torch.empty(need, dtype=torch.uint8, device=self.device) if need else None
                 hip.check(l.vad_map_normalize(maps.data_ptr(), n, h, w, mean.data_ptr(), std.data_ptr(), min_std, hip.ptr(out), hip.ptr(fmax),
                                               hip.ptr(ws), need, hip.current_stream()), "vad_map_normalize")
-                hip.calls["map_normalize"] = hip.calls.get("map_normalize", 0) + 1
+                _count("map_normalize")
         if only:
             return fmax
         return (out, fmax) if return_max else out

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import hip
+from . import metrics
 
 
 def roc_auc(labels, scores) -> float:
@@ -70,11 +71,8 @@ def compute_auroc_smoothed(model, test_loader: Iterable[dict], device, sigma: fl
     moves the mean.  Same batches, same 4-tuple; `map` as in `pixel_auroc`.  The maps stay on the device: a batch's scores are read
     back once, as `compute_auroc` does.  `calibration`, `min_std` as in `pixel_auroc`: the score is the maximum of the z-score of the
     smoothed map (the smoothed map is normalised, its maximum taken by the same call)."""
-    from . import metrics
-    if map not in ("mse", "ssim"):
-        raise hip.VadError(f"compute_auroc_smoothed: map must be 'mse' or 'ssim', got {map!r}")
-    if calibration is not None:
-        min_std = _check_calibration(calibration, "compute_auroc_smoothed", map, sigma, truncate, min_std)
+    _check_map_name(map, "compute_auroc_smoothed")
+    min_std = _check_calibration(calibration, "compute_auroc_smoothed", map, sigma, truncate, min_std)
     all_labels, all_scores, all_types = [], [], []
     with torch.no_grad():
         for batch in test_loader:
@@ -383,7 +381,6 @@ def _anomaly_maps(model, images, map: str, sigma, truncate, calibration=None, mi
     """The batch's anomaly map [B,1,H,W] of the pixel metrics: the error map or the SSIM map, through `metrics.smooth_maps` when a
     sigma is given, then - with a `calibration` - turned into its z-score in place (the map is this call's own), then through the
     steps of `morph` (`metrics.morph_steps`), in z-score units when calibrated."""
-    from . import metrics
     if map == "mse":
         values = model.score_all(images)["errmap"]
     else:
@@ -397,6 +394,23 @@ def _anomaly_maps(model, images, map: str, sigma, truncate, calibration=None, mi
     return values
 
 
+def _check_map_name(map, what: str) -> None:
+    if map not in ("mse", "ssim"):
+        raise hip.VadError(f"{what}: map must be 'mse' or 'ssim', got {map!r}")
+
+
+def _refuse_clips_on(map, what: str, verb: str) -> None:
+    """The video model has an error map only; `verb`: what `what` does with clips."""
+    raise hip.VadError(f"{what}: clips [B,T,C,H,W] are {verb} on the error map only (map='mse'), got {map!r}")
+
+
+def _masked_maps(model, batch: dict, device, map: str, sigma, truncate, calibration, min_std, morph, key: str = "image"):
+    """One batch of the mask metrics: (`_anomaly_maps` of batch[key], batch['mask']), both on the device."""
+    images = batch[key].to(device)
+    masks = torch.as_tensor(batch["mask"]).to(device)
+    return _anomaly_maps(model, images, map, sigma, truncate, calibration, min_std, morph), masks
+
+
 def _map_meta(map: str, sigma, truncate) -> dict:
     """What kind of map a calibration holds the statistics of: `MapStatistics.meta`."""
     return {"map": map, "sigma": None if sigma is None else float(sigma), "truncate": float(truncate)}
@@ -404,8 +418,9 @@ def _map_meta(map: str, sigma, truncate) -> dict:
 
 def _check_calibration(calibration, what: str, map: str, sigma, truncate, min_std) -> float:
     """A calibration applies to the maps it was gathered on: `ValueError` for another map, sigma or truncate - thresholds on such
-    z-scores would be meaningless.  -> the min_std to use."""
-    from . import metrics
+    z-scores would be meaningless.  -> the min_std to use (without a calibration: as given, it is not used)."""
+    if calibration is None:
+        return min_std
     if not isinstance(calibration, metrics.MapStatistics):
         raise hip.VadError(f"{what}: calibration must be a metrics.MapStatistics, got {type(calibration).__name__}")
     want = _map_meta(map, sigma, truncate)
@@ -422,9 +437,7 @@ def calibrate(model, loader: Iterable[dict], device, map: str = "mse", sigma=Non
     `MapStatistics.update`; no map is copied to the host.  Returns the `metrics.MapStatistics` with `meta` = {map, sigma, truncate};
     pass `stats` to continue one (its meta must be that of this call).  Hand the result to `pixel_auroc` / `pixel_aupro` /
     `compute_auroc_smoothed` / `localize` as `calibration=`."""
-    from . import metrics
-    if map not in ("mse", "ssim"):
-        raise hip.VadError(f"calibrate: map must be 'mse' or 'ssim', got {map!r}")
+    _check_map_name(map, "calibrate")
     meta = _map_meta(map, sigma, truncate)
     if stats is not None:
         if not isinstance(stats, metrics.MapStatistics):
@@ -435,7 +448,7 @@ def calibrate(model, loader: Iterable[dict], device, map: str = "mse", sigma=Non
         for batch in loader:
             video = "frames" in batch
             if video and map != "mse":
-                raise hip.VadError(f"calibrate: clips [B,T,C,H,W] are calibrated on the error map only (map='mse'), got {map!r}")
+                _refuse_clips_on(map, "calibrate", "calibrated")
             values = _anomaly_maps(model, batch["frames" if video else "image"].to(device), map, sigma, truncate)
             if stats is None:
                 stats = metrics.MapStatistics(tuple(int(v) for v in values.shape[-2:]), values.device)
@@ -470,19 +483,14 @@ def pixel_auroc(model, loader: Iterable[dict], device, map: str = "mse", mantiss
     at most four, e.g. `[("open", 2), ("close", 5)]` - applied with `metrics.morph_maps` after the smoothing and the calibration (in
     z-score units when calibrated) and before the histogram.  `calibrate` takes none: statistics are those of the un-morphed map.
     Grey morphology commutes with a threshold, so a threshold read from this histogram is the one `localize(morph=...)` takes."""
-    from . import metrics
-    if map not in ("mse", "ssim"):
-        raise hip.VadError(f"pixel_auroc: map must be 'mse' or 'ssim', got {map!r}")
+    _check_map_name(map, "pixel_auroc")
     morph = metrics.morph_steps(morph)
-    if calibration is not None:
-        min_std = _check_calibration(calibration, "pixel_auroc", map, sigma, truncate, min_std)
+    min_std = _check_calibration(calibration, "pixel_auroc", map, sigma, truncate, min_std)
     if hist is None:
         hist = metrics.ScoreHistogram(mantissa_bits, device)
     with torch.no_grad():
         for batch in loader:
-            images = batch["image"].to(device)
-            masks = torch.as_tensor(batch["mask"]).to(device)
-            hist.accumulate(_anomaly_maps(model, images, map, sigma, truncate, calibration, min_std, morph), masks)
+            hist.accumulate(*_masked_maps(model, batch, device, map, sigma, truncate, calibration, min_std, morph))
     auroc, tie_bound = hist.auroc()
     return auroc, tie_bound, hist
 
@@ -498,19 +506,14 @@ def pixel_aupro(model, loader: Iterable[dict], device, map: str = "mse", fpr_lim
     (`metrics.aupro_from_counts`); pass `hist` to continue an earlier evaluation or to all-reduce before reading, in which case
     its own mantissa_bits and connectivity apply.  `hist.auroc()` is the pixel AUROC of the same evaluation.  `calibration`,
     `min_std`, `morph` as in `pixel_auroc`."""
-    from . import metrics
-    if map not in ("mse", "ssim"):
-        raise hip.VadError(f"pixel_aupro: map must be 'mse' or 'ssim', got {map!r}")
+    _check_map_name(map, "pixel_aupro")
     morph = metrics.morph_steps(morph)
-    if calibration is not None:
-        min_std = _check_calibration(calibration, "pixel_aupro", map, sigma, truncate, min_std)
+    min_std = _check_calibration(calibration, "pixel_aupro", map, sigma, truncate, min_std)
     if hist is None:
         hist = metrics.ProHistogram(mantissa_bits, device, connectivity)
     with torch.no_grad():
         for batch in loader:
-            images = batch["image"].to(device)
-            masks = torch.as_tensor(batch["mask"]).to(device)
-            hist.accumulate(_anomaly_maps(model, images, map, sigma, truncate, calibration, min_std, morph), masks)
+            hist.accumulate(*_masked_maps(model, batch, device, map, sigma, truncate, calibration, min_std, morph))
     aupro, quant_bound, weight_bound = hist.aupro(fpr_limit)
     return aupro, quant_bound, weight_bound, hist
 
@@ -529,13 +532,10 @@ def detection_report(model, loader: Iterable[dict], device, threshold: float, ma
     `gt_fraction`, `pred_fraction` as in `metrics.match_regions`.  Returns (report dict of `metrics.report_from_counts`, the
     `metrics.DetectionCounts`); pass `counts` to continue an earlier evaluation or to all-reduce before reading
     (`counts.all_reduce()`, then `counts.report()`) - counters gathered at another operating point are refused with `ValueError`."""
-    from . import metrics
     what = "detection_report"
-    if map not in ("mse", "ssim"):
-        raise hip.VadError(f"{what}: map must be 'mse' or 'ssim', got {map!r}")
+    _check_map_name(map, what)
     morph = metrics.morph_steps(None if morph == () else morph)          # () = no morphology, like None elsewhere
-    if calibration is not None:
-        min_std = _check_calibration(calibration, what, map, sigma, truncate, min_std)
+    min_std = _check_calibration(calibration, what, map, sigma, truncate, min_std)
     params = metrics._match_params(what, threshold, connectivity, min_area, gt_fraction, pred_fraction)
     meta = dict(_map_meta(map, sigma, truncate), morph=tuple(morph), calibrated=calibration is not None,
                 min_std=None if calibration is None else float(min_std))
@@ -548,10 +548,8 @@ def detection_report(model, loader: Iterable[dict], device, threshold: float, ma
         for batch in loader:
             video = "frames" in batch
             if video and map != "mse":
-                raise hip.VadError(f"{what}: clips [B,T,C,H,W] are reported on the error map only (map='mse'), got {map!r}")
-            images = batch["frames" if video else "image"].to(device)
-            masks = torch.as_tensor(batch["mask"]).to(device)
-            maps = _anomaly_maps(model, images, map, sigma, truncate, calibration, min_std, morph)
+                _refuse_clips_on(map, what, "reported")
+            maps, masks = _masked_maps(model, batch, device, map, sigma, truncate, calibration, min_std, morph, "frames" if video else "image")
             counts.update(metrics.match_regions(maps, masks, threshold, connectivity, min_area, gt_fraction, pred_fraction, max_regions=1), meta)
     return counts.report(), counts
 
@@ -561,7 +559,6 @@ def frame_auroc(model, loader: Iterable[dict], device, hist=None, mantissa_bits:
     `score_clips(per_frame=True)` - batches {'frames' [B,T,C,H,W], 'frame_labels' [B,T], ...} -, each batch's frame scores and
     labels going into a histogram on the device.  Returns (auroc, tie_bound, hist); ranks of a sharded evaluation call
     `hist.all_reduce()` on a histogram they pass in instead of gathering score vectors."""
-    from . import metrics
     if hist is None:
         hist = metrics.ScoreHistogram(mantissa_bits, device)
     with torch.no_grad():
@@ -587,14 +584,11 @@ def localize(model, images, threshold: float, map: str = "mse", sigma=None, trun
     `morph` as in `pixel_auroc` (one `metrics.morph_maps` launch per step, last in the chain): the regions are those of the morphed
     maps - `("open", 2)` drops single-pixel speckle before it is labelled, where `min_area` drops it after and cannot cut a
     one-pixel bridge between two defects - and the maps returned are the morphed maps."""
-    from . import metrics
-    if map not in ("mse", "ssim"):
-        raise hip.VadError(f"localize: map must be 'mse' or 'ssim', got {map!r}")
+    _check_map_name(map, "localize")
     morph = metrics.morph_steps(morph)
     if images.dim() == 5 and map != "mse":
-        raise hip.VadError(f"localize: clips [B,T,C,H,W] are localised on the error map only (map='mse'), got {map!r}")
-    if calibration is not None:
-        min_std = _check_calibration(calibration, "localize", map, sigma, truncate, min_std)
+        _refuse_clips_on(map, "localize", "localised")
+    min_std = _check_calibration(calibration, "localize", map, sigma, truncate, min_std)
     with torch.no_grad():
         maps = _anomaly_maps(model, images, map, sigma, truncate, calibration, min_std, morph)
         return metrics.detect_regions(maps, threshold, connectivity, min_area, max_regions), maps
@@ -610,14 +604,11 @@ def localize_events(model, images, threshold: float, map: str = "mse", sigma=Non
     `calibration`, `min_std`, `morph` as in `localize`.  Per batch ONE scoring call, the optional smoothing and calibration calls and ONE
     `detect_events` call; nothing but the flag word is read by the host.  Returns (`metrics.Events`, maps): the table with the
     leading shape `[B]` (video) or `()` (image), and the maps it was made from, `[B,T,1,H,W]` / `[N,1,H,W]`, still on the device."""
-    from . import metrics
-    if map not in ("mse", "ssim"):
-        raise hip.VadError(f"localize_events: map must be 'mse' or 'ssim', got {map!r}")
+    _check_map_name(map, "localize_events")
     morph = metrics.morph_steps(morph)
     if images.dim() == 5 and map != "mse":
-        raise hip.VadError(f"localize_events: clips [B,T,C,H,W] are localised on the error map only (map='mse'), got {map!r}")
-    if calibration is not None:
-        min_std = _check_calibration(calibration, "localize_events", map, sigma, truncate, min_std)
+        _refuse_clips_on(map, "localize_events", "localised")
+    min_std = _check_calibration(calibration, "localize_events", map, sigma, truncate, min_std)
     with torch.no_grad():
         maps = _anomaly_maps(model, images, map, sigma, truncate, calibration, min_std, morph)
         volumes = maps if maps.dim() == 5 else maps[:, 0]                 # [B,T,1,H,W], or the image batch as one clip [N,H,W]
@@ -635,12 +626,10 @@ def localize_stream(model, frames, tracker, state=None, sigma=None, truncate: fl
     they were made from (`[B,T,1,H,W]` / `[B,1,H,W]`, on the device), and the scoring state for the next call.  The tracker's
     threshold applies to the maps as made here: with a `calibration` it is a z-score.  `morph` as in `localize`: every frame is
     morphed on its own, so the result does not depend on how the frames are split over calls."""
-    from . import metrics
     morph = metrics.morph_steps(morph)
     if not isinstance(tracker, metrics.EventTracker):
         raise hip.VadError(f"localize_stream: tracker must be a metrics.EventTracker, got {type(tracker).__name__}")
-    if calibration is not None:
-        min_std = _check_calibration(calibration, "localize_stream", "mse", sigma, truncate, min_std)
+    min_std = _check_calibration(calibration, "localize_stream", "mse", sigma, truncate, min_std)
     video = hasattr(model, "score_stateful")
     if not video and state is not None:
         raise hip.VadError("localize_stream: the image model carries no state between calls; pass state=None")
