@@ -31,6 +31,7 @@
 #include <hip/hip_runtime.h>
 
 #include "region_table.h"
+#include "vad_args.h"
 #include "vad_common.h"
 
 namespace {
@@ -373,7 +374,7 @@ __global__ __launch_bounds__(EV_THREADS) void events_finish_kernel(EventP p) {
 
 // b >= 0, t, h, w >= 1, t * h * w < 2^31 - 1, b * t * h * w <= 2^38; *vol = t * h * w, *total = b * vol
 bool events_dims_ok(long long b, int t, int h, int w, long long* vol, long long* total) {
-    if (b < 0 || t < 1 || h < 1 || w < 1 || (long long)h * w >= 2147483647ll) return false;
+    if (b < 0 || t < 1 || !vad_label_hw_ok(h, w)) return false;
     if (__builtin_mul_overflow((long long)t, (long long)h * w, vol) || *vol >= 2147483647ll) return false;
     return !__builtin_mul_overflow(b, *vol, total) && *total <= (1ll << 38);
 }
@@ -401,37 +402,29 @@ int vad_events_plan(int* label_round, int* volume_round, int* scan_round, int* r
 int vad_detect_events(const float* maps, long long b, int t, int h, int w, float threshold, int connectivity, int temporal,
                       unsigned min_duration, unsigned min_volume, int max_events, int32_t* labels_or_null, uint32_t* records,
                       uint32_t* counts, uint32_t* frame_counts, void* ws, size_t ws_bytes, void* stream) {
-    VAD_REQUIRE(maps != nullptr, "detect_events: maps is NULL");
-    VAD_REQUIRE((uintptr_t)maps % 4 == 0, "detect_events: maps must be 4-byte aligned");
-    VAD_REQUIRE(b >= 0, "detect_events: b must be >= 0, got %lld", b);
-    VAD_REQUIRE(t >= 1, "detect_events: t must be >= 1, got %d", t);
-    VAD_REQUIRE(h >= 1 && w >= 1 && (long long)h * w < 2147483647ll, "detect_events: h and w must be >= 1 with h * w < 2^31 - 1, got %d x %d",
-                h, w);
+    const char* who = "detect_events";
+    VAD_ARG(vad_req_ptr(who, "maps", maps, 4));
+    VAD_ARG(vad_req_label_n(who, "b", b));
+    VAD_ARG(vad_req_t(who, t));
+    VAD_ARG(vad_req_label_hw(who, h, w));
     long long vol = 0, total = 0;
     VAD_REQUIRE(!__builtin_mul_overflow((long long)t, (long long)h * w, &vol) && vol < 2147483647ll,
                 "detect_events: t * h * w must be below 2^31 - 1 (%d x %d x %d)", t, h, w);
     VAD_REQUIRE(events_dims_ok(b, t, h, w, &vol, &total), "detect_events: b * t * h * w must be at most 2^38 (%lld x %d x %d x %d)", b, t, h, w);
-    VAD_REQUIRE(threshold == threshold, "detect_events: threshold is NaN");
-    VAD_REQUIRE(connectivity == 4 || connectivity == 8, "detect_events: connectivity must be 4 or 8, got %d", connectivity);
+    VAD_ARG(vad_req_threshold(who, threshold));
+    VAD_ARG(vad_req_connectivity(who, connectivity));
     VAD_REQUIRE(temporal == 1 || temporal == 9, "detect_events: temporal must be 1 or 9, got %d", temporal);
     VAD_REQUIRE(temporal == 1 || connectivity == 8, "detect_events: temporal 9 needs connectivity 8, got connectivity %d", connectivity);
-    VAD_REQUIRE(min_duration >= 1u, "detect_events: min_duration must be >= 1, got 0");
-    VAD_REQUIRE(min_volume >= 1u, "detect_events: min_volume must be >= 1, got 0");
-    VAD_REQUIRE(max_events >= 1 && max_events <= EV_MAX_EVENTS, "detect_events: max_events must be in 1..%d, got %d", EV_MAX_EVENTS, max_events);
-    VAD_REQUIRE((uintptr_t)labels_or_null % 4 == 0, "detect_events: labels must be 4-byte aligned");
-    VAD_REQUIRE(records != nullptr, "detect_events: records is NULL");
-    VAD_REQUIRE((uintptr_t)records % 16 == 0, "detect_events: records must be 16-byte aligned");
-    VAD_REQUIRE(counts != nullptr, "detect_events: counts is NULL");
-    VAD_REQUIRE((uintptr_t)counts % 4 == 0, "detect_events: counts must be 4-byte aligned");
-    VAD_REQUIRE(frame_counts != nullptr, "detect_events: frame_counts is NULL");
-    VAD_REQUIRE((uintptr_t)frame_counts % 4 == 0, "detect_events: frame_counts must be 4-byte aligned");
-    VAD_REQUIRE(ws != nullptr, "detect_events: ws is NULL");
-    VAD_REQUIRE((uintptr_t)ws % 16 == 0, "detect_events: ws must be 16-byte aligned");
+    VAD_ARG(vad_req_nonzero(who, "min_duration", min_duration));
+    VAD_ARG(vad_req_nonzero(who, "min_volume", min_volume));
+    VAD_ARG(vad_req_capacity(who, "max_events", max_events, EV_MAX_EVENTS));
+    VAD_ARG(vad_req_aligned(who, "labels", labels_or_null, 4));
+    VAD_ARG(vad_req_ptr(who, "records", records, 16));
+    VAD_ARG(vad_req_ptr(who, "counts", counts, 4));
+    VAD_ARG(vad_req_ptr(who, "frame_counts", frame_counts, 4));
+    VAD_ARG(vad_req_ptr(who, "ws", ws, 16));
     const int given = labels_or_null != nullptr ? 1 : 0;
-    const size_t need = vad_events_workspace_bytes(b, t, h, w, given);
-    if (ws_bytes < need)
-        return vad_fail(VAD_ERR_WS, "detect_events: ws_bytes %zu is less than vad_events_workspace_bytes(%lld, %d, %d, %d, %d) = %zu", ws_bytes,
-                        b, t, h, w, given, need);
+    VAD_REQUIRE_WS(VAD_ERR_WS, who, ws_bytes, vad_events_workspace_bytes(b, t, h, w, given), "vad_events_workspace_bytes(%lld, %d, %d, %d, %d)", b, t, h, w, given);
     const hipStream_t s = (hipStream_t)stream;
     if (b == 0) {                                            // nothing to detect: the flag word still reads "no defect"
         VAD_HIP_TRY(hipMemsetAsync(ws, 0, VAD_LABEL_WS_HEAD_BYTES, s));

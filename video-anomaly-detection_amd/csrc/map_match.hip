@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include "region_table.h"
+#include "vad_args.h"
 #include "vad_common.h"
 
 namespace {
@@ -260,36 +261,25 @@ int vad_match_plan(int* label_round, int* join_round, int* scan_round, int* thre
 int vad_match_regions(const float* maps, const void* masks, int mask_format, long long n, int h, int w, float threshold,
                       int connectivity, unsigned min_area, double gt_fraction, double pred_fraction, int max_regions,
                       uint32_t* gt_records, uint32_t* pred_records, uint64_t* counts, void* ws, size_t ws_bytes, void* stream) {
-    VAD_REQUIRE(maps != nullptr, "match_regions: maps is NULL");
-    VAD_REQUIRE((uintptr_t)maps % 4 == 0, "match_regions: maps must be 4-byte aligned");
-    VAD_REQUIRE(masks != nullptr, "match_regions: masks is NULL");
-    VAD_REQUIRE(mask_format == VAD_LBL_U8_ELEM || mask_format == VAD_LBL_F32_ELEM,
-                "match_regions: mask_format must be VAD_LBL_U8_ELEM (%d) or VAD_LBL_F32_ELEM (%d), got %d", VAD_LBL_U8_ELEM, VAD_LBL_F32_ELEM,
-                mask_format);
-    VAD_REQUIRE(mask_format != VAD_LBL_F32_ELEM || (uintptr_t)masks % 4 == 0, "match_regions: float masks must be 4-byte aligned");
-    VAD_REQUIRE(n >= 0, "match_regions: n must be >= 0, got %lld", n);
-    VAD_REQUIRE(h >= 1 && w >= 1 && (long long)h * w < 2147483647ll, "match_regions: h and w must be >= 1 with h * w < 2^31 - 1, got %d x %d",
-                h, w);
+    const char* who = "match_regions";
     long long total = 0;
-    VAD_REQUIRE(vad_label_dims_ok(n, h, w, &total), "match_regions: n * h * w must be at most 2^38 (%lld x %d x %d)", n, h, w);
-    VAD_REQUIRE(threshold == threshold, "match_regions: threshold is NaN");
-    VAD_REQUIRE(connectivity == 4 || connectivity == 8, "match_regions: connectivity must be 4 or 8, got %d", connectivity);
-    VAD_REQUIRE(min_area >= 1u, "match_regions: min_area must be >= 1, got 0");
+    VAD_ARG(vad_req_ptr(who, "maps", maps, 4));
+    VAD_ARG(vad_req_masks(who, masks, "mask_format", mask_format));
+    VAD_ARG(vad_req_label_n(who, "n", n));
+    VAD_ARG(vad_req_label_hw(who, h, w));
+    VAD_ARG(vad_req_label_total(who, n, h, w, &total));
+    VAD_ARG(vad_req_threshold(who, threshold));
+    VAD_ARG(vad_req_connectivity(who, connectivity));
+    VAD_ARG(vad_req_nonzero(who, "min_area", min_area));
     VAD_REQUIRE(gt_fraction >= 0.0 && gt_fraction <= 1.0, "match_regions: gt_fraction must be in [0, 1], got %g", gt_fraction);
     VAD_REQUIRE(pred_fraction >= 0.0 && pred_fraction <= 1.0, "match_regions: pred_fraction must be in [0, 1], got %g", pred_fraction);
-    VAD_REQUIRE(max_regions >= 1 && max_regions <= MT_MAX_REGIONS, "match_regions: max_regions must be in 1..%d, got %d", MT_MAX_REGIONS,
-                max_regions);
-    VAD_REQUIRE(gt_records != nullptr, "match_regions: gt_records is NULL");
-    VAD_REQUIRE(pred_records != nullptr, "match_regions: pred_records is NULL");
-    VAD_REQUIRE((uintptr_t)gt_records % 16 == 0 && (uintptr_t)pred_records % 16 == 0, "match_regions: records must be 16-byte aligned");
-    VAD_REQUIRE(counts != nullptr, "match_regions: counts is NULL");
-    VAD_REQUIRE((uintptr_t)counts % 8 == 0, "match_regions: counts must be 8-byte aligned");
-    VAD_REQUIRE(ws != nullptr, "match_regions: ws is NULL");
-    VAD_REQUIRE((uintptr_t)ws % 16 == 0, "match_regions: ws must be 16-byte aligned");
-    const size_t need = vad_match_workspace_bytes(n, h, w);
-    if (ws_bytes < need)
-        return vad_fail(VAD_ERR_WS, "match_regions: ws_bytes %zu is less than vad_match_workspace_bytes(%lld, %d, %d) = %zu", ws_bytes, n, h, w,
-                        need);
+    VAD_ARG(vad_req_capacity(who, "max_regions", max_regions, MT_MAX_REGIONS));
+    VAD_ARG(vad_req_nonnull(who, "gt_records", gt_records));
+    VAD_ARG(vad_req_nonnull(who, "pred_records", pred_records));
+    VAD_REQUIRE(vad_aligned(gt_records, 16) && vad_aligned(pred_records, 16), "match_regions: records must be 16-byte aligned");
+    VAD_ARG(vad_req_ptr(who, "counts", counts, 8));
+    VAD_ARG(vad_req_ptr(who, "ws", ws, 16));
+    VAD_REQUIRE_WS(VAD_ERR_WS, who, ws_bytes, vad_match_workspace_bytes(n, h, w), "vad_match_workspace_bytes(%lld, %d, %d)", n, h, w);
     const hipStream_t s = (hipStream_t)stream;
     if (n == 0) {                                            // nothing to match: the flag word still reads "no defect"
         VAD_HIP_TRY(hipMemsetAsync(ws, 0, VAD_LABEL_WS_HEAD_BYTES, s));

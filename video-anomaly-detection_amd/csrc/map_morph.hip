@@ -35,6 +35,7 @@
 
 #include <atomic>
 
+#include "vad_args.h"
 #include "vad_common.h"
 
 namespace {
@@ -256,15 +257,11 @@ extern "C" int vad_morph_maps(const float* maps, long long n, int h, int w, int 
     VAD_REQUIRE(op >= VAD_MORPH_ERODE && op <= VAD_MORPH_CLOSE, "morph_maps: unknown op %d (0 erode, 1 dilate, 2 open, 3 close)", op);
     VAD_REQUIRE(size_h >= 1 && size_h <= VAD_MORPH_MAX_SIZE && size_w >= 1 && size_w <= VAD_MORPH_MAX_SIZE,
                 "morph_maps: size must be in 1..%d per side, got %dx%d", VAD_MORPH_MAX_SIZE, size_h, size_w);
-    VAD_REQUIRE(n >= 0, "morph_maps: n=%lld is negative", n);
-    VAD_REQUIRE(h >= 1 && w >= 1, "morph_maps: h and w must be positive, got %dx%d", h, w);
-    VAD_REQUIRE_PIXELS("morph_maps", h, w);
-    VAD_REQUIRE(n <= (1ll << 60) / ((long long)h * w), "morph_maps: n * h * w is not representable (n=%lld)", n);
+    VAD_ARG(vad_req_map_dims("morph_maps", n, h, w));
     VAD_REQUIRE(maps != nullptr && out != nullptr, "morph_maps: maps or out is NULL");
-    VAD_REQUIRE((uintptr_t)maps % 4 == 0 && (uintptr_t)out % 4 == 0, "morph_maps: maps and out must be 4-byte aligned");
-    const size_t bytes = (size_t)n * h * w * sizeof(float);
-    const uintptr_t a = (uintptr_t)maps, b = (uintptr_t)out;
-    VAD_REQUIRE(a + bytes <= b || b + bytes <= a, "morph_maps: out overlaps maps (a pixel's window reads its neighbours: not in place)");
+    VAD_REQUIRE(vad_aligned(maps, 4) && vad_aligned(out, 4), "morph_maps: maps and out must be 4-byte aligned");
+    VAD_REQUIRE(vad_disjoint(maps, out, (size_t)n * h * w * sizeof(float)),
+                "morph_maps: out overlaps maps (a pixel's window reads its neighbours: not in place)");
     if (n == 0) return VAD_OK;
 
     MorphP p;

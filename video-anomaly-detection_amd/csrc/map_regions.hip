@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include "region_table.h"
+#include "vad_args.h"
 #include "vad_common.h"
 
 namespace {
@@ -185,30 +186,22 @@ size_t vad_regions_workspace_bytes(long long n, int h, int w, int labels_given) 
 int vad_detect_regions(const float* maps, long long n, int h, int w, float threshold, int connectivity, unsigned min_area,
                        int max_regions, int32_t* labels_or_null, uint32_t* records, uint32_t* counts, void* ws, size_t ws_bytes,
                        void* stream) {
-    VAD_REQUIRE(maps != nullptr, "detect_regions: maps is NULL");
-    VAD_REQUIRE((uintptr_t)maps % 4 == 0, "detect_regions: maps must be 4-byte aligned");
-    VAD_REQUIRE(n >= 0, "detect_regions: n must be >= 0, got %lld", n);
-    VAD_REQUIRE(h >= 1 && w >= 1 && (long long)h * w < 2147483647ll, "detect_regions: h and w must be >= 1 with h * w < 2^31 - 1, got %d x %d",
-                h, w);
+    const char* who = "detect_regions";
     long long total = 0;
-    VAD_REQUIRE(vad_label_dims_ok(n, h, w, &total), "detect_regions: n * h * w must be at most 2^38 (%lld x %d x %d)", n, h, w);
-    VAD_REQUIRE(threshold == threshold, "detect_regions: threshold is NaN");
-    VAD_REQUIRE(connectivity == 4 || connectivity == 8, "detect_regions: connectivity must be 4 or 8, got %d", connectivity);
-    VAD_REQUIRE(min_area >= 1u, "detect_regions: min_area must be >= 1, got 0");
-    VAD_REQUIRE(max_regions >= 1 && max_regions <= REG_MAX_REGIONS, "detect_regions: max_regions must be in 1..%d, got %d", REG_MAX_REGIONS,
-                max_regions);
-    VAD_REQUIRE((uintptr_t)labels_or_null % 4 == 0, "detect_regions: labels must be 4-byte aligned");
-    VAD_REQUIRE(records != nullptr, "detect_regions: records is NULL");
-    VAD_REQUIRE((uintptr_t)records % 16 == 0, "detect_regions: records must be 16-byte aligned");
-    VAD_REQUIRE(counts != nullptr, "detect_regions: counts is NULL");
-    VAD_REQUIRE((uintptr_t)counts % 4 == 0, "detect_regions: counts must be 4-byte aligned");
-    VAD_REQUIRE(ws != nullptr, "detect_regions: ws is NULL");
-    VAD_REQUIRE((uintptr_t)ws % 16 == 0, "detect_regions: ws must be 16-byte aligned");
+    VAD_ARG(vad_req_ptr(who, "maps", maps, 4));
+    VAD_ARG(vad_req_label_n(who, "n", n));
+    VAD_ARG(vad_req_label_hw(who, h, w));
+    VAD_ARG(vad_req_label_total(who, n, h, w, &total));
+    VAD_ARG(vad_req_threshold(who, threshold));
+    VAD_ARG(vad_req_connectivity(who, connectivity));
+    VAD_ARG(vad_req_nonzero(who, "min_area", min_area));
+    VAD_ARG(vad_req_capacity(who, "max_regions", max_regions, REG_MAX_REGIONS));
+    VAD_ARG(vad_req_aligned(who, "labels", labels_or_null, 4));
+    VAD_ARG(vad_req_ptr(who, "records", records, 16));
+    VAD_ARG(vad_req_ptr(who, "counts", counts, 4));
+    VAD_ARG(vad_req_ptr(who, "ws", ws, 16));
     const int given = labels_or_null != nullptr ? 1 : 0;
-    const size_t need = vad_regions_workspace_bytes(n, h, w, given);
-    if (ws_bytes < need)
-        return vad_fail(VAD_ERR_WS, "detect_regions: ws_bytes %zu is less than vad_regions_workspace_bytes(%lld, %d, %d, %d) = %zu", ws_bytes,
-                        n, h, w, given, need);
+    VAD_REQUIRE_WS(VAD_ERR_WS, who, ws_bytes, vad_regions_workspace_bytes(n, h, w, given), "vad_regions_workspace_bytes(%lld, %d, %d, %d)", n, h, w, given);
     const hipStream_t s = (hipStream_t)stream;
     if (n == 0) {                                            // nothing to detect: the flag word still reads "no defect"
         VAD_HIP_TRY(hipMemsetAsync(ws, 0, VAD_LABEL_WS_HEAD_BYTES, s));

@@ -29,6 +29,7 @@
 
 #include <atomic>
 
+#include "vad_args.h"
 #include "vad_common.h"
 
 #pragma clang fp contract(off)
@@ -195,8 +196,7 @@ __global__ __launch_bounds__(64) void smooth_max_kernel(const float* tile_max, i
 }
 
 inline bool smooth_dims_ok(long long n, int h, int w, int radius) {
-    return n >= 0 && h >= 1 && w >= 1 && vad_frame_pixels_ok(h, w) && radius >= 1 && radius <= VAD_SMOOTH_MAX_RADIUS && radius <= h &&
-           radius <= w && n <= (1ll << 60) / ((long long)h * w);
+    return vad_map_dims_ok(n, h, w) && radius >= 1 && radius <= VAD_SMOOTH_MAX_RADIUS && radius <= h && radius <= w;
 }
 
 inline long long smooth_tiles(int h, int w) { return (long long)((h + SM_TH - 1) / SM_TH) * ((w + SM_TW - 1) / SM_TW); }
@@ -216,22 +216,17 @@ extern "C" size_t vad_smooth_workspace_bytes(long long n, int h, int w, int radi
 
 extern "C" int vad_smooth_maps(const float* maps, long long n, int h, int w, const float* taps_dev, int radius, float* out, float* frame_max,
                                void* ws, size_t ws_bytes, void* stream) {
-    VAD_REQUIRE(n >= 0, "smooth_maps: n=%lld is negative", n);
-    VAD_REQUIRE(h >= 1 && w >= 1, "smooth_maps: h and w must be positive, got %dx%d", h, w);
-    VAD_REQUIRE_PIXELS("smooth_maps", h, w);
+    VAD_ARG(vad_req_map_n("smooth_maps", n));
+    VAD_ARG(vad_req_map_hw("smooth_maps", h, w));
     VAD_REQUIRE(radius >= 1 && radius <= VAD_SMOOTH_MAX_RADIUS, "smooth_maps: radius must be in 1..%d, got %d", VAD_SMOOTH_MAX_RADIUS, radius);
     VAD_REQUIRE(radius <= h && radius <= w, "smooth_maps: radius %d exceeds min(h, w) of a %dx%d map (one reflection only)", radius, h, w);
-    VAD_REQUIRE(n <= (1ll << 60) / ((long long)h * w), "smooth_maps: n * h * w is not representable (n=%lld)", n);
+    VAD_ARG(vad_req_map_total("smooth_maps", n, h, w));
     VAD_REQUIRE(out != nullptr || frame_max != nullptr, "smooth_maps: out and frame_max are both NULL");
     VAD_REQUIRE(maps != nullptr && taps_dev != nullptr, "smooth_maps: maps or taps is NULL");
-    VAD_REQUIRE((uintptr_t)maps % 4 == 0 && (uintptr_t)taps_dev % 4 == 0 && (uintptr_t)out % 4 == 0 && (uintptr_t)frame_max % 4 == 0 &&
-                    (uintptr_t)ws % 4 == 0,
+    VAD_REQUIRE(vad_aligned(maps, 4) && vad_aligned(taps_dev, 4) && vad_aligned(out, 4) && vad_aligned(frame_max, 4) && vad_aligned(ws, 4),
                 "smooth_maps: maps, taps, out, frame_max and ws must be 4-byte aligned");
-    const size_t bytes = (size_t)n * h * w * sizeof(float);
-    if (out != nullptr) {
-        const uintptr_t a = (uintptr_t)maps, b = (uintptr_t)out;
-        VAD_REQUIRE(a + bytes <= b || b + bytes <= a, "smooth_maps: out overlaps maps (a pixel's window reads its neighbours: not in place)");
-    }
+    VAD_REQUIRE(out == nullptr || vad_disjoint(maps, out, (size_t)n * h * w * sizeof(float)),
+                "smooth_maps: out overlaps maps (a pixel's window reads its neighbours: not in place)");
     const long long tiles = smooth_tiles(h, w);
     if (frame_max != nullptr) {
         const size_t need = vad_smooth_workspace_bytes(n, h, w, radius);

@@ -30,6 +30,7 @@
 
 #include <math.h>
 
+#include "vad_args.h"
 #include "vad_common.h"
 
 #pragma clang fp contract(off)
@@ -277,18 +278,10 @@ __global__ __launch_bounds__(64) void map_normalize_max_kernel(const float* chun
     if (threadIdx.x == 0) frame_max[f] = m;
 }
 
-inline bool ms_dims_ok(int h, int w) { return h >= 1 && w >= 1 && vad_frame_pixels_ok(h, w); }
 inline unsigned ms_blocks(int h, int w) { return (unsigned)(((long long)h * w + MS_THREADS - 1) / MS_THREADS); }
 inline long long nz_chunks(int h, int w) { return ((long long)h * w + NZ_CHUNK - 1) / NZ_CHUNK; }
 
 }  // namespace
-
-#define MS_REQUIRE_DIMS(who, h, w)                                                                      \
-    VAD_REQUIRE((h) >= 1 && (w) >= 1, who ": h and w must be positive, got %dx%d", h, w);               \
-    VAD_REQUIRE_PIXELS(who, h, w)
-#define MS_REQUIRE_STATE(who, name, ptr)                                                                \
-    VAD_REQUIRE((ptr) != nullptr, who ": " name " is NULL");                                            \
-    VAD_REQUIRE((uintptr_t)(ptr) % 16 == 0, who ": " name " must be 16-byte aligned")
 
 extern "C" int vad_mapstat_plan(int* pixels_per_thread, int* frames_in_flight, int* threads) {
     if (pixels_per_thread) *pixels_per_thread = MS_PIXELS_PER_THREAD;
@@ -298,25 +291,22 @@ extern "C" int vad_mapstat_plan(int* pixels_per_thread, int* frames_in_flight, i
 }
 
 extern "C" size_t vad_mapstat_state_bytes(int h, int w) {
-    if (!ms_dims_ok(h, w)) return 0;
+    if (!vad_map_hw_ok(h, w)) return 0;
     return MS_HEADER_BYTES + 3 * sizeof(double) * (size_t)h * w;
 }
 
 extern "C" int vad_mapstat_reset(void* state, int h, int w, void* stream) {
-    MS_REQUIRE_DIMS("mapstat_reset", h, w);
-    MS_REQUIRE_STATE("mapstat_reset", "state", state);
+    VAD_ARG(vad_req_map_hw("mapstat_reset", h, w));
+    VAD_ARG(vad_req_ptr("mapstat_reset", "state", state, 16));
     hipLaunchKernelGGL(mapstat_reset_kernel, dim3(ms_blocks(h, w)), dim3(MS_THREADS), 0, (hipStream_t)stream, state, h, w);
     VAD_LAUNCH_CHECK();
     return VAD_OK;
 }
 
 extern "C" int vad_mapstat_accumulate(const float* maps, long long n, int h, int w, void* state, void* stream) {
-    VAD_REQUIRE(n >= 0, "mapstat_accumulate: n=%lld is negative", n);
-    MS_REQUIRE_DIMS("mapstat_accumulate", h, w);
-    VAD_REQUIRE(n <= (1ll << 60) / ((long long)h * w), "mapstat_accumulate: n * h * w is not representable (n=%lld)", n);
-    VAD_REQUIRE(maps != nullptr, "mapstat_accumulate: maps is NULL");
-    VAD_REQUIRE((uintptr_t)maps % 4 == 0, "mapstat_accumulate: maps must be 4-byte aligned");
-    MS_REQUIRE_STATE("mapstat_accumulate", "state", state);
+    VAD_ARG(vad_req_map_dims("mapstat_accumulate", n, h, w));
+    VAD_ARG(vad_req_ptr("mapstat_accumulate", "maps", maps, 4));
+    VAD_ARG(vad_req_ptr("mapstat_accumulate", "state", state, 16));
     if (n == 0) return VAD_OK;
     const hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(mapstat_accumulate_kernel, dim3(ms_blocks(h, w)), dim3(MS_THREADS), 0, s, maps, n, h, w, state);
@@ -327,12 +317,10 @@ extern "C" int vad_mapstat_accumulate(const float* maps, long long n, int h, int
 }
 
 extern "C" int vad_mapstat_merge(void* state, const void* other, int h, int w, void* stream) {
-    MS_REQUIRE_DIMS("mapstat_merge", h, w);
-    MS_REQUIRE_STATE("mapstat_merge", "state", state);
-    MS_REQUIRE_STATE("mapstat_merge", "other", other);
-    const size_t bytes = vad_mapstat_state_bytes(h, w);
-    const uintptr_t a = (uintptr_t)state, b = (uintptr_t)other;
-    VAD_REQUIRE(a + bytes <= b || b + bytes <= a, "mapstat_merge: other overlaps state");
+    VAD_ARG(vad_req_map_hw("mapstat_merge", h, w));
+    VAD_ARG(vad_req_ptr("mapstat_merge", "state", state, 16));
+    VAD_ARG(vad_req_ptr("mapstat_merge", "other", other, 16));
+    VAD_REQUIRE(vad_disjoint(state, other, vad_mapstat_state_bytes(h, w)), "mapstat_merge: other overlaps state");
     const hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(mapstat_merge_kernel, dim3(ms_blocks(h, w)), dim3(MS_THREADS), 0, s, state, other, h, w);
     VAD_LAUNCH_CHECK();
@@ -342,37 +330,32 @@ extern "C" int vad_mapstat_merge(void* state, const void* other, int h, int w, v
 }
 
 extern "C" int vad_mapstat_finalize(const void* state, int h, int w, int ddof, float* mean, float* std_out, void* stream) {
-    MS_REQUIRE_DIMS("mapstat_finalize", h, w);
-    MS_REQUIRE_STATE("mapstat_finalize", "state", state);
+    VAD_ARG(vad_req_map_hw("mapstat_finalize", h, w));
+    VAD_ARG(vad_req_ptr("mapstat_finalize", "state", state, 16));
     VAD_REQUIRE(ddof == 0 || ddof == 1, "mapstat_finalize: ddof must be 0 or 1, got %d", ddof);
     VAD_REQUIRE(mean != nullptr || std_out != nullptr, "mapstat_finalize: mean and std are both NULL");
-    VAD_REQUIRE((uintptr_t)mean % 4 == 0 && (uintptr_t)std_out % 4 == 0, "mapstat_finalize: mean and std must be 4-byte aligned");
+    VAD_REQUIRE(vad_aligned(mean, 4) && vad_aligned(std_out, 4), "mapstat_finalize: mean and std must be 4-byte aligned");
     hipLaunchKernelGGL(mapstat_finalize_kernel, dim3(ms_blocks(h, w)), dim3(MS_THREADS), 0, (hipStream_t)stream, state, h, w, ddof, mean, std_out);
     VAD_LAUNCH_CHECK();
     return VAD_OK;
 }
 
 extern "C" size_t vad_map_normalize_workspace_bytes(long long n, int h, int w) {
-    if (n < 0 || !ms_dims_ok(h, w) || n > (1ll << 60) / ((long long)h * w)) return 0;
+    if (!vad_map_dims_ok(n, h, w)) return 0;
     return (size_t)n * (size_t)nz_chunks(h, w) * sizeof(float);
 }
 
 extern "C" int vad_map_normalize(const float* maps, long long n, int h, int w, const float* mean, const float* std_in, float min_std, float* out,
                                  float* frame_max, void* ws, size_t ws_bytes, void* stream) {
-    VAD_REQUIRE(n >= 0, "map_normalize: n=%lld is negative", n);
-    MS_REQUIRE_DIMS("map_normalize", h, w);
-    VAD_REQUIRE(n <= (1ll << 60) / ((long long)h * w), "map_normalize: n * h * w is not representable (n=%lld)", n);
+    VAD_ARG(vad_req_map_dims("map_normalize", n, h, w));
     VAD_REQUIRE(min_std > 0.f && min_std <= 3.402823466e38f, "map_normalize: min_std must be finite and greater than 0, got %g", (double)min_std);
     VAD_REQUIRE(out != nullptr || frame_max != nullptr, "map_normalize: out and frame_max are both NULL");
     VAD_REQUIRE(maps != nullptr && mean != nullptr && std_in != nullptr, "map_normalize: maps, mean or std is NULL");
-    VAD_REQUIRE((uintptr_t)maps % 4 == 0 && (uintptr_t)mean % 4 == 0 && (uintptr_t)std_in % 4 == 0 && (uintptr_t)out % 4 == 0 &&
-                    (uintptr_t)frame_max % 4 == 0 && (uintptr_t)ws % 4 == 0,
+    VAD_REQUIRE(vad_aligned(maps, 4) && vad_aligned(mean, 4) && vad_aligned(std_in, 4) && vad_aligned(out, 4) && vad_aligned(frame_max, 4) &&
+                    vad_aligned(ws, 4),
                 "map_normalize: maps, mean, std, out, frame_max and ws must be 4-byte aligned");
-    const size_t bytes = (size_t)n * h * w * sizeof(float);
-    if (out != nullptr && out != maps) {
-        const uintptr_t a = (uintptr_t)maps, b = (uintptr_t)out;
-        VAD_REQUIRE(a + bytes <= b || b + bytes <= a, "map_normalize: out partly overlaps maps (out == maps, in place, is allowed)");
-    }
+    VAD_REQUIRE(out == nullptr || out == maps || vad_disjoint(maps, out, (size_t)n * h * w * sizeof(float)),
+                "map_normalize: out partly overlaps maps (out == maps, in place, is allowed)");
     const long long chunks = nz_chunks(h, w);
     if (frame_max != nullptr) {
         const size_t need = vad_map_normalize_workspace_bytes(n, h, w);

@@ -30,6 +30,7 @@
 #include <hip/hip_runtime.h>
 
 #include "region_table.h"
+#include "vad_args.h"
 #include "vad_common.h"
 
 namespace {
@@ -504,35 +505,29 @@ int track_run(const char* who, const float* maps, long long b, int t, int h, int
               unsigned min_duration, unsigned min_volume, int max_open, int max_closed, void* state, uint32_t* closed, uint32_t* counts,
               uint32_t* frame_counts, void* ws, size_t ws_bytes, void* stream) {
     const bool flush = t == 0;
-    VAD_REQUIRE(flush || maps != nullptr, "%s: maps is NULL", who);
-    VAD_REQUIRE((uintptr_t)maps % 4 == 0, "%s: maps must be 4-byte aligned", who);
+    if (!flush) VAD_ARG(vad_req_nonnull(who, "maps", maps));
+    VAD_ARG(vad_req_aligned(who, "maps", maps, 4));
     VAD_REQUIRE(b >= 0 && b <= (1ll << 20), "%s: b must be in 0..2^20, got %lld", who, b);
-    VAD_REQUIRE(flush || t >= 1, "%s: t must be >= 1, got %d", who, t);
+    if (!flush) VAD_ARG(vad_req_t(who, t));
     VAD_REQUIRE(h >= 1 && w >= 1 && (long long)h * w <= TR_MAX_PIXELS, "%s: h and w must be >= 1 with h * w <= 2^24, got %d x %d", who, h, w);
     VAD_REQUIRE(flush || (long long)b * t * ((long long)h * w) <= (1ll << 38), "%s: b * t * h * w must be at most 2^38 (%lld x %d x %d x %d)", who,
                 b, t, h, w);
-    VAD_REQUIRE(threshold == threshold, "%s: threshold is NaN", who);
-    VAD_REQUIRE(connectivity == 4 || connectivity == 8, "%s: connectivity must be 4 or 8, got %d", who, connectivity);
+    VAD_ARG(vad_req_threshold(who, threshold));
+    VAD_ARG(vad_req_connectivity(who, connectivity));
     VAD_REQUIRE(temporal == 1 || temporal == 9, "%s: temporal must be 1 or 9, got %d", who, temporal);
     VAD_REQUIRE(temporal == 1 || connectivity == 8, "%s: temporal 9 needs connectivity 8, got connectivity %d", who, connectivity);
-    VAD_REQUIRE(min_duration >= 1u, "%s: min_duration must be >= 1, got 0", who);
-    VAD_REQUIRE(min_volume >= 1u, "%s: min_volume must be >= 1, got 0", who);
-    VAD_REQUIRE(max_open >= 1 && max_open <= TR_MAX_OPEN, "%s: max_open must be in 1..%d, got %d", who, TR_MAX_OPEN, max_open);
-    VAD_REQUIRE(max_closed >= 1 && max_closed <= TR_MAX_CLOSED, "%s: max_closed must be in 1..%d, got %d", who, TR_MAX_CLOSED, max_closed);
-    VAD_REQUIRE(state != nullptr, "%s: state is NULL", who);
-    VAD_REQUIRE((uintptr_t)state % 16 == 0, "%s: state must be 16-byte aligned", who);
-    VAD_REQUIRE(closed != nullptr, "%s: closed is NULL", who);
-    VAD_REQUIRE((uintptr_t)closed % 16 == 0, "%s: closed must be 16-byte aligned", who);
-    VAD_REQUIRE(counts != nullptr, "%s: counts is NULL", who);
-    VAD_REQUIRE((uintptr_t)counts % 4 == 0, "%s: counts must be 4-byte aligned", who);
-    VAD_REQUIRE(flush || frame_counts != nullptr, "%s: frame_counts is NULL", who);
-    VAD_REQUIRE((uintptr_t)frame_counts % 4 == 0, "%s: frame_counts must be 4-byte aligned", who);
-    VAD_REQUIRE(ws != nullptr, "%s: ws is NULL", who);
-    VAD_REQUIRE((uintptr_t)ws % 16 == 0, "%s: ws must be 16-byte aligned", who);
+    VAD_ARG(vad_req_nonzero(who, "min_duration", min_duration));
+    VAD_ARG(vad_req_nonzero(who, "min_volume", min_volume));
+    VAD_ARG(vad_req_capacity(who, "max_open", max_open, TR_MAX_OPEN));
+    VAD_ARG(vad_req_capacity(who, "max_closed", max_closed, TR_MAX_CLOSED));
+    VAD_ARG(vad_req_ptr(who, "state", state, 16));
+    VAD_ARG(vad_req_ptr(who, "closed", closed, 16));
+    VAD_ARG(vad_req_ptr(who, "counts", counts, 4));
+    if (!flush) VAD_ARG(vad_req_nonnull(who, "frame_counts", frame_counts));
+    VAD_ARG(vad_req_aligned(who, "frame_counts", frame_counts, 4));
+    VAD_ARG(vad_req_ptr(who, "ws", ws, 16));
     const TrackWs c = track_carve(b, t, h, w, max_open);
-    if (ws_bytes < c.total)
-        return vad_fail(VAD_ERR_WS, "%s: ws_bytes %zu is less than vad_track_workspace_bytes(%lld, %d, %d, %d, %d) = %zu", who, ws_bytes, b, t, h, w,
-                        max_open, c.total);
+    VAD_REQUIRE_WS(VAD_ERR_WS, who, ws_bytes, c.total, "vad_track_workspace_bytes(%lld, %d, %d, %d, %d)", b, t, h, w, max_open);
     const hipStream_t s = (hipStream_t)stream;
     if (b == 0) {                                            // nothing to track: the flag word still reads "no defect"
         VAD_HIP_TRY(hipMemsetAsync(ws, 0, VAD_LABEL_WS_HEAD_BYTES, s));
@@ -630,11 +625,10 @@ int vad_track_plan(int* label_round, int* pixel_round, int* scan_round, int* tab
 }
 
 int vad_track_init(void* state, long long b, int h, int w, int max_open, void* stream) {
-    VAD_REQUIRE(state != nullptr, "track_init: state is NULL");
-    VAD_REQUIRE((uintptr_t)state % 16 == 0, "track_init: state must be 16-byte aligned");
+    VAD_ARG(vad_req_ptr("track_init", "state", state, 16));
     VAD_REQUIRE(b >= 0 && b <= (1ll << 20), "track_init: b must be in 0..2^20, got %lld", b);
     VAD_REQUIRE(h >= 1 && w >= 1 && (long long)h * w <= TR_MAX_PIXELS, "track_init: h and w must be >= 1 with h * w <= 2^24, got %d x %d", h, w);
-    VAD_REQUIRE(max_open >= 1 && max_open <= TR_MAX_OPEN, "track_init: max_open must be in 1..%d, got %d", TR_MAX_OPEN, max_open);
+    VAD_ARG(vad_req_capacity("track_init", "max_open", max_open, TR_MAX_OPEN));
     if (b == 0) return VAD_OK;
     TrackP p = {};
     p.state = (unsigned*)state;
@@ -653,7 +647,7 @@ int vad_track_init(void* state, long long b, int h, int w, int max_open, void* s
 int vad_track_events(const float* maps, long long b, int t, int h, int w, float threshold, int connectivity, int temporal,
                      unsigned min_duration, unsigned min_volume, int max_open, int max_closed, void* state, uint32_t* closed,
                      uint32_t* counts, uint32_t* frame_counts, void* ws, size_t ws_bytes, void* stream) {
-    VAD_REQUIRE(t >= 1, "track_events: t must be >= 1, got %d", t);
+    VAD_ARG(vad_req_t("track_events", t));
     return track_run("track_events", maps, b, t, h, w, threshold, connectivity, temporal, min_duration, min_volume, max_open, max_closed, state,
                      closed, counts, frame_counts, ws, ws_bytes, stream);
 }

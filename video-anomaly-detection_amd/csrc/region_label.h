@@ -13,9 +13,6 @@ constexpr size_t VAD_LABEL_WS_HEAD_BYTES = 16;   // the flag word, padded so tha
 constexpr unsigned VAD_LABEL_FLAG_WALK = 1u;     // flag word: a root chase or a union ran out of its step budget
 constexpr unsigned VAD_LABEL_ROUND_PIXELS = 4096u * 256u;   // pixels of one frame that one grid round of the labelling kernels covers
 
-// n >= 0, h, w >= 1, h * w < 2^31 - 1, n * h * w <= 2^38: the limits of vad_label_regions; *total = n * h * w.
-bool vad_label_dims_ok(long long n, int h, int w, long long* total);
-
 // init, merge, flatten on `s`: labels int32 [n, h, w] (0, or 1 + the smallest y * w + x of the region), sizes (may be NULL)
 // uint32 [n, h, w] (the pixel count at the root, 0 elsewhere), flags[0] cleared by the first kernel and set by a walk that ran out
 // of its bound.  `threshold` is read under VAD_LABEL_FMT_F32_GE only.  The arguments are the caller's to check.

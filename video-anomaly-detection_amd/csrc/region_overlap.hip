@@ -26,6 +26,7 @@
 
 #include "region_label.h"
 #include "score_hist_lds.h"
+#include "vad_args.h"
 #include "vad_common.h"
 
 namespace {
@@ -36,7 +37,6 @@ constexpr int LABEL_THREADS = 256;
 constexpr unsigned LABEL_MAX_BLOCKS_X = 4096;
 constexpr unsigned LABEL_FLAG_WALK = VAD_LABEL_FLAG_WALK;   // a root chase or a union ran out of its step budget
 constexpr unsigned LABEL_FLAG_SIZE = 2u;       // an anomalous pixel's region has size 0 (the label planes are not a labelling)
-constexpr long long PRO_MAX_ELEMS = 1ll << 38; // n * h * w of one call: a work-group's run of a 256-group launch stays below 2^32
 constexpr size_t WS_HEAD_BYTES = VAD_LABEL_WS_HEAD_BYTES;
 static_assert(LABEL_MAX_BLOCKS_X * LABEL_THREADS == VAD_LABEL_ROUND_PIXELS, "region_label.h reports the labeller's grid round");
 
@@ -268,29 +268,16 @@ __global__ __launch_bounds__(256) void pro_merge_kernel(unsigned* dst, const uns
     }
 }
 
-bool pro_m_ok(int m) { return m >= VAD_HIST_MIN_M && m <= VAD_HIST_MAX_M; }
-
 // The checks the two labelling entry points share; *total = n * h * w.
 int label_args(const char* fn, const void* masks, int label_format, long long n, int h, int w, int connectivity, long long* total) {
-    VAD_REQUIRE(masks != nullptr, "%s: masks is NULL", fn);
-    VAD_REQUIRE(label_format == VAD_LBL_U8_ELEM || label_format == VAD_LBL_F32_ELEM,
-                "%s: label_format must be VAD_LBL_U8_ELEM (%d) or VAD_LBL_F32_ELEM (%d), got %d", fn, VAD_LBL_U8_ELEM, VAD_LBL_F32_ELEM,
-                label_format);
-    VAD_REQUIRE(label_format != VAD_LBL_F32_ELEM || (uintptr_t)masks % 4 == 0, "%s: float masks must be 4-byte aligned", fn);
-    VAD_REQUIRE(n >= 0, "%s: n must be >= 0, got %lld", fn, n);
-    VAD_REQUIRE(h >= 1 && w >= 1 && (long long)h * w < 2147483647ll, "%s: h and w must be >= 1 with h * w < 2^31 - 1, got %d x %d", fn, h, w);
-    VAD_REQUIRE(connectivity == 4 || connectivity == 8, "%s: connectivity must be 4 or 8, got %d", fn, connectivity);
-    VAD_REQUIRE(!__builtin_mul_overflow(n, (long long)h * w, total) && *total <= PRO_MAX_ELEMS,
-                "%s: n * h * w must be at most 2^38 (%lld x %d x %d)", fn, n, h, w);
-    return VAD_OK;
+    VAD_ARG(vad_req_masks(fn, masks, "label_format", label_format));
+    VAD_ARG(vad_req_label_n(fn, "n", n));
+    VAD_ARG(vad_req_label_hw(fn, h, w));
+    VAD_ARG(vad_req_connectivity(fn, connectivity));
+    return vad_req_label_total(fn, n, h, w, total);
 }
 
 }  // namespace
-
-bool vad_label_dims_ok(long long n, int h, int w, long long* total) {
-    return n >= 0 && h >= 1 && w >= 1 && (long long)h * w < 2147483647ll && !__builtin_mul_overflow(n, (long long)h * w, total) &&
-           *total <= PRO_MAX_ELEMS;
-}
 
 int vad_label_launch(const void* masks, int fmt, float threshold, long long n, int h, int w, int conn, int* labels, unsigned* sizes,
                      unsigned* flags, hipStream_t s) {
@@ -318,14 +305,13 @@ int vad_label_launch(const void* masks, int fmt, float threshold, long long n, i
 }
 
 size_t vad_pro_state_bytes(int m) {
-    if (!pro_m_ok(m)) return 0;
+    if (!vad_hist_m_ok(m)) return 0;
     return 16 + 8 * (3 * (size_t)hist_nbins(m) + PRO_TAIL_WORDS);
 }
 
 int vad_pro_reset(void* state, int m, void* stream) {
-    VAD_REQUIRE(pro_m_ok(m), "pro_reset: m (mantissa_bits) must be in 4..15, got %d", m);
-    VAD_REQUIRE(state != nullptr, "pro_reset: state is NULL");
-    VAD_REQUIRE((uintptr_t)state % 16 == 0, "pro_reset: state must be 16-byte aligned");
+    VAD_ARG(vad_req_mantissa("pro_reset", m));
+    VAD_ARG(vad_req_ptr("pro_reset", "state", state, 16));
     const hipStream_t s = (hipStream_t)stream;
     VAD_HIP_TRY(hipMemsetAsync(state, 0, vad_pro_state_bytes(m), s));
     hipLaunchKernelGGL(pro_header_kernel, dim3(1), dim3(64), 0, s, (unsigned*)state, m);
@@ -334,10 +320,10 @@ int vad_pro_reset(void* state, int m, void* stream) {
 }
 
 int vad_pro_merge(void* dst, const void* src, int m, void* stream) {
-    VAD_REQUIRE(pro_m_ok(m), "pro_merge: m (mantissa_bits) must be in 4..15, got %d", m);
-    VAD_REQUIRE(dst != nullptr, "pro_merge: dst is NULL");
-    VAD_REQUIRE(src != nullptr, "pro_merge: src is NULL");
-    VAD_REQUIRE((uintptr_t)dst % 16 == 0 && (uintptr_t)src % 16 == 0, "pro_merge: dst and src must be 16-byte aligned");
+    VAD_ARG(vad_req_mantissa("pro_merge", m));
+    VAD_ARG(vad_req_nonnull("pro_merge", "dst", dst));
+    VAD_ARG(vad_req_nonnull("pro_merge", "src", src));
+    VAD_REQUIRE(vad_aligned(dst, 16) && vad_aligned(src, 16), "pro_merge: dst and src must be 16-byte aligned");
     VAD_REQUIRE(dst != src, "pro_merge: dst and src are the same state");
     const unsigned words = 3u * hist_nbins(m) + PRO_TAIL_WORDS;
     unsigned blocks = (words + 255u) / 256u;
@@ -356,13 +342,11 @@ size_t vad_pro_workspace_bytes(long long n, int h, int w) {
 int vad_label_regions(const void* masks, int label_format, long long n, int h, int w, int connectivity, int32_t* labels,
                       uint32_t* sizes_or_null, void* ws, size_t ws_bytes, void* stream) {
     long long total = 0;
-    if (int rc = label_args("label_regions", masks, label_format, n, h, w, connectivity, &total)) return rc;
-    VAD_REQUIRE(labels != nullptr, "label_regions: labels is NULL");
-    VAD_REQUIRE((uintptr_t)labels % 4 == 0 && (uintptr_t)sizes_or_null % 4 == 0, "label_regions: labels and sizes must be 4-byte aligned");
-    VAD_REQUIRE(ws != nullptr, "label_regions: ws is NULL");
-    VAD_REQUIRE((uintptr_t)ws % 16 == 0, "label_regions: ws must be 16-byte aligned");
-    VAD_REQUIRE(ws_bytes >= vad_pro_workspace_bytes(n, h, w), "label_regions: ws_bytes %zu is less than vad_pro_workspace_bytes(%lld, %d, %d) = %zu",
-                ws_bytes, n, h, w, vad_pro_workspace_bytes(n, h, w));
+    VAD_ARG(label_args("label_regions", masks, label_format, n, h, w, connectivity, &total));
+    VAD_ARG(vad_req_nonnull("label_regions", "labels", labels));
+    VAD_REQUIRE(vad_aligned(labels, 4) && vad_aligned(sizes_or_null, 4), "label_regions: labels and sizes must be 4-byte aligned");
+    VAD_ARG(vad_req_ptr("label_regions", "ws", ws, 16));
+    VAD_REQUIRE_WS(VAD_ERR_ARG, "label_regions", ws_bytes, vad_pro_workspace_bytes(n, h, w), "vad_pro_workspace_bytes(%lld, %d, %d)", n, h, w);
     const hipStream_t s = (hipStream_t)stream;
     if (n == 0) {                                            // nothing to label: the flag word still reads "no defect"
         VAD_HIP_TRY(hipMemsetAsync(ws, 0, WS_HEAD_BYTES, s));
@@ -373,17 +357,14 @@ int vad_label_regions(const void* masks, int label_format, long long n, int h, i
 
 int vad_pro_accumulate(const float* values, const void* masks, int label_format, long long n, int h, int w, int connectivity,
                        void* state, int m, void* ws, size_t ws_bytes, void* stream) {
-    VAD_REQUIRE(pro_m_ok(m), "pro_accumulate: m (mantissa_bits) must be in 4..15, got %d", m);
-    VAD_REQUIRE(values != nullptr, "pro_accumulate: values is NULL");
-    VAD_REQUIRE((uintptr_t)values % 4 == 0, "pro_accumulate: values must be 4-byte aligned");
+    const char* who = "pro_accumulate";
+    VAD_ARG(vad_req_mantissa(who, m));
+    VAD_ARG(vad_req_ptr(who, "values", values, 4));
     long long total = 0;
-    if (int rc = label_args("pro_accumulate", masks, label_format, n, h, w, connectivity, &total)) return rc;
-    VAD_REQUIRE(state != nullptr, "pro_accumulate: state is NULL");
-    VAD_REQUIRE((uintptr_t)state % 16 == 0, "pro_accumulate: state must be 16-byte aligned");
-    VAD_REQUIRE(ws != nullptr, "pro_accumulate: ws is NULL");
-    VAD_REQUIRE((uintptr_t)ws % 16 == 0, "pro_accumulate: ws must be 16-byte aligned");
-    VAD_REQUIRE(ws_bytes >= vad_pro_workspace_bytes(n, h, w), "pro_accumulate: ws_bytes %zu is less than vad_pro_workspace_bytes(%lld, %d, %d) = %zu",
-                ws_bytes, n, h, w, vad_pro_workspace_bytes(n, h, w));
+    VAD_ARG(label_args(who, masks, label_format, n, h, w, connectivity, &total));
+    VAD_ARG(vad_req_ptr(who, "state", state, 16));
+    VAD_ARG(vad_req_ptr(who, "ws", ws, 16));
+    VAD_REQUIRE_WS(VAD_ERR_ARG, who, ws_bytes, vad_pro_workspace_bytes(n, h, w), "vad_pro_workspace_bytes(%lld, %d, %d)", n, h, w);
     if (n == 0) return VAD_OK;
     const hipStream_t s = (hipStream_t)stream;
     unsigned* flags = (unsigned*)ws;

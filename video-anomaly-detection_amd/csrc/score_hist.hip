@@ -30,6 +30,7 @@
 #include <hip/hip_runtime.h>
 
 #include "score_hist_lds.h"
+#include "vad_args.h"
 #include "vad_common.h"
 
 namespace {
@@ -170,19 +171,16 @@ __global__ __launch_bounds__(256) void hist_merge_kernel(unsigned* dst, const un
     for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < pairs; i += gridDim.x * 256u) d[i] += s[i];
 }
 
-bool hist_m_ok(int m) { return m >= 4 && m <= 15; }
-
 }  // namespace
 
 size_t vad_hist_state_bytes(int m) {
-    if (!hist_m_ok(m)) return 0;
+    if (!vad_hist_m_ok(m)) return 0;
     return 16 + 8 * (2 * (size_t)hist_nbins(m) + 2);
 }
 
 int vad_hist_reset(void* state, int m, void* stream) {
-    VAD_REQUIRE(hist_m_ok(m), "hist_reset: m (mantissa_bits) must be in 4..15, got %d", m);
-    VAD_REQUIRE(state != nullptr, "hist_reset: state is NULL");
-    VAD_REQUIRE((uintptr_t)state % 16 == 0, "hist_reset: state must be 16-byte aligned");
+    VAD_ARG(vad_req_mantissa("hist_reset", m));
+    VAD_ARG(vad_req_ptr("hist_reset", "state", state, 16));
     const hipStream_t s = (hipStream_t)stream;
     VAD_HIP_TRY(hipMemsetAsync(state, 0, vad_hist_state_bytes(m), s));
     hipLaunchKernelGGL(hist_header_kernel, dim3(1), dim3(64), 0, s, (unsigned*)state, m);
@@ -192,10 +190,11 @@ int vad_hist_reset(void* state, int m, void* stream) {
 
 int vad_hist_accumulate(const float* values, long long n_groups, long long group_elems, const void* labels, int label_format,
                         void* state, int m, void* stream) {
-    VAD_REQUIRE(hist_m_ok(m), "hist_accumulate: m (mantissa_bits) must be in 4..15, got %d", m);
-    VAD_REQUIRE(values != nullptr, "hist_accumulate: values is NULL");
-    VAD_REQUIRE(labels != nullptr, "hist_accumulate: labels is NULL");
-    VAD_REQUIRE(state != nullptr, "hist_accumulate: state is NULL");
+    const char* who = "hist_accumulate";
+    VAD_ARG(vad_req_mantissa(who, m));
+    VAD_ARG(vad_req_nonnull(who, "values", values));
+    VAD_ARG(vad_req_nonnull(who, "labels", labels));
+    VAD_ARG(vad_req_nonnull(who, "state", state));
     VAD_REQUIRE(label_format == VAD_LBL_U8_ELEM || label_format == VAD_LBL_F32_ELEM || label_format == VAD_LBL_U8_GROUP,
                 "hist_accumulate: label_format must be VAD_LBL_U8_ELEM (%d), VAD_LBL_F32_ELEM (%d) or VAD_LBL_U8_GROUP (%d), got %d",
                 VAD_LBL_U8_ELEM, VAD_LBL_F32_ELEM, VAD_LBL_U8_GROUP, label_format);
@@ -204,9 +203,9 @@ int vad_hist_accumulate(const float* values, long long n_groups, long long group
     long long total = 0;
     VAD_REQUIRE(!__builtin_mul_overflow(n_groups, group_elems, &total) && total <= (1ll << 60),
                 "hist_accumulate: n_groups * group_elems is not representable (%lld x %lld)", n_groups, group_elems);
-    VAD_REQUIRE((uintptr_t)values % 4 == 0, "hist_accumulate: values must be 4-byte aligned");
-    VAD_REQUIRE(label_format != VAD_LBL_F32_ELEM || (uintptr_t)labels % 4 == 0, "hist_accumulate: float labels must be 4-byte aligned");
-    VAD_REQUIRE((uintptr_t)state % 16 == 0, "hist_accumulate: state must be 16-byte aligned");
+    VAD_ARG(vad_req_aligned(who, "values", values, 4));
+    VAD_ARG(vad_req_float_labels(who, "labels", labels, label_format));
+    VAD_ARG(vad_req_aligned(who, "state", state, 16));
 
     const hipStream_t s = (hipStream_t)stream;
     for (long long base = 0; base < total; base += HIST_LAUNCH_ELEMS) {
@@ -238,10 +237,10 @@ int vad_hist_accumulate(const float* values, long long n_groups, long long group
 }
 
 int vad_hist_merge(void* dst, const void* src, int m, void* stream) {
-    VAD_REQUIRE(hist_m_ok(m), "hist_merge: m (mantissa_bits) must be in 4..15, got %d", m);
-    VAD_REQUIRE(dst != nullptr, "hist_merge: dst is NULL");
-    VAD_REQUIRE(src != nullptr, "hist_merge: src is NULL");
-    VAD_REQUIRE((uintptr_t)dst % 16 == 0 && (uintptr_t)src % 16 == 0, "hist_merge: dst and src must be 16-byte aligned");
+    VAD_ARG(vad_req_mantissa("hist_merge", m));
+    VAD_ARG(vad_req_nonnull("hist_merge", "dst", dst));
+    VAD_ARG(vad_req_nonnull("hist_merge", "src", src));
+    VAD_REQUIRE(vad_aligned(dst, 16) && vad_aligned(src, 16), "hist_merge: dst and src must be 16-byte aligned");
     VAD_REQUIRE(dst != src, "hist_merge: dst and src are the same state");
     const unsigned pairs = hist_nbins(m) + 1u;
     unsigned blocks = (pairs + 255u) / 256u;

@@ -7,6 +7,7 @@
 #include <atomic>
 #include <mutex>
 #include <vector>
+#include "vad_args.h"
 #include "vad_common.h"
 #include "vad_layout.h"
 
@@ -126,7 +127,6 @@ extern "C" int vad_debug_set_tail_group(int frames) { g_vad_tail_group = frames;
 // (frames of more than VAD_MAX_FRAME_PIXELS pixels do not fit the kernels' 24-bit pixel indices, vad_common.h)
 static bool frame_shape_ok(int h, int w) { return h > 0 && w > 0 && h % 16 == 0 && w % 16 == 0 && vad_frame_pixels_ok(h, w); }
 static bool in_ch_ok(int in_ch) { return in_ch >= 3 && in_ch <= VAD_MAX_IN_CH; }
-static bool aligned(const void* p, uintptr_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
 
 static int req_frame_shape(const char* who, int h, int w, const char* why) {
     VAD_REQUIRE(h > 0 && w > 0 && h % 16 == 0 && w % 16 == 0, "%s: H=%d W=%d must be positive multiples of 16%s", who, h, w, why);
@@ -147,11 +147,11 @@ static int req_input(const char* who, int x_format, int in_ch) {
 // the caller's workspace holds what the carve needs, and it and the weight blob are aligned
 static int req_workspace(const char* who, const void* ws, size_t ws_bytes, size_t need, const void* packed) {
     if (ws_bytes < need) return vad_fail(VAD_ERR_WS, "%s: workspace %zu B < required %zu B", who, ws_bytes, need);
-    VAD_REQUIRE(aligned(ws, 256) && aligned(packed, 16), "%s: workspace must be 256-B and weights 16-B aligned", who);
+    VAD_REQUIRE(vad_aligned(ws, 256) && vad_aligned(packed, 16), "%s: workspace must be 256-B and weights 16-B aligned", who);
     return VAD_OK;
 }
 static int req_state_aligned(const char* who, const float* state_in, const float* state_out) {
-    VAD_REQUIRE(aligned(state_in, 16) && aligned(state_out, 16), "%s: state blobs must be 16-B aligned", who);
+    VAD_REQUIRE(vad_aligned(state_in, 16) && vad_aligned(state_out, 16), "%s: state blobs must be 16-B aligned", who);
     return VAD_OK;
 }
 
@@ -690,7 +690,7 @@ extern "C" int vad_convlstm_seq(const float* x, int precision, long long b, int 
     LstmRun R{};
     const size_t need = seq_carve(ws, R, (int)b, t, gh, gw, hid_p, layers, all_layers);
     if (ws_bytes < need) return vad_fail(VAD_ERR_WS, "convlstm_seq: workspace %zu B < required %zu B", ws_bytes, need);
-    VAD_REQUIRE(aligned(ws, 256) && aligned(packed, 16) && aligned(x, 16) && aligned(hseq_out, 16),
+    VAD_REQUIRE(vad_aligned(ws, 256) && vad_aligned(packed, 16) && vad_aligned(x, 16) && vad_aligned(hseq_out, 16),
                 "convlstm_seq: workspace must be 256-B, weights / x / hseq_out 16-B aligned");
     TRY(req_state_aligned("convlstm_seq", state_in, state_out));
     hipStream_t s = (hipStream_t)stream;

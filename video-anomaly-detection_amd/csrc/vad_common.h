@@ -31,8 +31,8 @@ int vad_fail(int code, const char* fmt, ...);
 // (VAD_MAX_FRAME_PIXELS = 2^23 - 1: include/vad_hip.h)
 static inline bool vad_frame_pixels_ok(int h, int w) { return (long long)h * w <= VAD_MAX_FRAME_PIXELS; }
 #define VAD_REQUIRE_PIXELS(who, h, w)                                                                                              \
-    VAD_REQUIRE(vad_frame_pixels_ok(h, w), who ": %dx%d = %lld pixels per frame exceed the limit of %d (2^23 - 1: pixel indices are " \
-                "24-bit multiply operands inside the kernels)", h, w, (long long)(h) * (w), VAD_MAX_FRAME_PIXELS)
+    VAD_REQUIRE(vad_frame_pixels_ok(h, w), "%s: %dx%d = %lld pixels per frame exceed the limit of %d (2^23 - 1: pixel indices are "   \
+                "24-bit multiply operands inside the kernels)", who, h, w, (long long)(h) * (w), VAD_MAX_FRAME_PIXELS)
 
 // A positive, finite power of two: multiplying by it is exact (up to overflow / underflow), which is what the gradient
 // rescaling of the split-fp16 training mode relies on.
