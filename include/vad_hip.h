@@ -852,6 +852,41 @@ int vad_smooth_maps(const float* maps, long long n, int h, int w, const float* t
                     void* ws, size_t ws_bytes, void* stream);
 int vad_smooth_tile(int* tile_h, int* tile_w);
 
+/* ------------------------------------------------------------------ Order statistics and top-k means of anomaly maps (csrc/map_topk.hip)
+ * The robust frame scores between the mean of a map (a small defect barely moves it) and its maximum (one pixel decides): the k-th
+ * largest pixel - a quantile - and the mean of the k largest pixels, for up to VAD_TOPK_MAX_RANKS ranks in one call.
+ *
+ * vad_map_topk: maps = n frames of h x w fp32, contiguous (any h, w >= 1 with P = h * w <= VAD_MAX_FRAME_PIXELS; 4-byte aligned).
+ * ranks: nk values in HOST memory (nk in 1 .. VAD_TOPK_MAX_RANKS), each in 1 .. P; rank k means the k-th largest.  Any order and
+ * duplicates are allowed: every column is independent of the others.  The ranks are read at call time and travel as kernel
+ * arguments, so a captured call replays with the ranks it was captured with.
+ * Pixels are ordered by the monotone key of their bits, key = bits ^ (bits >> 31 ? 0xFFFFFFFF : 0x80000000), compared unsigned:
+ * -inf < ... < -0.0 < +0.0 < ... < +inf; a tie between -0.0 and +0.0 is decided.
+ * kth (may be NULL) [n, nk]: kth[i, j] is the pixel of frame i whose key is the ranks[j]-th largest, its bits unchanged.
+ * topk_mean (may be NULL; not both) [n, nk]: (float)((S + (double)(k - c) * (double)v) / (double)k) with k = ranks[j], v = kth[i, j],
+ * c = the number of pixels of the frame with key > key(v) and S = the float64 sum of those c pixels - every term is exact in double,
+ * the order of the additions is the kernel's and is fixed, so S is within c * 2^-53 * sum|x| of the exact sum and the mean within
+ * half a float32 spacing more.  IEEE double arithmetic decides the infinities: a +inf among the k largest gives +inf, both signs NaN.
+ * A frame with any NaN pixel gets the canonical quiet NaN (0x7FC00000) in every output, torch.amax's rule and frame_max's above; no
+ * other frame changes a bit.  A frame's outputs are the same words for any n, any position in the batch, any contents of the other
+ * frames, eager or replayed: integer atomics on counters only, sums folded in a fixed order, no work-group reads another's results.
+ * ws: caller-provided, 16-byte aligned, vad_topk_workspace_bytes(n, h, w, nk) bytes (0 for arguments out of range; no device is
+ * needed).  It begins with 16 bytes per frame and rank, the record the outputs were formed from - uint32 bits of v, uint32 c, double
+ * S (a NaN frame: 0x7FC00000, 0, NaN); frames above the split boundary add 80 bytes of state and nk tables of 8 KiB per frame and
+ * 8 bytes per slice, frame and rank.  VAD_ERR_ARG for both outputs NULL, nk out of range, a rank of 0 or above P, n < 0 (or above
+ * 2^56), h or w out of range, a NULL or misaligned pointer, an output overlapping maps; VAD_ERR_WS for a short workspace.  n == 0
+ * returns VAD_OK and launches nothing.  Three reads of the maps.  Frames of at most `split_above` pixels: one launch, one work-group
+ * per frame.  Larger frames - which one CU would read for milliseconds - are split into slices of `slice_pixels` pixels, one
+ * work-group each: a memset and six launches (per digit a histogram launch that adds integer counters into the frame's tables and
+ * a pick launch; the slices' float64 sums are added in slice order).  All on `stream`, no allocation, no host synchronisation:
+ * capturable in a graph.
+ * vad_topk_plan reports the boundary between the two paths and the slice - what a test needs to put a frame on each side. */
+#define VAD_TOPK_MAX_RANKS 8
+size_t vad_topk_workspace_bytes(long long n, int h, int w, int nk);
+int vad_topk_plan(int* split_above, int* slice_pixels);
+int vad_map_topk(const float* maps, long long n, int h, int w, const unsigned* ranks, int nk, float* kth, float* topk_mean,
+                 void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ Grey morphology of anomaly maps (csrc/map_morph.hip)
  * The clean-up between the map and its threshold: an opening removes speckle that no Gaussian removes without blurring real
  * defects, a closing fills pinholes and joins the fragments of one defect.  Flat rectangular structuring element.

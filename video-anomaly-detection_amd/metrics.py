@@ -30,6 +30,9 @@ sixteen counters per frame into the report a line is accepted on.
 
 Across all of them sits the calibration: `MapStatistics` (csrc/map_stats.hip) holds the per-pixel mean and standard deviation of the
 map over normal frames and turns a map into its z-score, which is then smoothed-and-ranked, thresholded and labelled like a raw map.
+
+At the end of the chain, where a map becomes ONE number per frame, sit `map_topk` and `reduce_maps` (csrc/map_topk.hip): the k-th
+largest pixel and the mean of the k largest, the robust frame scores between the mean of the map and its maximum.
 """
 from __future__ import annotations
 
@@ -985,6 +988,130 @@ def apply_morph(maps: torch.Tensor, steps) -> torch.Tensor:
             bufs.append(morph_maps(maps, op, size, out=bufs[-2]))
         maps = bufs[-1]
     return maps
+
+
+# ====================================================================== robust frame scores: top-k means and quantiles of maps
+# The reduction from a map to a frame score.  The reference's score is the mean of the error map, which a
+# 20 x 20 scratch on a 256 x 256 frame barely moves; the maximum (`smooth_maps(return_max=)`) is one pixel.  Between the two sit
+# the mean of the k largest pixels (top-k pooling, k = 0.1 % .. 10 % of the frame) and a high quantile of the map: a radix select
+# on the device (`vad_map_topk`, csrc/map_topk.hip), no sort, no `torch.topk` / `torch.quantile` over `[N, H * W]`.
+TOPK_MAX_RANKS = hip.TOPK_MAX_RANKS
+REDUCE_KINDS = ("topk", "quantile", "rank")
+
+
+def _check_pixels(pixels, what: str) -> int:
+    return _check_int(pixels, "pixels", what, 1, hip.MAX_FRAME_PIXELS)
+
+
+def rank_of_fraction(fraction, pixels: int) -> int:
+    """The rank k of "the top `fraction` of a frame of `pixels` pixels": min(P, max(1, ceil(fraction * P))), in exact rational
+    arithmetic on the Python float as given - 0.01 of 65,536 pixels is 656 (the double nearest 0.01 lies above it).  `fraction` in
+    (0, 1]; `VadError` for anything else."""
+    from fractions import Fraction
+    what = "rank_of_fraction"
+    p = _check_pixels(pixels, what)
+    _check_number(fraction, "fraction", what, lambda v: 0.0 < float(v) <= 1.0, "a number in (0, 1]")   # false for NaN
+    k = Fraction(float(fraction)) * p
+    return min(p, max(1, -((-k.numerator) // k.denominator)))
+
+
+def rank_of_quantile(q, pixels: int) -> int:
+    """The rank k at which `kth` is `np.quantile(frame, q, method="higher")`: P - ceil(q * (P - 1)), the product in float64 as numpy
+    forms it.  `q` in [0, 1] (1 = the maximum, rank 1; 0 = the minimum, rank P); `VadError` for anything else."""
+    import math
+    what = "rank_of_quantile"
+    p = _check_pixels(pixels, what)
+    q = _check_fraction(q, "q", what)
+    return p - int(math.ceil(float(np.float64(q) * np.float64(p - 1))))
+
+
+def _check_ranks(ranks, pixels: int, what: str) -> Tuple[list, bool]:
+    """An int or a sequence of 1 .. 8 ints, each in 1 .. pixels -> (list, was it a single int)."""
+    single = _is_int(ranks)
+    if single:
+        ranks = [ranks]
+    if not isinstance(ranks, (list, tuple)) or not 1 <= len(ranks) <= TOPK_MAX_RANKS or not all(_is_int(k) for k in ranks):
+        raise hip.VadError(f"{what}: ranks must be an int or a sequence of 1..{TOPK_MAX_RANKS} ints, got {ranks!r}")
+    for k in ranks:
+        if not 1 <= int(k) <= pixels:
+            raise hip.VadError(f"{what}: a rank must be in 1..{pixels} (H * W; rank k = the k-th largest pixel), got {k!r}")
+    return [int(k) for k in ranks], single
+
+
+def map_topk(maps: torch.Tensor, ranks, kth: bool = True, mean: bool = True) -> dict:
+    """Order statistics and top-k means of every H x W frame of `maps` on the GPU (`vad_map_topk`, csrc/map_topk.hip).  `maps` as
+    `smooth_maps` takes them: float32 GPU tensor, contiguous, the last two dimensions H, W and any leading ones (`[B,1,H,W]`, the
+    `[B,T,1,H,W]` maps of the video model, `[N,H,W]`); every frame on its own.  `ranks`: an int or a sequence of 1 .. 8 ints, each in
+    1 .. H * W; rank k is the k-th largest pixel; any order, duplicates allowed (`rank_of_fraction`, `rank_of_quantile` make them).
+    Returns a dict with 'kth' (if `kth`) and 'mean' (if `mean`), each float32 `[..., nk]` - `[...]` for an int - on the device:
+      kth   the k-th largest pixel in the order -inf < ... < -0.0 < +0.0 < ... < +inf, its bits unchanged;
+      mean  the mean of the k largest pixels, summed in float64 and rounded once to float32: within half a float32 spacing plus
+            P * 2^-52 * mean(|top k|) of the exact mean (tests/map_topk_ref.py).
+    A frame with a NaN pixel is NaN in both (`torch.amax`'s rule).  A frame's results do not depend on the batch around it.  One
+    launch (frames above `vad_topk_plan`'s 262,144 pixels: split over work-groups, six launches), no sort, no host synchronisation;
+    the ranks travel with the launches.  Asynchronous on the current stream."""
+    what = "map_topk"
+    if not isinstance(maps, torch.Tensor):
+        raise hip.VadError(f"{what}: maps must be a torch tensor")
+    if not (isinstance(kth, bool) and isinstance(mean, bool)) or not (kth or mean):
+        raise hip.VadError(f"{what}: kth and mean must be bools, at least one of them True, got {kth!r} and {mean!r}")
+    if not maps.is_cuda:
+        raise hip.VadError(f"{what}: maps ({maps.device}) must be on the GPU (the selection runs on the device; there is no CPU fallback)")
+    if maps.dtype != torch.float32:
+        raise hip.VadError(f"{what}: maps must be float32, got {maps.dtype}")
+    if maps.dim() < 2:
+        raise hip.VadError(f"{what}: maps must have at least the two dimensions H, W, got {tuple(maps.shape)}")
+    if not maps.is_contiguous():
+        raise hip.VadError(f"{what}: maps must be contiguous (got strides {tuple(maps.stride())} for {tuple(maps.shape)}); it is not copied silently")
+    lead, h, w = tuple(maps.shape[:-2]), int(maps.shape[-2]), int(maps.shape[-1])
+    if h < 1 or w < 1 or h * w > hip.MAX_FRAME_PIXELS:
+        raise hip.VadError(f"{what}: frames of {h} x {w} are out of range (H, W >= 1 and H * W <= {hip.MAX_FRAME_PIXELS})")
+    ranks, single = _check_ranks(ranks, h * w, what)
+    nk = len(ranks)
+    n = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    shape = lead if single else lead + (nk,)
+    with torch.cuda.device(maps.device):
+        out = {name: torch.empty(shape, dtype=torch.float32, device=maps.device) for name, on in (("kth", kth), ("mean", mean)) if on}
+        if n > 0:
+            l = hip.lib()
+            ws = _workspace(l.vad_topk_workspace_bytes(n, h, w, nk), maps.device, what, f"{n} maps of {h} x {w} with {nk} ranks are out of range")
+            hip.check(l.vad_map_topk(maps.data_ptr(), n, h, w, (hip.C.c_uint * nk)(*ranks), nk, hip.ptr(out.get("kth")), hip.ptr(out.get("mean")),
+                                     ws.data_ptr(), ws.numel(), hip.current_stream()), "vad_map_topk")
+            _count("map_topk")
+    return out
+
+
+def reduce_spec(reduce, what: str) -> Tuple[str, object]:
+    """What the `reduce=` arguments of the scoring entry points take, checked and normalised to (kind, argument): "max" -> ("rank",
+    1); ("topk", fraction in (0, 1]); ("quantile", q in [0, 1]); ("rank", k >= 1).  `VadError`, naming the spec, for anything else -
+    "mean" among them: the scoring tails already produce the mean with their own arithmetic."""
+    if reduce == "max":
+        return "rank", 1
+    if not isinstance(reduce, (tuple, list)) or len(reduce) != 2 or reduce[0] not in REDUCE_KINDS:
+        raise hip.VadError(f"{what}: reduce must be 'max', ('topk', fraction), ('quantile', q) or ('rank', k), got {reduce!r}")
+    kind, arg = reduce
+    if kind == "topk":
+        _check_number(arg, "the fraction of reduce=('topk', fraction)", what, lambda v: 0.0 < float(v) <= 1.0, "a number in (0, 1]")
+    elif kind == "quantile":
+        _check_fraction(arg, "the q of reduce=('quantile', q)", what)
+    else:
+        arg = _check_int(arg, "the k of reduce=('rank', k)", what, 1, hip.MAX_FRAME_PIXELS)
+    return kind, arg
+
+
+def reduce_maps(maps: torch.Tensor, reduce) -> torch.Tensor:
+    """The one place that turns maps `[..., H, W]` into frame scores `[...]`, on the device, with ONE `map_topk` call: `reduce` =
+    "max" (rank 1), ("topk", fraction) - the mean of the `rank_of_fraction(fraction, H * W)` largest pixels -, ("quantile", q) - the
+    pixel at `rank_of_quantile(q, H * W)`, numpy's `quantile(method="higher")` -, or ("rank", k) - the k-th largest pixel."""
+    what = "reduce_maps"
+    kind, arg = reduce_spec(reduce, what)
+    if not isinstance(maps, torch.Tensor) or maps.dim() < 2:
+        raise hip.VadError(f"{what}: maps must be a torch tensor with at least the two dimensions H, W")
+    pixels = int(maps.shape[-2]) * int(maps.shape[-1])
+    if kind == "topk":
+        return map_topk(maps, rank_of_fraction(arg, pixels), kth=False)["mean"]
+    rank = rank_of_quantile(arg, pixels) if kind == "quantile" else arg
+    return map_topk(maps, rank, mean=False)["kth"]
 
 
 # ====================================================================== defect regions of an anomaly map

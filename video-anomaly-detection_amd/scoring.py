@@ -97,6 +97,55 @@ def compute_auroc_smoothed(model, test_loader: Iterable[dict], device, sigma: fl
     return auroc, labels, scores, per_defect
 
 
+def frame_scores(model, images, reduce, map: str = "mse", sigma=None, truncate: float = 4.0, calibration=None,
+                 min_std: Optional[float] = None, morph=None):
+    """Robust frame scores of one batch: the model's anomaly maps - the chain of `localize`: `map`, `sigma`,
+    `truncate`, `calibration`, `min_std`, `morph` as there - reduced per frame by `metrics.reduce_maps(maps, reduce)`: `reduce` =
+    "max", ("topk", fraction) - the mean of the top fraction of the pixels -, ("quantile", q) or ("rank", k).  `images`: `[B,C,H,W]`
+    for the image model, `[B,T,C,H,W]` clips for the video model (map "mse" only).  Per batch ONE scoring call, the optional
+    smoothing / calibration / morphology calls and ONE `metrics.map_topk` call; nothing is read by the host.  Returns (scores, maps):
+    `[B]` / `[B,T]` float32 on the device, and the maps they were reduced from (`[B,1,H,W]` / `[B,T,1,H,W]`), so that a stream which
+    also localises does not score twice."""
+    what = "frame_scores"
+    _check_map_name(map, what)
+    metrics.reduce_spec(reduce, what)
+    morph = metrics.morph_steps(morph)
+    if images.dim() == 5 and map != "mse":
+        _refuse_clips_on(map, what, "scored")
+    min_std = _check_calibration(calibration, what, map, sigma, truncate, min_std)
+    with torch.no_grad():
+        maps = _anomaly_maps(model, images, map, sigma, truncate, calibration, min_std, morph)
+        return metrics.reduce_maps(maps, reduce).reshape(maps.shape[:-3]), maps
+
+
+def compute_auroc_maps(model, test_loader: Iterable[dict], device, reduce=("topk", 0.01), map: str = "mse", sigma=None,
+                       truncate: float = 4.0, calibration=None, min_std: Optional[float] = None, morph=None):
+    """`compute_auroc` with a robust image score: `frame_scores(model, images, reduce, ...)` - by default the mean of the top 1 % of
+    the error map's pixels - instead of the mean squared error, which a small defect on a large frame barely moves, or the maximum
+    (`compute_auroc_smoothed`), which is one pixel.  Same batches, same 4-tuple; the map arguments as in `pixel_auroc`.  The maps stay
+    on the device: a batch's scores are read back once, as `compute_auroc` does."""
+    what = "compute_auroc_maps"
+    _check_map_name(map, what)
+    metrics.reduce_spec(reduce, what)
+    metrics.morph_steps(morph)
+    _check_calibration(calibration, what, map, sigma, truncate, min_std)
+    all_labels, all_scores, all_types = [], [], []
+    for batch in test_loader:
+        scores, _ = frame_scores(model, batch["image"].to(device), reduce, map, sigma, truncate, calibration, min_std, morph)
+        all_scores.extend(scores.cpu().numpy())
+        all_labels.extend(np.asarray(batch["label"]))
+        all_types.extend(batch["defect_type"])
+    labels = np.array(all_labels)
+    scores = np.array(all_scores)
+    auroc = roc_auc(labels, scores)
+    per_defect = {}
+    for name in set(all_types):
+        m = np.array([d == name for d in all_types])
+        per_defect[name] = {"count": int(m.sum()), "mean_score": scores[m].mean(),
+                            "is_anomaly": labels[m][0] if m.any() else 0}
+    return auroc, labels, scores, per_defect
+
+
 def score_clips(model, loader: Iterable[dict], device, per_frame: bool = False):
     """Clip loop of the reference's evaluate_video.evaluate (evaluate_video.py:137-154): returns
     (clip scores float32[N], labels) and, when per_frame, also float32[N,T] frame scores computed in
@@ -554,18 +603,31 @@ def detection_report(model, loader: Iterable[dict], device, threshold: float, ma
     return counts.report(), counts
 
 
-def frame_auroc(model, loader: Iterable[dict], device, hist=None, mantissa_bits: int = 11):
+def frame_auroc(model, loader: Iterable[dict], device, hist=None, mantissa_bits: int = 11, reduce=None, sigma=None, truncate: float = 4.0,
+                calibration=None, min_std: Optional[float] = None, morph=None):
     """Frame-level AUROC of a video model (evaluate_video.py:171-176) without gathering the scores: the clip loop of
     `score_clips(per_frame=True)` - batches {'frames' [B,T,C,H,W], 'frame_labels' [B,T], ...} -, each batch's frame scores and
     labels going into a histogram on the device.  Returns (auroc, tie_bound, hist); ranks of a sharded evaluation call
-    `hist.all_reduce()` on a histogram they pass in instead of gathering score vectors."""
+    `hist.all_reduce()` on a histogram they pass in instead of gathering score vectors.
+    `reduce` (None = the mean squared error per frame of `score_seq_and_frames`, as before; the other arguments are then not used):
+    a `frame_scores` spec - "max", ("topk", fraction), ("quantile", q), ("rank", k) -; the frame scores are then those of
+    `frame_scores(model, frames, reduce, "mse", sigma, truncate, calibration, min_std, morph)`, reduced from the error maps on the
+    device, and go into the same histogram (which bins scores >= 0: a calibrated score below 0 is counted in `hist.rejected()`)."""
+    if reduce is not None:
+        metrics.reduce_spec(reduce, "frame_auroc")
+        metrics.morph_steps(morph)
+        _check_calibration(calibration, "frame_auroc", "mse", sigma, truncate, min_std)
     if hist is None:
         hist = metrics.ScoreHistogram(mantissa_bits, device)
     with torch.no_grad():
         for batch in loader:
             frames = batch["frames"].to(device)
             labels = torch.as_tensor(np.asarray(batch["frame_labels"])).to(device)
-            hist.accumulate(model.score_seq_and_frames(frames)["frame"], labels)
+            if reduce is None:
+                scores = model.score_seq_and_frames(frames)["frame"]
+            else:
+                scores, _ = frame_scores(model, frames, reduce, "mse", sigma, truncate, calibration, min_std, morph)
+            hist.accumulate(scores, labels)
     auroc, tie_bound = hist.auroc()
     return auroc, tie_bound, hist
 
