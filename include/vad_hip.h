@@ -913,6 +913,50 @@ enum { VAD_MORPH_ERODE = 0, VAD_MORPH_DILATE = 1, VAD_MORPH_OPEN = 2, VAD_MORPH_
 int vad_morph_maps(const float* maps, long long n, int h, int w, int op, int size_h, int size_w, float* out, void* stream);
 int vad_morph_tile(int size_h, int size_w, int op, int* tile_h, int* tile_w);
 
+/* ------------------------------------------------------------------ Temporal filters of anomaly maps (csrc/map_temporal.hip)
+ * The step a video line takes between the map and its threshold: every pixel filtered over the last k frames of its stream.  The
+ * minimum is a temporal erosion ("high in each of the last k frames": removes noise that differs from frame to frame, without any
+ * spatial blur), the maximum a temporal dilation (holds a detection across a dropped frame), the mean and the exponential average
+ * lower the noise floor of a fixed camera.  Per pixel, causal, windowed over the frames that exist.
+ *
+ * Frames of one stream are x[0], x[1], ...; frame 0 is the first after vad_tfilt_init, or the first of a clip.
+ *   VAD_TFILT_MIN / MAX  y[t] = minimum / maximum of x[max(0, t - k + 1) .. t], k in 1 .. VAD_TFILT_MAX_K: scipy.ndimage.
+ *                        minimum_filter1d / maximum_filter1d(x, size=k, axis=0, mode="nearest", origin=(k - 1) // 2).  The IEEE-754-2019
+ *                        minimum / maximum: a NaN makes exactly the k outputs whose window holds it NaN, -0 orders below +0, +-Inf are
+ *                        ordinary values.  Nothing is rounded; k = 1 is a copy.  They only compare, so they commute with a threshold.
+ *   VAD_TFILT_MEAN       y[t] = (float)(S / (double)c), c = min(t + 1, k), S the float64 sum of the window's values added oldest to
+ *                        newest, formed anew for every output; one rounding to float32 at the end.  Within 2^-24 |m| + 2^-150 +
+ *                        (c + 1) 2^-53 sum|x| / c of the exact mean m.  NaN / Inf follow the arithmetic.
+ *   VAD_TFILT_EMA        y[0] = x[0], y[t] = y[t-1] + a * (x[t] - y[t-1]) with a = alpha (float32, 0 < a < 1), every operation rounded
+ *                        to float32 on its own, no fused multiply-add: a finite constant stream stays constant to the bit (-0 becomes +0, an
+ *                        infinity NaN: x - y is then +0 or NaN).  A NaN stays in
+ *                        the state until the stream is initialised again - never a finite wrong value.  k is not used.
+ * vad_tfilt_maps: maps fp32 [b, t, h, w], contiguous, 4-byte aligned (b in 0 .. 2^20, t >= 0, any h, w >= 1 with h * w <=
+ * VAD_MAX_FRAME_PIXELS) are the next t frames of b streams; out [b, t, h, w] must not overlap maps.  state_or_null == NULL is the
+ * clip mode: every one of the b clips is a fresh stream, nothing is carried; it gives the bits a freshly initialised state gives.
+ * The result of a stream does not depend on how its frames are split over calls.
+ * State (caller-owned device memory, 16-byte aligned, vad_tfilt_state_bytes(b, h, w, op, k) bytes; 0 for arguments out of range, no
+ * device needed), per stream: a header of 16 words - frames seen (it stops at 2^32 - 1; only the mean's divisor and the EMA's first
+ * frame read it), ring position, a ticket word, 0, a magic word, op, k (0 for the EMA), h, w, zeros - and a ring of k - 1 planes of
+ * h * w floats padded to 16 bytes (EMA: one plane, y[t-1]).  A call of t frames writes its last min(t, k - 1) frames into the ring;
+ * nothing is shifted.  The counters are advanced on the device, so a captured call can be replayed.  vad_tfilt_init writes fresh
+ * state for b streams (asynchronous); one stream of a blob is re-initialised by a call with its address (state + s * bytes / b) and
+ * b = 1.  A blob that was made for another op, k, h or w is detected on the device: out is NaN and the blob is left alone.
+ * VAD_ERR_ARG for an unknown op, k outside 1 .. VAD_TFILT_MAX_K (min, max, mean), alpha not in (0, 1) or NaN (ema), b, t, h, w out
+ * of range, a NULL or misaligned pointer, out overlapping maps.  b == 0 or t == 0 returns VAD_OK and launches nothing.  One launch
+ * per call (per 65535 streams) on `stream`, one read and one write of the maps plus the ring, no workspace, no allocation, no host
+ * synchronisation: capturable in a graph.  16-byte loads and stores when h * w is a multiple of 4 and maps, out are 16-byte
+ * aligned; one pixel per work item otherwise.
+ * vad_tfilt_plan: the threads of a work-group and the pixels of a work item on the 16-byte path - a stream of more than threads *
+ * vector_pixels pixels has more than one work-group on either path. */
+#define VAD_TFILT_MAX_K 16
+enum { VAD_TFILT_MIN = 0, VAD_TFILT_MAX = 1, VAD_TFILT_MEAN = 2, VAD_TFILT_EMA = 3 };
+size_t vad_tfilt_state_bytes(long long b, int h, int w, int op, int k);
+int vad_tfilt_init(void* state, long long b, int h, int w, int op, int k, void* stream);
+int vad_tfilt_maps(const float* maps, long long b, int t, int h, int w, int op, int k, float alpha, void* state_or_null, float* out,
+                   void* stream);
+int vad_tfilt_plan(int* threads, int* vector_pixels);
+
 /* ------------------------------------------------------------------ Defect regions of an anomaly map (csrc/map_regions.hip)
  * What turns a map and an operating threshold into detections: the connected regions of {v >= threshold} of every frame, as a
  * compact table - where they are, how large, how strong.  The maps stay on the device; the table is what leaves it.

@@ -16,7 +16,7 @@ PKG_DIR = Path(__file__).resolve().parent
 REPO_DIR = PKG_DIR.parent
 CSRC = PKG_DIR / "csrc"
 LIB_PATH = Path(os.environ.get("VAD_LIB", PKG_DIR / "libvad_hip.so"))
-SOURCES = ["conv_mfma.hip", "conv_wino.hip", "dec4_fused.hip", "tail.hip", "wide_io.hip", "state_io.hip", "resize_u8.hip", "frame_gather.hip", "score_hist.hip", "region_overlap.hip", "map_regions.hip", "map_match.hip", "map_events.hip", "map_track.hip", "map_smooth.hip", "map_topk.hip", "map_morph.hip", "map_stats.hip", "ssim.hip", "train_ops.hip", "wgrad.hip", "train_step.hip", "train_step_img.hip", "vad_api.hip", "pack.cpp"]
+SOURCES = ["conv_mfma.hip", "conv_wino.hip", "dec4_fused.hip", "tail.hip", "wide_io.hip", "state_io.hip", "resize_u8.hip", "frame_gather.hip", "score_hist.hip", "region_overlap.hip", "map_regions.hip", "map_match.hip", "map_events.hip", "map_track.hip", "map_smooth.hip", "map_topk.hip", "map_morph.hip", "map_temporal.hip", "map_stats.hip", "ssim.hip", "train_ops.hip", "wgrad.hip", "train_step.hip", "train_step_img.hip", "vad_api.hip", "pack.cpp"]
 
 VAD_OK = 0
 ABI_VERSION = 3
@@ -63,6 +63,9 @@ TRACK_NO_RECORD = 0xFFFFFFFF   # slot plane: a pixel of an open event behind the
 TOPK_MAX_RANKS = 8        # VAD_TOPK_MAX_RANKS: most ranks of one vad_map_topk call
 MORPH_MAX_SIZE = 31       # VAD_MORPH_MAX_SIZE: largest side of the structuring element of vad_morph_maps
 MORPH_OPS = {"erode": 0, "dilate": 1, "open": 2, "close": 3}   # VAD_MORPH_*
+TFILT_MAX_K = 16          # VAD_TFILT_MAX_K: longest window of vad_tfilt_maps
+TFILT_OPS = {"min": 0, "max": 1, "mean": 2, "ema": 3}   # VAD_TFILT_*
+TFILT_HEADER_WORDS = 16   # per stream of a temporal filter's state: frames seen, ring position, ticket, 0, magic, op, k, h, w, zeros
 SMOOTH_TILE = (32, 64)    # csrc/map_smooth.hip SM_TH x SM_TW: the output tile of one work-group (vad_smooth_tile reports the library's)
 MAX_FRAME_PIXELS = 2 ** 23 - 1    # VAD_MAX_FRAME_PIXELS: largest H * W (pixel indices are 24-bit multiply operands inside the kernels)
 FRAME_RULE = f"H and W must be multiples of 16 with H * W <= {MAX_FRAME_PIXELS}"
@@ -91,8 +94,9 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     # map_smooth.hip: every product and sum of the smoothing rounds on its own, so numpy float32 restates it bit for bit
     # map_stats.hip: the float64 sums of the per-pixel statistics and the fp32 z-score likewise (tests/map_stats_ref.py)
     # map_match.hip: the fraction tests are one double multiply and one compare (tests/match_ref.py)
+    # map_temporal.hip: the exponential average is a subtraction, a product and a sum, each rounded (tests/map_temporal_ref.py)
     extra = {"pack.cpp": ["-ffp-contract=off"], "map_smooth.hip": ["-ffp-contract=off"], "map_stats.hip": ["-ffp-contract=off"],
-             "map_match.hip": ["-ffp-contract=off"]}
+             "map_match.hip": ["-ffp-contract=off"], "map_temporal.hip": ["-ffp-contract=off"]}
 
     def compile_one(src: Path) -> Path:
         obj = objdir / (src.name + ".o")
@@ -319,6 +323,11 @@ SIGNATURES = {
     # grey morphology of anomaly maps: erode, dilate, open, close (csrc/map_morph.hip)
     "vad_morph_maps": (_i, [_vp, _ll, _i, _i, _i, _i, _i, _vp, _vp]),
     "vad_morph_tile": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
+    # temporal filters of anomaly maps: causal min, max, mean over the last k frames, exponential average (csrc/map_temporal.hip)
+    "vad_tfilt_state_bytes": (_sz, [_ll, _i, _i, _i, _i]),
+    "vad_tfilt_init": (_i, [_vp, _ll, _i, _i, _i, _i, _vp]),
+    "vad_tfilt_maps": (_i, [_vp, _ll, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "vad_tfilt_plan": (_i, [C.POINTER(_i), C.POINTER(_i)]),
     # defect regions of an anomaly map: boxes, areas, peaks (csrc/map_regions.hip)
     "vad_regions_workspace_bytes": (_sz, [_ll, _i, _i, _i]),
     "vad_detect_regions": (_i, [_vp, _ll, _i, _i, _f, _i, C.c_uint, _i, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -31,6 +31,9 @@ sixteen counters per frame into the report a line is accepted on.
 Across all of them sits the calibration: `MapStatistics` (csrc/map_stats.hip) holds the per-pixel mean and standard deviation of the
 map over normal frames and turns a map into its z-score, which is then smoothed-and-ranked, thresholded and labelled like a raw map.
 
+Between the frames of a clip or a live stream sit `temporal_maps` / `TemporalFilter` (csrc/map_temporal.hip): every pixel filtered
+over the last k frames - causal minimum, maximum, mean, exponential average - before the threshold.
+
 At the end of the chain, where a map becomes ONE number per frame, sit `map_topk` and `reduce_maps` (csrc/map_topk.hip): the k-th
 largest pixel and the mean of the k largest, the robust frame scores between the mean of the map and its maximum.
 """
@@ -988,6 +991,215 @@ def apply_morph(maps: torch.Tensor, steps) -> torch.Tensor:
             bufs.append(morph_maps(maps, op, size, out=bufs[-2]))
         maps = bufs[-1]
     return maps
+
+
+# ====================================================================== temporal filters of anomaly maps
+# Every pixel filtered over the last k frames of its stream, between the calibration / morphology and the
+# threshold: the minimum is a temporal erosion - "high in each of the last k frames", which removes noise that differs from frame
+# to frame without any spatial blur -, the maximum holds a detection across a dropped frame, the mean and the exponential average
+# lower the noise floor of a fixed camera.  Causal, windowed over the frames that exist; `vad_tfilt_maps`, csrc/map_temporal.hip.
+TEMPORAL_MAX_K = hip.TFILT_MAX_K
+TEMPORAL_OPS = tuple(hip.TFILT_OPS)
+TEMPORAL_MAX_STEPS = 4
+
+
+def _temporal_op(op, what: str) -> str:
+    if not isinstance(op, str) or op not in hip.TFILT_OPS:
+        raise hip.VadError(f"{what}: op must be one of {TEMPORAL_OPS}, got {op!r}")
+    return op
+
+
+def _temporal_param(op: str, v, what: str):
+    """k in 1..16 for "min" / "max" / "mean" -> int; alpha for "ema" -> the float32 value the kernel multiplies with, 0 < alpha < 1."""
+    if op == "ema":
+        _check_number(v, "alpha", what, lambda a: 0.0 < float(np.float32(a)) < 1.0, "a number with 0 < float32(alpha) < 1")   # false for NaN
+        return float(np.float32(v))
+    return _check_int(v, "k", what, 1, TEMPORAL_MAX_K)
+
+
+def temporal_steps(spec) -> Tuple[Tuple[str, object], ...]:
+    """What the `temporal=` arguments of the scoring entry points and `TemporalFilter` take, normalised to a tuple of steps: None ->
+    (), one step `("min", 3)` / `("max", k)` / `("mean", k)` (k in 1..16) / `("ema", alpha)` (0 < float32(alpha) < 1), or a list of at
+    most four steps that run in order: `[("min", 3), ("max", 3)]` is a temporal opening.  `VadError` for anything else."""
+    what = "temporal_steps"
+    if spec is None:
+        return ()
+    if isinstance(spec, tuple) and len(spec) == 2 and isinstance(spec[0], str):
+        spec = [spec]
+    if not isinstance(spec, list):
+        raise hip.VadError(f"{what}: a spec is None, one step (op, k) / ('ema', alpha) or a list of steps, got {spec!r}")
+    if not 1 <= len(spec) <= TEMPORAL_MAX_STEPS:
+        raise hip.VadError(f"{what}: a list holds 1..{TEMPORAL_MAX_STEPS} steps, got {len(spec)}")
+    steps = []
+    for step in spec:
+        if not isinstance(step, (tuple, list)) or len(step) != 2:
+            raise hip.VadError(f"{what}: a step is (op, k) or ('ema', alpha), got {step!r}")
+        op = _temporal_op(step[0], what)
+        steps.append((op, _temporal_param(op, step[1], what)))
+    return tuple(steps)
+
+
+def _temporal_frames(maps, what: str) -> Tuple[int, int, int, int]:
+    """maps [B,T,H,W] or [B,T,1,H,W], float32, on the GPU, contiguous -> (B, T, H, W)."""
+    _check_maps(maps, what, "the filter runs on the device")
+    if not (maps.dim() == 4 or (maps.dim() == 5 and maps.shape[2] == 1)):
+        raise hip.VadError(f"{what}: maps must be [B,T,H,W] or [B,T,1,H,W] - T consecutive frames of B streams -, got {tuple(maps.shape)}")
+    if not maps.is_contiguous():
+        raise hip.VadError(f"{what}: maps must be contiguous (got strides {tuple(maps.stride())} for {tuple(maps.shape)}); it is not copied silently")
+    b, t, h, w = int(maps.shape[0]), int(maps.shape[1]), int(maps.shape[-2]), int(maps.shape[-1])
+    if h < 1 or w < 1 or h * w > hip.MAX_FRAME_PIXELS:
+        raise hip.VadError(f"{what}: frames of {h} x {w} are out of range (H, W >= 1 and H * W <= {hip.MAX_FRAME_PIXELS})")
+    if b > 2 ** 20:
+        raise hip.VadError(f"{what}: {b} streams are out of range (B <= 2^20)")
+    return b, t, h, w
+
+
+def _temporal_out(maps, out, what: str):
+    if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(maps.shape) or out.dtype != torch.float32
+                            or out.device != maps.device or not out.is_contiguous()):
+        raise hip.VadError(f"{what}: out must be a contiguous float32 tensor {tuple(maps.shape)} on {maps.device}")
+    return torch.empty_like(maps) if out is None else out
+
+
+def _tfilt(maps, b, t, h, w, op: str, param, state_ptr, out) -> None:
+    k, alpha = (0, param) if op == "ema" else (param, 0.0)
+    if b > 0 and t > 0:
+        hip.check(hip.lib().vad_tfilt_maps(maps.data_ptr(), b, t, h, w, hip.TFILT_OPS[op], k, alpha, state_ptr, out.data_ptr(), hip.current_stream()),
+                  "vad_tfilt_maps")
+        _count("tfilt_maps")
+
+
+def temporal_maps(maps: torch.Tensor, op: str, k_or_alpha, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One temporal filter over the T frames of every clip of `maps` (`[B,T,H,W]` or `[B,T,1,H,W]`, float32 GPU tensor, contiguous),
+    every clip a fresh stream (`vad_tfilt_maps` without a state, csrc/map_temporal.hip).  Per pixel, causal, over the frames that exist:
+    `op` "min" / "max": `y[t]` = minimum / maximum of `x[max(0, t - k + 1) .. t]` - `scipy.ndimage.minimum_filter1d` /
+    `maximum_filter1d(x, size=k, axis=1, mode="nearest", origin=(k - 1) // 2)` -, nothing rounded, NaN in exactly the k outputs whose
+    window holds one, -0 below +0; they commute with a threshold.  "mean": the float64 sum of the window added oldest to newest,
+    divided by the frames in it, rounded once.  "ema": `y[0] = x[0]`, `y[t] = y[t-1] + a * (x[t] - y[t-1])` in float32 without a fused
+    multiply-add, `a = float32(alpha)`, so a finite constant stream stays constant to the bit; a NaN stays in the average to the end of
+    the clip.  tests/map_temporal_ref.py restates all
+    four to the bit.  k in 1..16 (1 is a copy), 0 < alpha < 1.  Returns a new tensor, or `out` (same shape, not overlapping
+    `maps`).  One launch; asynchronous on the current stream."""
+    what = "temporal_maps"
+    if not isinstance(maps, torch.Tensor):
+        raise hip.VadError(f"{what}: maps must be a torch tensor")
+    op = _temporal_op(op, what)
+    param = _temporal_param(op, k_or_alpha, what)
+    b, t, h, w = _temporal_frames(maps, what)
+    with torch.cuda.device(maps.device):
+        out = _temporal_out(maps, out, what)
+        _tfilt(maps, b, t, h, w, op, param, None, out)
+    return out
+
+
+def apply_temporal(maps: torch.Tensor, steps) -> torch.Tensor:
+    """`maps` (clips, as `temporal_maps` takes them) through the steps of `temporal_steps(...)`, one launch per step.  One step returns
+    a new tensor; a list ping-pongs two buffers of its own, so `maps` is never written.  No steps: `maps` itself."""
+    bufs = []
+    for op, param in steps:
+        if len(bufs) < 2:
+            bufs.append(temporal_maps(maps, op, param))
+        else:
+            bufs.append(temporal_maps(maps, op, param, out=bufs[-2]))
+        maps = bufs[-1]
+    return maps
+
+
+class TemporalFilter:
+    """The temporal filters of `temporal_steps(steps)` over B live streams, carried across calls on the device (DESIGN.md section
+    4.23): `update(maps)` takes the next T >= 0 maps of every stream and returns them filtered - the bits `apply_temporal` gives on the
+    whole stream, for any split of its frames over calls.  One state blob per step (a ring of the k - 1 newest planes of its input;
+    one plane for "ema") and one launch per step; the frame counters live in the blobs and are advanced by the kernel, so a captured
+    `update` can be replayed.  An "ema" step keeps a NaN it has met until the stream is reset.  No CPU fallback."""
+
+    def __init__(self, streams: int, h: int, w: int, steps, device=None):
+        what = "TemporalFilter"
+        self.steps = temporal_steps(steps)
+        if not self.steps:
+            raise hip.VadError(f"{what}: steps must hold at least one step, got {steps!r}")
+        self.streams = _check_int(streams, "streams", what, 0, 2 ** 20)
+        self.h, self.w = _check_int(h, "h", what, 1, hip.MAX_FRAME_PIXELS), _check_int(w, "w", what, 1, hip.MAX_FRAME_PIXELS)
+        if self.h * self.w > hip.MAX_FRAME_PIXELS:
+            raise hip.VadError(f"{what}: frames of {h} x {w} are out of range (h * w <= {hip.MAX_FRAME_PIXELS})")
+        dev = torch.device("cuda" if device is None else device)
+        if dev.type != "cuda":
+            raise hip.VadError(f"{what}: device ({dev}) must be a GPU (the filter runs on the device; there is no CPU fallback)")
+        self.device = dev
+        l = hip.lib()
+        self.states = []
+        for op, param in self.steps:
+            size = l.vad_tfilt_state_bytes(self.streams, self.h, self.w, hip.TFILT_OPS[op], self._k(op, param))
+            self.states.append(torch.empty(size // 4, dtype=torch.int32, device=dev))
+        self.reset()
+
+    @staticmethod
+    def _k(op: str, param) -> int:
+        return 0 if op == "ema" else param
+
+    def _stream_words(self, i: int) -> int:
+        return self.states[i].numel() // max(self.streams, 1)
+
+    def reset(self, streams=None) -> None:
+        """Fresh state (asynchronous): of every stream, or of the streams in `streams` (indices) - their next frame is frame 0."""
+        l = hip.lib()
+        which = [None] if streams is None else [int(s) for s in streams]
+        for s in which:
+            if s is not None and not 0 <= s < self.streams:
+                raise hip.VadError(f"TemporalFilter.reset: stream {s} is out of range (0..{self.streams - 1})")
+        if not self.streams:
+            return
+        with torch.cuda.device(self.device):
+            for i, (op, param) in enumerate(self.steps):
+                for s in which:
+                    at, n = (0, self.streams) if s is None else (4 * s * self._stream_words(i), 1)
+                    hip.check(l.vad_tfilt_init(self.states[i].data_ptr() + at, n, self.h, self.w, hip.TFILT_OPS[op], self._k(op, param),
+                                               hip.current_stream()), "vad_tfilt_init")
+
+    def frames_seen(self) -> torch.Tensor:
+        """int64 [B] on the device: the frames every stream has taken in since its last reset (it stops at 2^32 - 1)."""
+        if not self.streams:
+            return torch.zeros(0, dtype=torch.int64, device=self.device)
+        return self.states[0].view(self.streams, -1)[:, 0].to(torch.int64) & 0xFFFFFFFF
+
+    def state_dict(self) -> dict:
+        return {"steps": [list(s) for s in self.steps], "streams": self.streams, "h": self.h, "w": self.w,
+                "states": [s.cpu().numpy().copy() for s in self.states]}
+
+    def load_state_dict(self, state: dict) -> "TemporalFilter":
+        what = "TemporalFilter.load_state_dict"
+        got = (tuple(tuple(s) for s in state["steps"]), int(state["streams"]), int(state["h"]), int(state["w"]))
+        if got != (self.steps, self.streams, self.h, self.w):
+            raise hip.VadError(f"{what}: the state is of steps {got[0]} on {got[1]} streams of {got[2]} x {got[3]}, this filter of "
+                               f"{self.steps} on {self.streams} streams of {self.h} x {self.w}")
+        blobs = [np.asarray(b, dtype=np.int32) for b in state["states"]]
+        if [b.shape for b in blobs] != [tuple(s.shape) for s in self.states]:
+            raise hip.VadError(f"{what}: the state's blobs do not have the sizes of this filter's")
+        for mine, b in zip(self.states, blobs):
+            mine.copy_(torch.from_numpy(b))
+        return self
+
+    def update(self, maps: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """maps: float32 GPU tensor `[B,T,H,W]` or `[B,T,1,H,W]`, the next T frames of the B streams -> the filtered maps, same shape.
+        The library call allocates nothing; this method makes one output tensor per step for the first two steps of a list
+        (`torch.empty_like`: the caching allocator, or the graph's pool under capture).  Pass `out` (same shape, float32,
+        contiguous, not overlapping `maps`) to receive the last step's result in a tensor of one's own - a one-step filter then
+        allocates nothing."""
+        what = "TemporalFilter.update"
+        b, t, h, w = _temporal_frames(maps, what)
+        if out is not None:
+            _temporal_out(maps, out, what)
+        if (b, h, w) != (self.streams, self.h, self.w):
+            raise hip.VadError(f"{what}: maps {tuple(maps.shape)} do not match the filter's state: {self.streams} streams of {self.h} x {self.w}")
+        if maps.device != self.states[0].device:
+            raise hip.VadError(f"{what}: maps ({maps.device}) and the filter's state ({self.states[0].device}) are on different devices")
+        with torch.cuda.device(maps.device):
+            bufs = []
+            for i, (op, param) in enumerate(self.steps):
+                step_out = out if out is not None and i == len(self.steps) - 1 else torch.empty_like(maps) if len(bufs) < 2 else bufs[-2]
+                _tfilt(maps, b, t, h, w, op, param, self.states[i].data_ptr(), step_out)
+                bufs.append(step_out)
+                maps = step_out
+        return maps
 
 
 # ====================================================================== robust frame scores: top-k means and quantiles of maps

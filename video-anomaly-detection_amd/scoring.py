@@ -98,23 +98,24 @@ def compute_auroc_smoothed(model, test_loader: Iterable[dict], device, sigma: fl
 
 
 def frame_scores(model, images, reduce, map: str = "mse", sigma=None, truncate: float = 4.0, calibration=None,
-                 min_std: Optional[float] = None, morph=None):
+                 min_std: Optional[float] = None, morph=None, temporal=None):
     """Robust frame scores of one batch: the model's anomaly maps - the chain of `localize`: `map`, `sigma`,
     `truncate`, `calibration`, `min_std`, `morph` as there - reduced per frame by `metrics.reduce_maps(maps, reduce)`: `reduce` =
     "max", ("topk", fraction) - the mean of the top fraction of the pixels -, ("quantile", q) or ("rank", k).  `images`: `[B,C,H,W]`
     for the image model, `[B,T,C,H,W]` clips for the video model (map "mse" only).  Per batch ONE scoring call, the optional
     smoothing / calibration / morphology calls and ONE `metrics.map_topk` call; nothing is read by the host.  Returns (scores, maps):
     `[B]` / `[B,T]` float32 on the device, and the maps they were reduced from (`[B,1,H,W]` / `[B,T,1,H,W]`), so that a stream which
-    also localises does not score twice."""
+    also localises does not score twice.  `temporal` as in `pixel_auroc` (clips only; last in the chain, before the reduction)."""
     what = "frame_scores"
     _check_map_name(map, what)
     metrics.reduce_spec(reduce, what)
     morph = metrics.morph_steps(morph)
+    temporal = metrics.temporal_steps(temporal)
     if images.dim() == 5 and map != "mse":
         _refuse_clips_on(map, what, "scored")
     min_std = _check_calibration(calibration, what, map, sigma, truncate, min_std)
     with torch.no_grad():
-        maps = _anomaly_maps(model, images, map, sigma, truncate, calibration, min_std, morph)
+        maps = _anomaly_maps(model, images, map, sigma, truncate, calibration, min_std, morph, temporal, what)
         return metrics.reduce_maps(maps, reduce).reshape(maps.shape[:-3]), maps
 
 
@@ -426,10 +427,14 @@ def score_stream(model, seed: int, n_frames: int, chunk: int = 512, h: int = 256
 
 
 # ------------------------------------------------------------------------------ ranking metrics on the device
-def _anomaly_maps(model, images, map: str, sigma, truncate, calibration=None, min_std=None, morph=()):
+def _anomaly_maps(model, images, map: str, sigma, truncate, calibration=None, min_std=None, morph=(), temporal=(), what: str = "scoring"):
     """The batch's anomaly map [B,1,H,W] of the pixel metrics: the error map or the SSIM map, through `metrics.smooth_maps` when a
     sigma is given, then - with a `calibration` - turned into its z-score in place (the map is this call's own), then through the
-    steps of `morph` (`metrics.morph_steps`), in z-score units when calibrated."""
+    steps of `morph` (`metrics.morph_steps`), in z-score units when calibrated, then - clips [B,T,C,H,W] only, every clip a fresh
+    stream - through the steps of `temporal` (`metrics.temporal_steps`): the order is sigma, calibration, morph, temporal."""
+    if temporal and images.dim() != 5:
+        raise hip.VadError(f"{what}: temporal= filters the consecutive frames of clips [B,T,C,H,W]; the frames of an image batch "
+                           f"{tuple(images.shape)} are not consecutive (a live camera: localize_stream(temporal_filter=))")
     if map == "mse":
         values = model.score_all(images)["errmap"]
     else:
@@ -440,6 +445,8 @@ def _anomaly_maps(model, images, map: str, sigma, truncate, calibration=None, mi
         values = calibration.normalize(values, min_std, out=values)
     if morph:
         values = metrics.apply_morph(values, morph)
+    if temporal:
+        values = metrics.apply_temporal(values, temporal)
     return values
 
 
@@ -453,11 +460,21 @@ def _refuse_clips_on(map, what: str, verb: str) -> None:
     raise hip.VadError(f"{what}: clips [B,T,C,H,W] are {verb} on the error map only (map='mse'), got {map!r}")
 
 
-def _masked_maps(model, batch: dict, device, map: str, sigma, truncate, calibration, min_std, morph, key: str = "image"):
+def _masked_maps(model, batch: dict, device, map: str, sigma, truncate, calibration, min_std, morph, key: str = "image", temporal=(),
+                 what: str = "scoring"):
     """One batch of the mask metrics: (`_anomaly_maps` of batch[key], batch['mask']), both on the device."""
     images = batch[key].to(device)
     masks = torch.as_tensor(batch["mask"]).to(device)
-    return _anomaly_maps(model, images, map, sigma, truncate, calibration, min_std, morph), masks
+    return _anomaly_maps(model, images, map, sigma, truncate, calibration, min_std, morph, temporal, what), masks
+
+
+def _clip_key(batch: dict, temporal, map, what: str) -> str:
+    """The key of a mask metric's frames: 'image', or - with `temporal=` - the 'frames' [B,T,C,H,W] of a video batch (map "mse")."""
+    if temporal and "frames" in batch and "image" not in batch:
+        if map != "mse":
+            _refuse_clips_on(map, what, "filtered")
+        return "frames"
+    return "image"
 
 
 def _map_meta(map: str, sigma, truncate) -> dict:
@@ -509,7 +526,7 @@ def calibrate(model, loader: Iterable[dict], device, map: str = "mse", sigma=Non
 
 
 def pixel_auroc(model, loader: Iterable[dict], device, map: str = "mse", mantissa_bits: int = 11, hist=None, sigma=None,
-                truncate: float = 4.0, calibration=None, min_std: Optional[float] = None, morph=None):
+                truncate: float = 4.0, calibration=None, min_std: Optional[float] = None, morph=None, temporal=None):
     """Pixel-level AUROC of an image model's anomaly map against the ground-truth masks - the localisation metric of MVTec-style
     datasets; the reference loads `sample['mask']` and only plots it beside the map (evaluate.py:142-171).  Batches are
     {'image', 'mask', ...} as `MVTecDataset` yields them (utils/dataset.py:150-156): mask float `[B,1,H,W]` (ToTensor: a pixel is
@@ -531,21 +548,30 @@ def pixel_auroc(model, loader: Iterable[dict], device, map: str = "mse", mantiss
     `morph` (None = no morphology, as before): a `metrics.morph_steps` spec - one step `("open", 3)` / `("close", (3, 5))` or a list of
     at most four, e.g. `[("open", 2), ("close", 5)]` - applied with `metrics.morph_maps` after the smoothing and the calibration (in
     z-score units when calibrated) and before the histogram.  `calibrate` takes none: statistics are those of the un-morphed map.
-    Grey morphology commutes with a threshold, so a threshold read from this histogram is the one `localize(morph=...)` takes."""
+    Grey morphology commutes with a threshold, so a threshold read from this histogram is the one `localize(morph=...)` takes.
+    `temporal` (None = no temporal filter, as before): a `metrics.temporal_steps` spec - one step `("min", k)` / `("max", k)` /
+    `("mean", k)` / `("ema", alpha)` or a list of at most four - for batches of CLIPS: {'frames' [B,T,C,H,W], 'mask' [B,T,1,H,W]} of the
+    video model (map "mse"; or 'image' holding such clips).  Every clip is a fresh stream; every pixel is filtered over the last k
+    frames of its clip with `metrics.temporal_maps`, LAST in the chain - sigma, calibration, morph, temporal - and before the
+    histogram.  An image batch [B,C,H,W] with it is refused with `VadError`: its frames are not consecutive.  `calibrate` takes
+    none: a calibration is gathered on unfiltered maps."""
     _check_map_name(map, "pixel_auroc")
     morph = metrics.morph_steps(morph)
+    temporal = metrics.temporal_steps(temporal)
     min_std = _check_calibration(calibration, "pixel_auroc", map, sigma, truncate, min_std)
     if hist is None:
         hist = metrics.ScoreHistogram(mantissa_bits, device)
     with torch.no_grad():
         for batch in loader:
-            hist.accumulate(*_masked_maps(model, batch, device, map, sigma, truncate, calibration, min_std, morph))
+            key = _clip_key(batch, temporal, map, "pixel_auroc")
+            hist.accumulate(*_masked_maps(model, batch, device, map, sigma, truncate, calibration, min_std, morph, key, temporal, "pixel_auroc"))
     auroc, tie_bound = hist.auroc()
     return auroc, tie_bound, hist
 
 
 def pixel_aupro(model, loader: Iterable[dict], device, map: str = "mse", fpr_limit: float = 0.3, mantissa_bits: int = 11, hist=None,
-                connectivity: int = 8, sigma=None, truncate: float = 4.0, calibration=None, min_std: Optional[float] = None, morph=None):
+                connectivity: int = 8, sigma=None, truncate: float = 4.0, calibration=None, min_std: Optional[float] = None, morph=None,
+                temporal=None):
     """Per-region overlap (AUPRO) of an image model's anomaly map against the ground-truth masks: every connected anomalous region
     of the masks weighs the same, and the curve is integrated up to a false-positive rate of `fpr_limit` - the localisation metric
     of the MVTec evaluation, where pixel AUROC is dominated by the large defects.  The loop of `pixel_auroc` (same batches, same
@@ -554,22 +580,27 @@ def pixel_aupro(model, loader: Iterable[dict], device, map: str = "mse", fpr_lim
     on the device; the only host read is the counters, once, at the end.  Returns (aupro, quant_bound, weight_bound, hist)
     (`metrics.aupro_from_counts`); pass `hist` to continue an earlier evaluation or to all-reduce before reading, in which case
     its own mantissa_bits and connectivity apply.  `hist.auroc()` is the pixel AUROC of the same evaluation.  `calibration`,
-    `min_std`, `morph` as in `pixel_auroc`."""
+    `min_std`, `morph`, `temporal` as in `pixel_auroc`."""
     _check_map_name(map, "pixel_aupro")
     morph = metrics.morph_steps(morph)
+    temporal = metrics.temporal_steps(temporal)
     min_std = _check_calibration(calibration, "pixel_aupro", map, sigma, truncate, min_std)
     if hist is None:
         hist = metrics.ProHistogram(mantissa_bits, device, connectivity)
     with torch.no_grad():
         for batch in loader:
-            hist.accumulate(*_masked_maps(model, batch, device, map, sigma, truncate, calibration, min_std, morph))
+            key = _clip_key(batch, temporal, map, "pixel_aupro")
+            maps, masks = _masked_maps(model, batch, device, map, sigma, truncate, calibration, min_std, morph, key, temporal, "pixel_aupro")
+            if temporal:                                                      # clips: every frame's regions on their own, [B*T,1,H,W]
+                maps, masks = maps.flatten(0, 1), masks.reshape(maps.shape[0] * maps.shape[1], *masks.shape[-3:])
+            hist.accumulate(maps, masks)
     aupro, quant_bound, weight_bound = hist.aupro(fpr_limit)
     return aupro, quant_bound, weight_bound, hist
 
 
 def detection_report(model, loader: Iterable[dict], device, threshold: float, map: str = "mse", sigma=None, truncate: float = 4.0,
                      calibration=None, min_std: Optional[float] = None, morph=(), connectivity: int = 8, min_area: int = 1,
-                     gt_fraction: float = 0.0, pred_fraction: float = 0.0, counts=None):
+                     gt_fraction: float = 0.0, pred_fraction: float = 0.0, counts=None, temporal=None):
     """What an operating point does against the ground-truth masks: how many of the labelled defects it finds, how many false
     alarms per frame it raises, which pixel IoU it reaches - the questions AUROC and AUPRO, which rank pixels over all thresholds and
     know nothing of `min_area` or of regions as units, do not answer.  The loop of `pixel_aupro`, over the same batches: {'image'
@@ -580,14 +611,19 @@ def detection_report(model, loader: Iterable[dict], device, threshold: float, ma
     `metrics.match_regions`, whose 16 counters per frame are summed on the device; no map or mask is copied to the host.
     `gt_fraction`, `pred_fraction` as in `metrics.match_regions`.  Returns (report dict of `metrics.report_from_counts`, the
     `metrics.DetectionCounts`); pass `counts` to continue an earlier evaluation or to all-reduce before reading
-    (`counts.all_reduce()`, then `counts.report()`) - counters gathered at another operating point are refused with `ValueError`."""
+    (`counts.all_reduce()`, then `counts.report()`) - counters gathered at another operating point are refused with `ValueError`.
+    `temporal` as in `pixel_auroc`: video batches only, every clip a fresh stream, after `morph` and before the threshold; it is part
+    of the operating point the counters are gathered at."""
     what = "detection_report"
     _check_map_name(map, what)
     morph = metrics.morph_steps(None if morph == () else morph)          # () = no morphology, like None elsewhere
+    temporal = metrics.temporal_steps(temporal)
     min_std = _check_calibration(calibration, what, map, sigma, truncate, min_std)
     params = metrics._match_params(what, threshold, connectivity, min_area, gt_fraction, pred_fraction)
     meta = dict(_map_meta(map, sigma, truncate), morph=tuple(morph), calibrated=calibration is not None,
                 min_std=None if calibration is None else float(min_std))
+    if temporal:
+        meta["temporal"] = tuple(temporal)
     if counts is None:
         counts = metrics.DetectionCounts(device)
     elif not isinstance(counts, metrics.DetectionCounts):
@@ -598,13 +634,14 @@ def detection_report(model, loader: Iterable[dict], device, threshold: float, ma
             video = "frames" in batch
             if video and map != "mse":
                 _refuse_clips_on(map, what, "reported")
-            maps, masks = _masked_maps(model, batch, device, map, sigma, truncate, calibration, min_std, morph, "frames" if video else "image")
+            maps, masks = _masked_maps(model, batch, device, map, sigma, truncate, calibration, min_std, morph, "frames" if video else "image",
+                                       temporal, what)
             counts.update(metrics.match_regions(maps, masks, threshold, connectivity, min_area, gt_fraction, pred_fraction, max_regions=1), meta)
     return counts.report(), counts
 
 
 def frame_auroc(model, loader: Iterable[dict], device, hist=None, mantissa_bits: int = 11, reduce=None, sigma=None, truncate: float = 4.0,
-                calibration=None, min_std: Optional[float] = None, morph=None):
+                calibration=None, min_std: Optional[float] = None, morph=None, temporal=None):
     """Frame-level AUROC of a video model (evaluate_video.py:171-176) without gathering the scores: the clip loop of
     `score_clips(per_frame=True)` - batches {'frames' [B,T,C,H,W], 'frame_labels' [B,T], ...} -, each batch's frame scores and
     labels going into a histogram on the device.  Returns (auroc, tie_bound, hist); ranks of a sharded evaluation call
@@ -612,7 +649,10 @@ def frame_auroc(model, loader: Iterable[dict], device, hist=None, mantissa_bits:
     `reduce` (None = the mean squared error per frame of `score_seq_and_frames`, as before; the other arguments are then not used):
     a `frame_scores` spec - "max", ("topk", fraction), ("quantile", q), ("rank", k) -; the frame scores are then those of
     `frame_scores(model, frames, reduce, "mse", sigma, truncate, calibration, min_std, morph)`, reduced from the error maps on the
-    device, and go into the same histogram (which bins scores >= 0: a calibrated score below 0 is counted in `hist.rejected()`)."""
+    device, and go into the same histogram (which bins scores >= 0: a calibrated score below 0 is counted in `hist.rejected()`).
+    `temporal` as in `frame_scores` (it filters maps, so it needs a `reduce`: `VadError` without one)."""
+    if metrics.temporal_steps(temporal) and reduce is None:
+        raise hip.VadError("frame_auroc: temporal= filters the error maps before they are reduced; pass a reduce (\"max\", (\"topk\", f), ...)")
     if reduce is not None:
         metrics.reduce_spec(reduce, "frame_auroc")
         metrics.morph_steps(morph)
@@ -626,7 +666,7 @@ def frame_auroc(model, loader: Iterable[dict], device, hist=None, mantissa_bits:
             if reduce is None:
                 scores = model.score_seq_and_frames(frames)["frame"]
             else:
-                scores, _ = frame_scores(model, frames, reduce, "mse", sigma, truncate, calibration, min_std, morph)
+                scores, _ = frame_scores(model, frames, reduce, "mse", sigma, truncate, calibration, min_std, morph, temporal)
             hist.accumulate(scores, labels)
     auroc, tie_bound = hist.auroc()
     return auroc, tie_bound, hist
@@ -658,27 +698,32 @@ def localize(model, images, threshold: float, map: str = "mse", sigma=None, trun
 
 def localize_events(model, images, threshold: float, map: str = "mse", sigma=None, truncate: float = 4.0, calibration=None,
                     min_std: Optional[float] = None, connectivity: int = 8, temporal: int = 9, min_duration: int = 1, min_volume: int = 1,
-                    max_events: int = 64, morph=None):
+                    max_events: int = 64, morph=None, temporal_filter=None):
     """`localize` with the event table: the model's anomaly maps and the events of `map >= threshold` in them - regions linked
     across consecutive frames (`metrics.detect_events`), so that a line alarms on what persists (`min_duration`) and not on one
     noisy map.  `images`: `[B,T,C,H,W]` clips for the video model (map "mse" only), every clip its own volume; `[N,C,H,W]` frames
     for the image model, the batch in order being N consecutive frames of one camera: one volume.  `map`, `sigma`, `truncate`,
     `calibration`, `min_std`, `morph` as in `localize`.  Per batch ONE scoring call, the optional smoothing and calibration calls and ONE
     `detect_events` call; nothing but the flag word is read by the host.  Returns (`metrics.Events`, maps): the table with the
-    leading shape `[B]` (video) or `()` (image), and the maps it was made from, `[B,T,1,H,W]` / `[N,1,H,W]`, still on the device."""
+    leading shape `[B]` (video) or `()` (image), and the maps it was made from, `[B,T,1,H,W]` / `[N,1,H,W]`, still on the device.
+    `temporal_filter`: the `temporal=` spec of `pixel_auroc` under another name - `temporal` is this entry point's link structure -:
+    clips only (an image batch is refused, although this entry point reads it as one volume: use `localize_stream(temporal_filter=)`
+    for a camera), every clip a fresh stream, after `morph` and before the threshold; the maps returned are the filtered maps.
+    `("min", 2)` in front of the labeller removes what differs from frame to frame."""
     _check_map_name(map, "localize_events")
     morph = metrics.morph_steps(morph)
+    temporal_filter = metrics.temporal_steps(temporal_filter)
     if images.dim() == 5 and map != "mse":
         _refuse_clips_on(map, "localize_events", "localised")
     min_std = _check_calibration(calibration, "localize_events", map, sigma, truncate, min_std)
     with torch.no_grad():
-        maps = _anomaly_maps(model, images, map, sigma, truncate, calibration, min_std, morph)
+        maps = _anomaly_maps(model, images, map, sigma, truncate, calibration, min_std, morph, temporal_filter, "localize_events")
         volumes = maps if maps.dim() == 5 else maps[:, 0]                 # [B,T,1,H,W], or the image batch as one clip [N,H,W]
         return metrics.detect_events(volumes, threshold, connectivity, temporal, min_duration, min_volume, max_events), maps
 
 
 def localize_stream(model, frames, tracker, state=None, sigma=None, truncate: float = 4.0, calibration=None, min_std: Optional[float] = None,
-                    morph=None):
+                    morph=None, temporal_filter=None):
     """One step of a live stream with events carried between calls (`metrics.EventTracker`): the newest
     frames are scored, their error maps smoothed and calibrated as in `localize_events`, and handed to `tracker.update`.
     Video model: `frames` `[B,T,C,H,W]` (or the uint8 layouts `score_stateful` takes) are the next T frames of B streams; ONE
@@ -687,8 +732,14 @@ def localize_stream(model, frames, tracker, state=None, sigma=None, truncate: fl
     Returns (`metrics.TrackUpdate`, maps, state): the events that closed in this step and the causal alarms of its frames, the maps
     they were made from (`[B,T,1,H,W]` / `[B,1,H,W]`, on the device), and the scoring state for the next call.  The tracker's
     threshold applies to the maps as made here: with a `calibration` it is a z-score.  `morph` as in `localize`: every frame is
-    morphed on its own, so the result does not depend on how the frames are split over calls."""
+    morphed on its own, so the result does not depend on how the frames are split over calls.
+    `temporal_filter` (None = none, as before): a `metrics.TemporalFilter` for B streams of these maps, which carries the last frames
+    between calls - the maps go through `temporal_filter.update` after the morphology and before the tracker, so tracker and filter
+    see what `localize_events(temporal=)` sees on the whole stream, however its frames are split over calls.  Both models: the image
+    model's `[B,1,H,W]` is one new frame of B cameras.  The maps returned are the filtered maps.  Reset it with the tracker."""
     morph = metrics.morph_steps(morph)
+    if temporal_filter is not None and not isinstance(temporal_filter, metrics.TemporalFilter):
+        raise hip.VadError(f"localize_stream: temporal_filter must be a metrics.TemporalFilter, got {type(temporal_filter).__name__}")
     if not isinstance(tracker, metrics.EventTracker):
         raise hip.VadError(f"localize_stream: tracker must be a metrics.EventTracker, got {type(tracker).__name__}")
     min_std = _check_calibration(calibration, "localize_stream", "mse", sigma, truncate, min_std)
@@ -707,5 +758,7 @@ def localize_stream(model, frames, tracker, state=None, sigma=None, truncate: fl
             maps = calibration.normalize(maps, min_std, out=maps)
         if morph:
             maps = metrics.apply_morph(maps, morph)
+        if temporal_filter is not None:                                   # [B,T,1,H,W] as it stands; [B,1,H,W] = B streams x 1 frame
+            maps = temporal_filter.update(maps.contiguous())
         update = tracker.update(maps if video else maps[:, 0])
     return update, maps, state
