@@ -1167,6 +1167,49 @@ int vad_track_flush(long long b, int h, int w, unsigned min_duration, unsigned m
                     uint32_t* closed /* [b, max_closed, 20] */, uint32_t* counts /* [b, 6] */, void* ws, size_t ws_bytes, void* stream);
 int vad_track_plan(int* label_round, int* pixel_round, int* scan_round, int* table_round, int* threads);
 
+/* ------------------------------------------------------------------ Per-frame tracks of anomaly events (csrc/map_event_tracks.hip)
+ * A box per event and frame, where the event tables above hold the union box of an event's whole life.  A CROSS-SECTION is the set
+ * of one event's pixels in one frame; it is one record of VAD_REGION_WORDS = 12 uint32 words in the layout of vad_detect_regions,
+ * so whatever reads a region record reads it:
+ *     word 0      the smallest y * w + x of the event's pixels in this frame
+ *     word 1      area: the event's pixels in this frame
+ *     words 2-5   x0, y0, x1, y1 of their bounding box, inclusive
+ *     word 6      peak: the float bits of the maximum over these pixels
+ *     word 7      peak index: the smallest y * w + x among the pixels that hold the maximum
+ *     words 8-9   uint64 sum of x over these pixels             (centroid = sum / area, exactly)
+ *     words 10-11 uint64 sum of y
+ * Values compare through the order-preserving key of their bits, so -0.0 < +0.0.  A cross-section may be disconnected inside its
+ * frame - its pieces may join through other frames - and is still ONE record; a frame in which the event has no pixel is an
+ * all-zero record.
+ *
+ * vad_event_tracks (a clip): maps fp32 [b, t, h, w] and labels int32 [b, t, h, w], records uint32 [b, max_events, VAD_EVENT_WORDS]
+ * and counts uint32 [b, 4] as ONE vad_detect_events call took and wrote them (labels: 0 or 1 + root; the kept records of a clip are
+ * its first min(counts[.][0], max_events), their roots ascend), with that call's limits on b, t, h, w and max_events in 1 .. 65536.
+ * tracks uint32 [b, max_events, t, 12], 16-byte aligned, event-major - one event's track is 48 * t contiguous bytes -, at most
+ * b * max_events * t = 2^26 records (3 GiB).  Record (e, f) is the cross-section of kept event e in frame f; the records of the
+ * slots behind the kept ones are all-zero; pixels of events that a filter dropped, or that have no record because the table was
+ * truncated, contribute nothing.  A pixel's record is found by its root, once per distinct root of a wave.  Three launches.
+ * vad_event_tracks_plan reports the pixels of a clip one grid round of the reduction covers and the threads of a work-group.
+ *
+ * vad_track_boxes (a live stream): after vad_track_events the state holds the open table and the slot plane of the newest frame.
+ * maps_newest fp32: the newest map [h, w] of stream s begins at maps_newest + s * frame_stride (frame_stride in floats, >= h * w:
+ * the last frame of a [b, t, h, w] call is used in place with maps + (t - 1) * h * w and frame_stride t * h * w); b, h, w, max_open
+ * with the limits of vad_track_events.  boxes uint32 [b, max_open, 12], 16-byte aligned: record r is the cross-section in the
+ * newest frame of the open event in slot r - its word 0 is that event's handle, word 3 of its open record -, all-zero behind the
+ * open ones; pixels of a lost event (0xffffffff in the plane) contribute nothing.  The header's magic, h, w and max_open are
+ * compared ON THE DEVICE: with any other blob every record is zero and nothing of the blob beyond its header is read.
+ *
+ * Integer atomics, min and max only: both tables are the same words for any batching, launch order or tiling.  No workspace, no
+ * flag word (there is no union-find walk), no host read.  VAD_ERR_ARG for a NULL or misaligned pointer, b, t, h, w out of range,
+ * max_events or max_open out of range, more than 2^26 records, a frame_stride below h * w.  b == 0 launches nothing.  Every launch
+ * is asynchronous on `stream`; nothing is allocated, the host never waits, the calls can be captured into a graph. */
+int vad_event_tracks(const float* maps, const int32_t* labels, const uint32_t* records /* [b, max_events, 16] */,
+                     const uint32_t* counts /* [b, 4] */, long long b, int t, int h, int w, int max_events,
+                     uint32_t* tracks /* [b, max_events, t, 12] */, void* stream);
+int vad_event_tracks_plan(int* reduce_round, int* threads);
+int vad_track_boxes(const float* maps_newest, long long frame_stride, long long b, int h, int w, int max_open, const void* state,
+                    uint32_t* boxes /* [b, max_open, 12] */, void* stream);
+
 /* ------------------------------------------------------------------ Per-pixel calibration of anomaly maps (csrc/map_stats.hip)
  * The mean and standard deviation of every pixel of the anomaly map over the normal (training) frames, and the z-score map
  * z = (map - mean) / std that is ranked, thresholded and labelled in place of the raw map.  The maps stay on the device.

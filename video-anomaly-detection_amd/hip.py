@@ -16,7 +16,7 @@ PKG_DIR = Path(__file__).resolve().parent
 REPO_DIR = PKG_DIR.parent
 CSRC = PKG_DIR / "csrc"
 LIB_PATH = Path(os.environ.get("VAD_LIB", PKG_DIR / "libvad_hip.so"))
-SOURCES = ["conv_mfma.hip", "conv_wino.hip", "dec4_fused.hip", "tail.hip", "wide_io.hip", "state_io.hip", "resize_u8.hip", "frame_gather.hip", "score_hist.hip", "region_overlap.hip", "map_regions.hip", "map_match.hip", "map_events.hip", "map_track.hip", "map_smooth.hip", "map_topk.hip", "map_morph.hip", "map_temporal.hip", "map_stats.hip", "ssim.hip", "train_ops.hip", "wgrad.hip", "train_step.hip", "train_step_img.hip", "vad_api.hip", "pack.cpp"]
+SOURCES = ["conv_mfma.hip", "conv_wino.hip", "dec4_fused.hip", "tail.hip", "wide_io.hip", "state_io.hip", "resize_u8.hip", "frame_gather.hip", "score_hist.hip", "region_overlap.hip", "map_regions.hip", "map_match.hip", "map_events.hip", "map_track.hip", "map_event_tracks.hip", "map_smooth.hip", "map_topk.hip", "map_morph.hip", "map_temporal.hip", "map_stats.hip", "ssim.hip", "train_ops.hip", "wgrad.hip", "train_step.hip", "train_step_img.hip", "vad_api.hip", "pack.cpp"]
 
 VAD_OK = 0
 ABI_VERSION = 3
@@ -60,6 +60,7 @@ TRACK_WORDS = 20          # VAD_TRACK_WORDS: uint32 words of one record of vad_t
 TRACK_HEADER_WORDS = 16   # the header of one stream's tracker state: frames, open, lost in total, flags, magic, h, w, max_open, zeros
 TRACK_MAX_OPEN = 65536    # largest max_open / max_closed of vad_track_events
 TRACK_NO_RECORD = 0xFFFFFFFF   # slot plane: a pixel of an open event behind the table
+MAX_TRACK_RECORDS = 2 ** 26    # most records b * max_events * t of one vad_event_tracks call
 TOPK_MAX_RANKS = 8        # VAD_TOPK_MAX_RANKS: most ranks of one vad_map_topk call
 MORPH_MAX_SIZE = 31       # VAD_MORPH_MAX_SIZE: largest side of the structuring element of vad_morph_maps
 MORPH_OPS = {"erode": 0, "dilate": 1, "open": 2, "close": 3}   # VAD_MORPH_*
@@ -346,6 +347,10 @@ SIGNATURES = {
     "vad_track_events": (_i, [_vp, _ll, _i, _i, _i, _f, _i, _i, C.c_uint, C.c_uint, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vad_track_flush": (_i, [_ll, _i, _i, C.c_uint, C.c_uint, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vad_track_plan": (_i, [C.POINTER(_i)] * 5),
+    # per-frame tracks of anomaly events: a box per event and frame (csrc/map_event_tracks.hip)
+    "vad_event_tracks": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _vp, _vp]),
+    "vad_event_tracks_plan": (_i, [C.POINTER(_i)] * 2),
+    "vad_track_boxes": (_i, [_vp, _ll, _ll, _i, _i, _i, _vp, _vp, _vp]),
     # per-pixel statistics of anomaly maps and the z-score map (csrc/map_stats.hip)
     "vad_mapstat_state_bytes": (_sz, [_i, _i]),
     "vad_mapstat_reset": (_i, [_vp, _i, _i, _vp]),

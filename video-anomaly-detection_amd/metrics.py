@@ -1671,6 +1671,7 @@ class Events:
       frame_counts  int32 [..., T, 3]: foreground pixels of the frame, pixels of the frame that belong to kept events (whether or
                     not the event has a record: independent of max_events), NaN pixels of the frame
       labels        int32 [..., T, H, W] or None: 0, or 1 + root, for ALL foreground pixels (with `return_labels=True`)
+      tracks        None, or the `EventTracks` that `scoring.localize_events(tracks=True)` attached: a box per event and frame
 
     Views of `records` (no copies): `root`, `volume`, `t0`, `t1`, `peak_index` int32 [..., E]; `box` int32 [..., E, 4] = x0, y0, x1,
     y1 inclusive, the union over the event's frames; `peak` float32 [..., E]; `sum_x`, `sum_y`, `sum_t` int64 [..., E].  A root or a
@@ -1682,6 +1683,7 @@ class Events:
         self.volume_shape, self.threshold, self.connectivity, self.temporal = volume_shape, threshold, connectivity, temporal
         self.min_duration, self.min_volume = min_duration, min_volume
         self.max_events = int(records.shape[-2])
+        self.tracks = None                                                    # an `EventTracks`, where a caller attached one
 
     root = property(lambda self: self.records[..., 0])
     volume = property(lambda self: self.records[..., 1])
@@ -1786,6 +1788,125 @@ def detect_events(maps: torch.Tensor, threshold: float, connectivity: int = 8, t
     return result(records, counts, frame_counts, labels)
 
 
+# ====================================================================== per-frame tracks of anomaly events
+# An event record holds the union box over the event's whole life; for anything that moves that is a smear over its path (DESIGN.md
+# section 4.24).  A cross-section is the set of one event's pixels in one frame, as a record in the layout of `Regions`: a box that
+# follows the object, where it is now, a trajectory.  The host route copies the label volume and runs scipy.ndimage find_objects /
+# sum / maximum_position per frame and label; here the reduction per (event, frame) runs behind the labeller, on the device.
+MAX_TRACK_RECORDS = hip.MAX_TRACK_RECORDS
+
+
+class _CrossSections:
+    """Views of cross-section records int32 [..., 12] (include/vad_hip.h: the words of a region record), no copies."""
+    records: torch.Tensor
+
+    root = property(lambda self: self.records[..., 0])
+    area = property(lambda self: self.records[..., 1])
+    box = property(lambda self: self.records[..., 2:6])
+    peak = property(lambda self: self.records[..., 6].view(torch.float32))
+    peak_index = property(lambda self: self.records[..., 7])
+    sum_x = property(lambda self: self.records[..., 8:10].view(torch.int64)[..., 0])
+    sum_y = property(lambda self: self.records[..., 10:12].view(torch.int64)[..., 0])
+
+    def present(self) -> torch.Tensor:
+        """bool [...]: the event has a pixel there (`area > 0`)."""
+        return self.area > 0
+
+    def centroids(self) -> torch.Tensor:
+        """float64 [..., 2] on the device: (y, x) = (sum_y / area, sum_x / area), each quotient rounded once; NaN where absent."""
+        area = self.area.to(torch.float64)
+        return torch.stack([self.sum_y.to(torch.float64) / area, self.sum_x.to(torch.float64) / area], dim=-1)
+
+    @staticmethod
+    def _row(r: np.ndarray, w: int) -> dict:
+        area = int(r[1])
+        sx, sy = (int(v) for v in r[8:12].copy().view(np.int64))
+        return {"root": int(r[0]), "area": area, "box": tuple(int(v) for v in r[2:6]), "peak": float(r[6:7].copy().view(np.float32)[0]),
+                "peak_yx": divmod(int(r[7]), w), "centroid_yx": (sy / area, sx / area)}
+
+
+class EventTracks(_CrossSections):
+    """What `event_tracks` returns, with the leading shape of the events it was made from (`[B]`, or `()` for one clip):
+
+      records  int32 [..., E, T, 12]: record (e, f) is the cross-section of kept event e - record e of the `Events` - in frame f:
+               the smallest pixel y * W + x, the area, the box, the peak and its pixel, the coordinate sums of the event's pixels IN
+               THAT FRAME; all-zero where the event has no pixel in the frame and for the slots behind the kept events
+      counts   int32 [..., 4]: the counts of the `Events` (a view: `counts[..., 0]` kept events, which may exceed E)
+
+    Views of `records` (no copies): `root`, `area`, `peak_index` int32 [..., E, T]; `box` int32 [..., E, T, 4] = x0, y0, x1, y1
+    inclusive; `peak` float32 [..., E, T]; `sum_x`, `sum_y` int64 [..., E, T].  A cross-section may be disconnected inside its frame
+    (its pieces join through other frames): it is one record."""
+
+    def __init__(self, records: torch.Tensor, counts: torch.Tensor, volume_shape: Tuple[int, int, int]):
+        self.records, self.counts, self.volume_shape = records, counts, volume_shape
+        self.max_events = int(records.shape[-3])
+
+    def frame(self, t: int) -> torch.Tensor:
+        """int32 [..., E, 12] view: the cross-sections of every event in frame t - a region table of that frame, by event."""
+        frames = int(self.records.shape[-2])
+        if not _is_int(t) or not -frames <= t < frames:
+            raise hip.VadError(f"EventTracks.frame: t must be an int in {-frames}..{frames - 1}, got {t!r}")
+        return self.records[..., t, :]
+
+    def to_list(self) -> list:
+        """A host copy of the kept events' tracks only - 48 bytes per event and frame, never a map -: one list per clip of one list
+        per kept event of one entry per frame, None where the event is absent, else {'root', 'area', 'box': (x0, y0, x1, y1), 'peak',
+        'peak_yx', 'centroid_yx'}."""
+        frames, w = int(self.records.shape[-2]), self.volume_shape[2]
+        kept = torch.clamp(self.counts.reshape(-1, 4)[:, 0], max=self.max_events).cpu().numpy()
+        flat = self.records.reshape(-1, self.max_events, frames, REGION_WORDS)
+        out = []
+        for c in range(flat.shape[0]):
+            rec = flat[c, :int(kept[c])].cpu().numpy()
+            out.append([[self._row(r, w) if r[1] else None for r in track] for track in rec])
+        return out
+
+
+def event_tracks(maps: torch.Tensor, events: "Events") -> EventTracks:
+    """The cross-sections of every kept event of `events` in every frame, on the GPU (`vad_event_tracks`,
+    csrc/map_event_tracks.hip).  `maps`: the float32 GPU tensor `events` was detected on (`[T,H,W]`, `[B,T,H,W]` or `[B,T,1,H,W]`);
+    `events`: what `detect_events(maps, ..., return_labels=True)` returned - its label volume says which event a pixel belongs to,
+    its records which events are kept and inside the table.  Events dropped by `min_duration` / `min_volume` and events without a
+    record (`events.truncated()`) have no track.  Returns an `EventTracks`; at most 2^26 records `B * max_events * T` per call.
+    Three launches behind the labeller, no workspace, nothing read by the host: the call can be captured.  No CPU fallback."""
+    what = "event_tracks"
+    if not isinstance(events, Events):
+        raise hip.VadError(f"{what}: events must be a metrics.Events, got {type(events).__name__}")
+    if events.labels is None:
+        raise hip.VadError(f"{what}: events carry no labels; detect them with detect_events(..., return_labels=True)")
+    if not isinstance(maps, torch.Tensor):
+        raise hip.VadError(f"{what}: maps must be a torch tensor")
+    t, h, w = events.volume_shape
+    lead = tuple(int(v) for v in events.counts.shape[:-1])
+    max_events = events.max_events
+    shapes = [(*lead, t, h, w)] + ([(*lead, t, 1, h, w)] if lead else [])
+    if tuple(maps.shape) not in shapes:
+        raise hip.VadError(f"{what}: maps {tuple(maps.shape)} do not match the events' volumes {shapes[0]}")
+    for name, v, shape in (("labels", events.labels, (*lead, t, h, w)), ("records", events.records, (*lead, max_events, EVENT_WORDS))):
+        if tuple(v.shape) != shape:
+            raise hip.VadError(f"{what}: the events' {name} {tuple(v.shape)} do not match their volumes: expected {shape}")
+    for name, v in (("labels", events.labels), ("records", events.records), ("counts", events.counts)):
+        if v.dtype != torch.int32:
+            raise hip.VadError(f"{what}: the events' {name} must be int32, got {v.dtype}")
+    _check_maps(maps, what, "tracks are reduced on the device")
+    for name, v in (("labels", events.labels), ("records", events.records), ("counts", events.counts)):
+        if v.device != maps.device:
+            raise hip.VadError(f"{what}: maps ({maps.device}) and the events' {name} ({v.device}) are on different devices")
+    b = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    if b * max_events * t > MAX_TRACK_RECORDS:
+        raise hip.VadError(f"{what}: {b} clips x {max_events} events x {t} frames are more than 2^26 records; call it on fewer clips")
+    dev = maps.device
+    clips, labels = maps.reshape(b, t, h, w).contiguous(), events.labels.reshape(b, t, h, w).contiguous()
+    records, counts = events.records.reshape(b, max_events, EVENT_WORDS).contiguous(), events.counts.reshape(b, 4).contiguous()
+    tracks = torch.empty((b, max_events, t, REGION_WORDS), dtype=torch.int32, device=dev)
+    if b:
+        with torch.cuda.device(dev):
+            hip.check(hip.lib().vad_event_tracks(clips.data_ptr(), labels.data_ptr(), records.data_ptr(), counts.data_ptr(), b, t, h, w,
+                                                 max_events, tracks.data_ptr(), hip.current_stream()), "vad_event_tracks")
+        _count(what)
+    return EventTracks(tracks.view(*lead, max_events, t, REGION_WORDS), events.counts, (t, h, w))
+
+
 # ====================================================================== anomaly events across the calls of a live stream
 # `detect_events` closes every event at the end of its clip.  A camera that hands over its newest frame (`score_stateful`) needs the
 # events continued between calls (DESIGN.md section 4.19): the open events and the newest frame's slot plane are state on the
@@ -1837,6 +1958,22 @@ class _TrackRecords:
         return out
 
 
+class TrackBoxes(_CrossSections):
+    """`TrackUpdate.boxes`: `records` int32 [B, max_open, 12] - record r is the cross-section, in the newest frame of the call, of
+    the open event in slot r (`vad_track_boxes`): its smallest pixel (the event's `handle`), area, box, peak and peak pixel,
+    coordinate sums IN THAT FRAME; all-zero behind the open events.  A lost event has no record.  The views of `EventTracks`
+    without the frame axis: `root`, `area`, `box`, `peak`, `peak_index`, `sum_x`, `sum_y`, `present()`, `centroids()`."""
+
+    def __init__(self, records, frame_shape):
+        self.records, self.frame_shape = records, frame_shape
+
+    def to_list(self) -> list:
+        """A host copy - 48 bytes per slot, never a map -: one list per stream of the open slots' cross-sections, in slot order."""
+        w = self.frame_shape[1]
+        rec = self.records.cpu().numpy()
+        return [[self._row(r, w) for r in stream if r[1]] for stream in rec]
+
+
 class TrackUpdate(_TrackRecords):
     """What one `EventTracker.update` / `flush` returns, as device tensors with the leading shape `[B]` of the streams:
 
@@ -1848,10 +1985,25 @@ class TrackUpdate(_TrackRecords):
                     (duration so far >= min_duration, volume so far >= min_volume), NaN pixels of the frame; T = 0 for a flush
 
     Views of `records` as in `Events`, with `root_pixel` / `t0` in place of `root`, `peak_pixel` / `peak_frame` in place of
-    `peak_index`, `handle`, and `volume` as int64."""
+    `peak_index`, `handle`, and `volume` as int64.
 
-    def __init__(self, records, counts, frame_counts, frame_shape, max_closed):
+      boxes         a `TrackBoxes` after `update(maps, boxes=True)`, else None: the cross-sections of the open events in the newest
+                    frame of the call"""
+
+    def __init__(self, records, counts, frame_counts, frame_shape, max_closed, boxes=None, tracker=None):
         self.records, self.counts, self.frame_counts, self.frame_shape, self.max_closed = records, counts, frame_counts, frame_shape, max_closed
+        self.boxes, self._tracker = boxes, tracker
+
+    def boxes_alarming(self) -> torch.Tensor:
+        """bool [B, max_open]: the open event in that slot alarms now - it has lasted `min_duration` frames and gathered
+        `min_volume` pixels -, false behind the open events.  Torch operations on the tracker's open table AS IT STANDS: ask before
+        the next `update` / `flush` / `reset` of the tracker.  Needs `update(maps, boxes=True)`."""
+        if self.boxes is None:
+            raise hip.VadError("TrackUpdate.boxes_alarming: this update carries no boxes; call update(maps, boxes=True)")
+        tr = self._tracker
+        opened = tr.open_events()
+        in_use = torch.arange(tr.max_open, device=opened.records.device)[None, :] < opened.counts[:, None]
+        return in_use & (opened.durations() >= tr.min_duration) & (opened.volume >= tr.min_volume)
 
     def alarms(self) -> torch.Tensor:
         """bool [B, T]: the frame holds a pixel of an event that has lasted min_duration frames and gathered min_volume pixels."""
@@ -1981,9 +2133,15 @@ class EventTracker:
             raise hip.VadError(f"{what}: flags {flags:#x} are set - a stream's frame counter stands at 2^32 - 1; reset the tracker")
         _raise_on_flags(flags, what)
 
-    def update(self, maps: torch.Tensor) -> TrackUpdate:
-        """maps: float32 GPU tensor `[B,H,W]` (one new map per stream), `[B,T,H,W]` or `[B,T,1,H,W]`."""
+    def update(self, maps: torch.Tensor, boxes: bool = False) -> TrackUpdate:
+        """maps: float32 GPU tensor `[B,H,W]` (one new map per stream), `[B,T,H,W]` or `[B,T,1,H,W]`.
+        `boxes=True`: `vad_track_boxes` is launched behind the tracker's launches and `TrackUpdate.boxes` holds, per open slot, the
+        cross-section of its event in the LAST frame of the call (a `TrackBoxes`; its `root` is `open_events().handle`) - the box
+        that follows the object, where the open record has the union box of the event's life.  With T > 1 only the last frame has
+        cross-sections: a live stream calls with T = 1.  `boxes=False` (the default): nothing more is launched, `boxes` is None."""
         what = "EventTracker.update"
+        if not isinstance(boxes, bool):
+            raise hip.VadError(f"{what}: boxes must be a bool, got {boxes!r}")
         _check_maps(maps, what, "events are tracked on the device")
         if maps.dim() == 3:
             maps = maps[:, None]
@@ -2003,16 +2161,24 @@ class EventTracker:
         records = torch.empty((b, self.max_closed, TRACK_WORDS), dtype=torch.int32, device=dev)
         counts = torch.empty((b, 6), dtype=torch.int32, device=dev)
         frame_counts = torch.empty((b, t, 3), dtype=torch.int32, device=dev)
+        table = torch.empty((b, self.max_open, REGION_WORDS), dtype=torch.int32, device=dev) if boxes else None
         if b == 0:
-            return TrackUpdate(records, counts, frame_counts, (self.h, self.w), self.max_closed)
+            return TrackUpdate(records, counts, frame_counts, (self.h, self.w), self.max_closed,
+                               TrackBoxes(table, (self.h, self.w)) if boxes else None, self)
         with torch.cuda.device(dev):
             ws = self._workspace(t)
             hip.check(hip.lib().vad_track_events(maps.data_ptr(), b, t, self.h, self.w, self.threshold, self.connectivity, self.temporal,
                                                  self.min_duration, self.min_volume, self.max_open, self.max_closed, self.state.data_ptr(),
                                                  records.data_ptr(), counts.data_ptr(), frame_counts.data_ptr(), ws.data_ptr(), ws.numel(),
                                                  hip.current_stream()), "vad_track_events")
+            if boxes:                                                         # the last frame of the call, in place
+                npix = self.h * self.w
+                hip.check(hip.lib().vad_track_boxes(maps.data_ptr() + 4 * (t - 1) * npix, t * npix, b, self.h, self.w, self.max_open,
+                                                    self.state.data_ptr(), table.data_ptr(), hip.current_stream()), "vad_track_boxes")
+                _count("track_boxes")
             self._done(ws, what)
-        return TrackUpdate(records, counts, frame_counts, (self.h, self.w), self.max_closed)
+        return TrackUpdate(records, counts, frame_counts, (self.h, self.w), self.max_closed,
+                           TrackBoxes(table, (self.h, self.w)) if boxes else None, self)
 
     def flush(self) -> TrackUpdate:
         """Closes every open event as if an empty frame had arrived - in slot order, through the same filters -, without advancing

@@ -698,7 +698,7 @@ def localize(model, images, threshold: float, map: str = "mse", sigma=None, trun
 
 def localize_events(model, images, threshold: float, map: str = "mse", sigma=None, truncate: float = 4.0, calibration=None,
                     min_std: Optional[float] = None, connectivity: int = 8, temporal: int = 9, min_duration: int = 1, min_volume: int = 1,
-                    max_events: int = 64, morph=None, temporal_filter=None):
+                    max_events: int = 64, morph=None, temporal_filter=None, tracks: bool = False):
     """`localize` with the event table: the model's anomaly maps and the events of `map >= threshold` in them - regions linked
     across consecutive frames (`metrics.detect_events`), so that a line alarms on what persists (`min_duration`) and not on one
     noisy map.  `images`: `[B,T,C,H,W]` clips for the video model (map "mse" only), every clip its own volume; `[N,C,H,W]` frames
@@ -709,8 +709,13 @@ def localize_events(model, images, threshold: float, map: str = "mse", sigma=Non
     `temporal_filter`: the `temporal=` spec of `pixel_auroc` under another name - `temporal` is this entry point's link structure -:
     clips only (an image batch is refused, although this entry point reads it as one volume: use `localize_stream(temporal_filter=)`
     for a camera), every clip a fresh stream, after `morph` and before the threshold; the maps returned are the filtered maps.
-    `("min", 2)` in front of the labeller removes what differs from frame to frame."""
+    `("min", 2)` in front of the labeller removes what differs from frame to frame.
+    `tracks=True`: the labels are requested from `detect_events` and ONE `metrics.event_tracks` call follows; `events.tracks` is then
+    a `metrics.EventTracks` - a box, a peak and a centroid per kept event and frame - and `events.labels` the label volume.  The
+    default leaves launches and outputs as they are (`events.tracks` is None)."""
     _check_map_name(map, "localize_events")
+    if not isinstance(tracks, bool):
+        raise hip.VadError(f"localize_events: tracks must be a bool, got {tracks!r}")
     morph = metrics.morph_steps(morph)
     temporal_filter = metrics.temporal_steps(temporal_filter)
     if images.dim() == 5 and map != "mse":
@@ -719,11 +724,14 @@ def localize_events(model, images, threshold: float, map: str = "mse", sigma=Non
     with torch.no_grad():
         maps = _anomaly_maps(model, images, map, sigma, truncate, calibration, min_std, morph, temporal_filter, "localize_events")
         volumes = maps if maps.dim() == 5 else maps[:, 0]                 # [B,T,1,H,W], or the image batch as one clip [N,H,W]
-        return metrics.detect_events(volumes, threshold, connectivity, temporal, min_duration, min_volume, max_events), maps
+        events = metrics.detect_events(volumes, threshold, connectivity, temporal, min_duration, min_volume, max_events, return_labels=tracks)
+        if tracks:
+            events.tracks = metrics.event_tracks(volumes, events)
+        return events, maps
 
 
 def localize_stream(model, frames, tracker, state=None, sigma=None, truncate: float = 4.0, calibration=None, min_std: Optional[float] = None,
-                    morph=None, temporal_filter=None):
+                    morph=None, temporal_filter=None, boxes: bool = False):
     """One step of a live stream with events carried between calls (`metrics.EventTracker`): the newest
     frames are scored, their error maps smoothed and calibrated as in `localize_events`, and handed to `tracker.update`.
     Video model: `frames` `[B,T,C,H,W]` (or the uint8 layouts `score_stateful` takes) are the next T frames of B streams; ONE
@@ -736,7 +744,9 @@ def localize_stream(model, frames, tracker, state=None, sigma=None, truncate: fl
     `temporal_filter` (None = none, as before): a `metrics.TemporalFilter` for B streams of these maps, which carries the last frames
     between calls - the maps go through `temporal_filter.update` after the morphology and before the tracker, so tracker and filter
     see what `localize_events(temporal=)` sees on the whole stream, however its frames are split over calls.  Both models: the image
-    model's `[B,1,H,W]` is one new frame of B cameras.  The maps returned are the filtered maps.  Reset it with the tracker."""
+    model's `[B,1,H,W]` is one new frame of B cameras.  The maps returned are the filtered maps.  Reset it with the tracker.
+    `boxes` is handed to `tracker.update`: with True, `update.boxes` holds the cross-section of every open event in the newest frame
+    (`metrics.TrackBoxes`), and `update.boxes_alarming()` which of them alarm now."""
     morph = metrics.morph_steps(morph)
     if temporal_filter is not None and not isinstance(temporal_filter, metrics.TemporalFilter):
         raise hip.VadError(f"localize_stream: temporal_filter must be a metrics.TemporalFilter, got {type(temporal_filter).__name__}")
@@ -760,5 +770,5 @@ def localize_stream(model, frames, tracker, state=None, sigma=None, truncate: fl
             maps = metrics.apply_morph(maps, morph)
         if temporal_filter is not None:                                   # [B,T,1,H,W] as it stands; [B,1,H,W] = B streams x 1 frame
             maps = temporal_filter.update(maps.contiguous())
-        update = tracker.update(maps if video else maps[:, 0])
+        update = tracker.update(maps if video else maps[:, 0], boxes=boxes)
     return update, maps, state
