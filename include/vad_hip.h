@@ -913,6 +913,37 @@ enum { VAD_MORPH_ERODE = 0, VAD_MORPH_DILATE = 1, VAD_MORPH_OPEN = 2, VAD_MORPH_
 int vad_morph_maps(const float* maps, long long n, int h, int w, int op, int size_h, int size_w, float* out, void* stream);
 int vad_morph_tile(int size_h, int size_w, int op, int* tile_h, int* tile_w);
 
+/* ------------------------------------------------------------------ Rank filters of anomaly maps (csrc/map_rankfilt.hip)
+ * The sliding-window median and its generalisation, the r-th smallest value of a rectangular window: the denoiser of impulsive
+ * noise (single hot pixels) that keeps step edges where they are and leaves the level of flat areas alone.  Erosion and dilation
+ * above are the two end ranks of this family.
+ *
+ * vad_rankfilt_maps: maps = n frames of h x w fp32, contiguous (any h, w >= 1 with h * w <= VAD_MAX_FRAME_PIXELS; 4-byte aligned).
+ * The window is size_h x size_w (N = size_h * size_w values), each side in 1 .. VAD_RANKFILT_MAX_SIZE, even sizes included; a side
+ * may exceed h or w.  rank is 0-based and ascending, 0 .. N - 1.
+ * Semantics: scipy.ndimage.rank_filter(x, rank, size=(size_h, size_w), mode="reflect") -
+ *   out[y][x] = the rank-th smallest of { x[R(y - size_h/2 + i, h)][R(x - size_w/2 + j, w)] : 0 <= i < size_h, 0 <= j < size_w }
+ *   R(i, L): m = i mod 2L (non-negative);  m < L ? m : 2L - 1 - m          (d c b a | a b c d | d c b a, periodic)
+ * with integer division: even sizes lean towards index 0, as VAD_MORPH_ERODE does.  A reflected pixel counts as often as it appears
+ * in the window (a rank, unlike a minimum or maximum, cannot clamp its window); a window larger than the frame reflects several
+ * times.  median_filter is rank = N / 2 (the upper median of an even N); percentile_filter(p) is p += 100 if p < 0, then rank =
+ * N - 1 if p == 100, else (int)((double)N * p / 100.0).
+ * Relations to vad_morph_maps: rank 0 equals VAD_MORPH_ERODE at every size.  Rank N - 1 equals VAD_MORPH_DILATE at ODD sizes only:
+ * scipy's dilation mirrors the origin of an even element (it reaches (s - 1) / 2 towards index 0, this window s / 2).
+ * Nothing is computed, only selected, so the result is specified to the bit: the order is that of the monotone integer key of
+ * vad_map_topk (-0 below +0; denormals and +-Inf are ordinary values), the result is one of the window's values with its bits
+ * unchanged, and a window that holds a NaN gives NaN at every rank, as vad_morph_maps does (scipy's result there is an accident of
+ * its selection algorithm and is not followed).  Size 1 x 1 is a copy.
+ * out: n x h x w; it must not overlap maps.  VAD_ERR_ARG for a size outside 1 .. VAD_RANKFILT_MAX_SIZE, a rank outside 0 .. N - 1,
+ * n < 0, h or w out of range, a NULL or misaligned pointer, out overlapping maps.  n == 0 returns VAD_OK and launches nothing.
+ * One launch per call on `stream` (n above 65535: one per 65535 frames, as vad_morph_maps), one read and one write of the maps, no
+ * workspace, no allocation, no host synchronisation: capturable in a graph.  A frame's bits do not depend on its batch.
+ * vad_rankfilt_tile reports the output tile of one work-group (rows, columns) for a size - what a test needs to build a frame of
+ * several tiles; VAD_ERR_ARG for a size out of range. */
+#define VAD_RANKFILT_MAX_SIZE 15
+int vad_rankfilt_maps(const float* maps, long long n, int h, int w, int size_h, int size_w, int rank, float* out, void* stream);
+int vad_rankfilt_tile(int size_h, int size_w, int* tile_h, int* tile_w);
+
 /* ------------------------------------------------------------------ Temporal filters of anomaly maps (csrc/map_temporal.hip)
  * The step a video line takes between the map and its threshold: every pixel filtered over the last k frames of its stream.  The
  * minimum is a temporal erosion ("high in each of the last k frames": removes noise that differs from frame to frame, without any

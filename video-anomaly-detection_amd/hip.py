@@ -16,7 +16,7 @@ PKG_DIR = Path(__file__).resolve().parent
 REPO_DIR = PKG_DIR.parent
 CSRC = PKG_DIR / "csrc"
 LIB_PATH = Path(os.environ.get("VAD_LIB", PKG_DIR / "libvad_hip.so"))
-SOURCES = ["conv_mfma.hip", "conv_wino.hip", "dec4_fused.hip", "tail.hip", "wide_io.hip", "state_io.hip", "resize_u8.hip", "frame_gather.hip", "score_hist.hip", "region_overlap.hip", "map_regions.hip", "map_match.hip", "map_events.hip", "map_track.hip", "map_event_tracks.hip", "map_smooth.hip", "map_topk.hip", "map_morph.hip", "map_temporal.hip", "map_stats.hip", "ssim.hip", "train_ops.hip", "wgrad.hip", "train_step.hip", "train_step_img.hip", "vad_api.hip", "pack.cpp"]
+SOURCES = ["conv_mfma.hip", "conv_wino.hip", "dec4_fused.hip", "tail.hip", "wide_io.hip", "state_io.hip", "resize_u8.hip", "frame_gather.hip", "score_hist.hip", "region_overlap.hip", "map_regions.hip", "map_match.hip", "map_events.hip", "map_track.hip", "map_event_tracks.hip", "map_smooth.hip", "map_topk.hip", "map_morph.hip", "map_rankfilt.hip", "map_temporal.hip", "map_stats.hip", "ssim.hip", "train_ops.hip", "wgrad.hip", "train_step.hip", "train_step_img.hip", "vad_api.hip", "pack.cpp"]
 
 VAD_OK = 0
 ABI_VERSION = 3
@@ -64,7 +64,8 @@ MAX_TRACK_RECORDS = 2 ** 26    # most records b * max_events * t of one vad_even
 TOPK_MAX_RANKS = 8        # VAD_TOPK_MAX_RANKS: most ranks of one vad_map_topk call
 MORPH_MAX_SIZE = 31       # VAD_MORPH_MAX_SIZE: largest side of the structuring element of vad_morph_maps
 MORPH_OPS = {"erode": 0, "dilate": 1, "open": 2, "close": 3}   # VAD_MORPH_*
-TFILT_MAX_K = 16          # VAD_TFILT_MAX_K: longest window of vad_tfilt_maps
+RANKFILT_MAX_SIZE = 15    # VAD_RANKFILT_MAX_SIZE: largest side of the window of vad_rankfilt_maps
+TFILT_MAX_K = 16         # VAD_TFILT_MAX_K: longest window of vad_tfilt_maps
 TFILT_OPS = {"min": 0, "max": 1, "mean": 2, "ema": 3}   # VAD_TFILT_*
 TFILT_HEADER_WORDS = 16   # per stream of a temporal filter's state: frames seen, ring position, ticket, 0, magic, op, k, h, w, zeros
 SMOOTH_TILE = (32, 64)    # csrc/map_smooth.hip SM_TH x SM_TW: the output tile of one work-group (vad_smooth_tile reports the library's)
@@ -324,6 +325,9 @@ SIGNATURES = {
     # grey morphology of anomaly maps: erode, dilate, open, close (csrc/map_morph.hip)
     "vad_morph_maps": (_i, [_vp, _ll, _i, _i, _i, _i, _i, _vp, _vp]),
     "vad_morph_tile": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
+    # rank filters of anomaly maps: median, percentile, rank (csrc/map_rankfilt.hip)
+    "vad_rankfilt_maps": (_i, [_vp, _ll, _i, _i, _i, _i, _i, _vp, _vp]),
+    "vad_rankfilt_tile": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i)]),
     # temporal filters of anomaly maps: causal min, max, mean over the last k frames, exponential average (csrc/map_temporal.hip)
     "vad_tfilt_state_bytes": (_sz, [_ll, _i, _i, _i, _i]),
     "vad_tfilt_init": (_i, [_vp, _ll, _i, _i, _i, _i, _vp]),

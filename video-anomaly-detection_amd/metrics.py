@@ -34,6 +34,9 @@ map over normal frames and turns a map into its z-score, which is then smoothed-
 Between the frames of a clip or a live stream sit `temporal_maps` / `TemporalFilter` (csrc/map_temporal.hip): every pixel filtered
 over the last k frames - causal minimum, maximum, mean, exponential average - before the threshold.
 
+Between the calibration and the morphology sit `rank_filter_maps` / `apply_rank_filter` (csrc/map_rankfilt.hip): the sliding-window
+median, percentile or rank of every map - the denoiser of single hot pixels that keeps edges and flat levels where they are.
+
 At the end of the chain, where a map becomes ONE number per frame, sit `map_topk` and `reduce_maps` (csrc/map_topk.hip): the k-th
 largest pixel and the mean of the k largest, the robust frame scores between the mean of the map and its maximum.
 """
@@ -989,6 +992,145 @@ def apply_morph(maps: torch.Tensor, steps) -> torch.Tensor:
             bufs.append(morph_maps(maps, op, size))
         else:
             bufs.append(morph_maps(maps, op, size, out=bufs[-2]))
+        maps = bufs[-1]
+    return maps
+
+
+# ====================================================================== rank filters of anomaly maps
+# The sliding-window median and its generalisation, the r-th smallest value of a rectangular window: the
+# denoiser of impulsive noise - single hot pixels on edges, gloss and sensor noise - that keeps step edges where they are and leaves
+# the level of flat areas alone.  Erosion and dilation are its two end ranks.  scipy.ndimage.rank_filter / median_filter /
+# percentile_filter with mode="reflect" to the bit on NaN-free maps; a NaN makes its windows NaN.
+RANKFILT_MAX_SIZE = hip.RANKFILT_MAX_SIZE
+RANKFILT_KINDS = ("median", "percentile", "rank")
+RANKFILT_MAX_STEPS = 4
+
+
+def _rankfilt_size(size, what: str) -> Tuple[int, int]:
+    """An int or (size_h, size_w), each in 1..15 -> (size_h, size_w)."""
+    if _is_int(size):
+        size = (size, size)
+    if not isinstance(size, (tuple, list)) or len(size) != 2 or not all(_is_int(v) for v in size):
+        raise hip.VadError(f"{what}: size must be an int or (size_h, size_w), got {size!r}")
+    sh, sw = int(size[0]), int(size[1])
+    if not (1 <= sh <= RANKFILT_MAX_SIZE and 1 <= sw <= RANKFILT_MAX_SIZE):
+        raise hip.VadError(f"{what}: size must be in 1..{RANKFILT_MAX_SIZE} per side, got {sh} x {sw}")
+    return sh, sw
+
+
+def _rankfilt_rank(rank, n: int, what: str) -> int:
+    """A 0-based ascending rank of a window of n values."""
+    if not _is_int(rank) or not 0 <= int(rank) < n:
+        raise hip.VadError(f"{what}: rank must be an int in 0..{n - 1} (a window of {n} values), got {rank!r}")
+    return int(rank)
+
+
+def rank_of_percentile(n: int, p) -> int:
+    """The 0-based ascending rank `scipy.ndimage.percentile_filter(x, p, ...)` selects from a window of n values: p += 100 if p < 0,
+    then n - 1 for p == 100, else int(float(n) * p / 100.0).  -100 <= p <= 100."""
+    what = "rank_of_percentile"
+    if not _is_int(n) or int(n) < 1:
+        raise hip.VadError(f"{what}: n must be an int >= 1, got {n!r}")
+    if isinstance(p, bool) or not isinstance(p, (int, float, np.integer, np.floating)) or not -100.0 <= float(p) <= 100.0:
+        raise hip.VadError(f"{what}: p must be a number in -100..100, got {p!r}")
+    p = float(p)
+    if p < 0.0:
+        p += 100.0
+    return int(n) - 1 if p == 100.0 else int(float(int(n)) * p / 100.0)
+
+
+def rank_filter_steps(spec) -> Tuple[Tuple[Tuple[int, int], int], ...]:
+    """What the `rank_filter=` arguments of the scoring entry points take, normalised to a tuple of ((size_h, size_w), rank) steps:
+    None -> (), one step or a list of at most four.  A step is `("median", size)` (rank n // 2: the upper median of an even
+    window), `("percentile", size, p)` (`rank_of_percentile`) or `("rank", size, r)` (0-based, ascending); `size` an int or
+    `(size_h, size_w)`, sides in 1..15.  `VadError` for anything else."""
+    what = "rank_filter_steps"
+    if spec is None:
+        return ()
+    if isinstance(spec, tuple) and len(spec) in (2, 3) and isinstance(spec[0], str):
+        spec = [spec]
+    if not isinstance(spec, list):
+        raise hip.VadError(f"{what}: a spec is None, one step (kind, size[, p or rank]) or a list of steps, got {spec!r}")
+    if not 1 <= len(spec) <= RANKFILT_MAX_STEPS:
+        raise hip.VadError(f"{what}: a list holds 1..{RANKFILT_MAX_STEPS} steps, got {len(spec)}")
+    steps = []
+    for step in spec:
+        if not isinstance(step, (tuple, list)) or len(step) not in (2, 3):
+            raise hip.VadError(f"{what}: a step is ('median', size), ('percentile', size, p) or ('rank', size, r), got {step!r}")
+        kind = step[0]
+        if not isinstance(kind, str) or kind not in RANKFILT_KINDS:
+            raise hip.VadError(f"{what}: kind must be one of {RANKFILT_KINDS}, got {kind!r}")
+        if len(step) != (2 if kind == "median" else 3):
+            raise hip.VadError(f"{what}: a step is ('median', size), ('percentile', size, p) or ('rank', size, r), got {step!r}")
+        sh, sw = _rankfilt_size(step[1], what)
+        n = sh * sw
+        if kind == "median":
+            rank = n // 2
+        elif kind == "percentile":
+            p = step[2]
+            if isinstance(p, bool) or not isinstance(p, (int, float, np.integer, np.floating)) or not -100.0 <= float(p) <= 100.0:
+                raise hip.VadError(f"{what}: a percentile must be a number in -100..100, got {p!r}")
+            rank = rank_of_percentile(n, p)
+        else:
+            rank = _rankfilt_rank(step[2], n, what)
+        steps.append(((sh, sw), rank))
+    return tuple(steps)
+
+
+def rank_filter_maps(maps: torch.Tensor, size, rank="median", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`scipy.ndimage.rank_filter(x, rank, size=(size_h, size_w), mode="reflect")` of every H x W frame of `maps` on the GPU
+    (`vad_rankfilt_maps`, csrc/map_rankfilt.hip): the `rank`-th smallest value (0-based) of the window around each pixel, even sizes
+    leaning towards index 0, reflected pixels counted as often as they appear; `size` an int (a square) or (size_h, size_w), sides in
+    1..15, larger than the frame allowed.  `rank` = "median" is n // 2 of the n = size_h * size_w values (`median_filter`; the upper
+    median of an even n); `rank_of_percentile(n, p)` gives `percentile_filter`'s.  Rank 0 is `morph_maps(x, "erode", size)`; rank
+    n - 1 is `"dilate"` at odd sizes only.  `maps` as `morph_maps` takes them: float32 GPU tensor, contiguous, the last two
+    dimensions H, W and any leading ones; frames are processed one by one.  Nothing is computed, only selected, so the result is
+    specified to the bit (tests/rank_filter_ref.py): one of the window's values, -0 ordered below +0; a NaN makes exactly the pixels
+    whose window holds it NaN, at every rank.  Returns a new tensor, or `out` (same shape, float32, contiguous, not overlapping
+    `maps`).  One launch, no workspace; asynchronous on the current stream."""
+    what = "rank_filter_maps"
+    if not isinstance(maps, torch.Tensor):
+        raise hip.VadError(f"{what}: maps must be a torch tensor")
+    sh, sw = _rankfilt_size(size, what)
+    if isinstance(rank, str):
+        if rank != "median":
+            raise hip.VadError(f"{what}: rank must be 'median' or an int in 0..{sh * sw - 1}, got {rank!r}")
+        r = (sh * sw) // 2
+    else:
+        r = _rankfilt_rank(rank, sh * sw, what)
+    if not maps.is_cuda:
+        raise hip.VadError(f"{what}: maps ({maps.device}) must be on the GPU (the rank filter runs on the device; there is no CPU fallback)")
+    if maps.dtype != torch.float32:
+        raise hip.VadError(f"{what}: maps must be float32, got {maps.dtype}")
+    if maps.dim() < 2:
+        raise hip.VadError(f"{what}: maps must have at least the two dimensions H, W, got {tuple(maps.shape)}")
+    if not maps.is_contiguous():
+        raise hip.VadError(f"{what}: maps must be contiguous (got strides {tuple(maps.stride())} for {tuple(maps.shape)}); it is not copied silently")
+    lead, h, w = tuple(maps.shape[:-2]), int(maps.shape[-2]), int(maps.shape[-1])
+    if h < 1 or w < 1 or h * w > hip.MAX_FRAME_PIXELS:
+        raise hip.VadError(f"{what}: frames of {h} x {w} are out of range (H, W >= 1 and H * W <= {hip.MAX_FRAME_PIXELS})")
+    if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(maps.shape) or out.dtype != torch.float32
+                            or out.device != maps.device or not out.is_contiguous()):
+        raise hip.VadError(f"{what}: out must be a contiguous float32 tensor {tuple(maps.shape)} on {maps.device}")
+    n = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    with torch.cuda.device(maps.device):
+        if out is None:
+            out = torch.empty_like(maps)
+        if n > 0:
+            hip.check(hip.lib().vad_rankfilt_maps(maps.data_ptr(), n, h, w, sh, sw, r, out.data_ptr(), hip.current_stream()), "vad_rankfilt_maps")
+            _count("rank_filter_maps")
+    return out
+
+
+def apply_rank_filter(maps: torch.Tensor, steps) -> torch.Tensor:
+    """`maps` through the steps of `rank_filter_steps(...)`, one launch per step.  One step returns a new tensor; a list ping-pongs
+    two buffers of its own, so `maps` is never written.  No steps: `maps` itself."""
+    bufs = []
+    for size, rank in steps:
+        if len(bufs) < 2:
+            bufs.append(rank_filter_maps(maps, size, rank))
+        else:
+            bufs.append(rank_filter_maps(maps, size, rank, out=bufs[-2]))
         maps = bufs[-1]
     return maps
 

@@ -98,29 +98,31 @@ def compute_auroc_smoothed(model, test_loader: Iterable[dict], device, sigma: fl
 
 
 def frame_scores(model, images, reduce, map: str = "mse", sigma=None, truncate: float = 4.0, calibration=None,
-                 min_std: Optional[float] = None, morph=None, temporal=None):
+                 min_std: Optional[float] = None, morph=None, temporal=None, *, rank_filter=None):
     """Robust frame scores of one batch: the model's anomaly maps - the chain of `localize`: `map`, `sigma`,
     `truncate`, `calibration`, `min_std`, `morph` as there - reduced per frame by `metrics.reduce_maps(maps, reduce)`: `reduce` =
     "max", ("topk", fraction) - the mean of the top fraction of the pixels -, ("quantile", q) or ("rank", k).  `images`: `[B,C,H,W]`
     for the image model, `[B,T,C,H,W]` clips for the video model (map "mse" only).  Per batch ONE scoring call, the optional
     smoothing / calibration / morphology calls and ONE `metrics.map_topk` call; nothing is read by the host.  Returns (scores, maps):
     `[B]` / `[B,T]` float32 on the device, and the maps they were reduced from (`[B,1,H,W]` / `[B,T,1,H,W]`), so that a stream which
-    also localises does not score twice.  `temporal` as in `pixel_auroc` (clips only; last in the chain, before the reduction)."""
+    also localises does not score twice.  `temporal` as in `pixel_auroc` (clips only; last in the chain, before the reduction);
+    `rank_filter` as there (after the calibration, before `morph`)."""
     what = "frame_scores"
     _check_map_name(map, what)
     metrics.reduce_spec(reduce, what)
     morph = metrics.morph_steps(morph)
+    rank_filter = metrics.rank_filter_steps(rank_filter)
     temporal = metrics.temporal_steps(temporal)
     if images.dim() == 5 and map != "mse":
         _refuse_clips_on(map, what, "scored")
     min_std = _check_calibration(calibration, what, map, sigma, truncate, min_std)
     with torch.no_grad():
-        maps = _anomaly_maps(model, images, map, sigma, truncate, calibration, min_std, morph, temporal, what)
+        maps = _anomaly_maps(model, images, map, sigma, truncate, calibration, min_std, morph, temporal, what, rank_filter=rank_filter)
         return metrics.reduce_maps(maps, reduce).reshape(maps.shape[:-3]), maps
 
 
 def compute_auroc_maps(model, test_loader: Iterable[dict], device, reduce=("topk", 0.01), map: str = "mse", sigma=None,
-                       truncate: float = 4.0, calibration=None, min_std: Optional[float] = None, morph=None):
+                       truncate: float = 4.0, calibration=None, min_std: Optional[float] = None, morph=None, *, rank_filter=None):
     """`compute_auroc` with a robust image score: `frame_scores(model, images, reduce, ...)` - by default the mean of the top 1 % of
     the error map's pixels - instead of the mean squared error, which a small defect on a large frame barely moves, or the maximum
     (`compute_auroc_smoothed`), which is one pixel.  Same batches, same 4-tuple; the map arguments as in `pixel_auroc`.  The maps stay
@@ -129,10 +131,12 @@ def compute_auroc_maps(model, test_loader: Iterable[dict], device, reduce=("topk
     _check_map_name(map, what)
     metrics.reduce_spec(reduce, what)
     metrics.morph_steps(morph)
+    metrics.rank_filter_steps(rank_filter)
     _check_calibration(calibration, what, map, sigma, truncate, min_std)
     all_labels, all_scores, all_types = [], [], []
     for batch in test_loader:
-        scores, _ = frame_scores(model, batch["image"].to(device), reduce, map, sigma, truncate, calibration, min_std, morph)
+        scores, _ = frame_scores(model, batch["image"].to(device), reduce, map, sigma, truncate, calibration, min_std, morph,
+                                 rank_filter=rank_filter)
         all_scores.extend(scores.cpu().numpy())
         all_labels.extend(np.asarray(batch["label"]))
         all_types.extend(batch["defect_type"])
@@ -427,11 +431,13 @@ def score_stream(model, seed: int, n_frames: int, chunk: int = 512, h: int = 256
 
 
 # ------------------------------------------------------------------------------ ranking metrics on the device
-def _anomaly_maps(model, images, map: str, sigma, truncate, calibration=None, min_std=None, morph=(), temporal=(), what: str = "scoring"):
+def _anomaly_maps(model, images, map: str, sigma, truncate, calibration=None, min_std=None, morph=(), temporal=(), what: str = "scoring",
+                  *, rank_filter=None):
     """The batch's anomaly map [B,1,H,W] of the pixel metrics: the error map or the SSIM map, through `metrics.smooth_maps` when a
     sigma is given, then - with a `calibration` - turned into its z-score in place (the map is this call's own), then through the
-    steps of `morph` (`metrics.morph_steps`), in z-score units when calibrated, then - clips [B,T,C,H,W] only, every clip a fresh
-    stream - through the steps of `temporal` (`metrics.temporal_steps`): the order is sigma, calibration, morph, temporal."""
+    steps of `rank_filter` (`metrics.rank_filter_steps`) and of `morph` (`metrics.morph_steps`), in z-score units when calibrated,
+    then - clips [B,T,C,H,W] only, every clip a fresh stream - through the steps of `temporal` (`metrics.temporal_steps`): the order
+    is sigma, calibration, rank filter, morph, temporal."""
     if temporal and images.dim() != 5:
         raise hip.VadError(f"{what}: temporal= filters the consecutive frames of clips [B,T,C,H,W]; the frames of an image batch "
                            f"{tuple(images.shape)} are not consecutive (a live camera: localize_stream(temporal_filter=))")
@@ -443,6 +449,8 @@ def _anomaly_maps(model, images, map: str, sigma, truncate, calibration=None, mi
         values = metrics.smooth_maps(values, sigma, truncate)
     if calibration is not None:
         values = calibration.normalize(values, min_std, out=values)
+    if rank_filter:
+        values = metrics.apply_rank_filter(values, rank_filter)
     if morph:
         values = metrics.apply_morph(values, morph)
     if temporal:
@@ -461,11 +469,11 @@ def _refuse_clips_on(map, what: str, verb: str) -> None:
 
 
 def _masked_maps(model, batch: dict, device, map: str, sigma, truncate, calibration, min_std, morph, key: str = "image", temporal=(),
-                 what: str = "scoring"):
+                 what: str = "scoring", rank_filter=()):
     """One batch of the mask metrics: (`_anomaly_maps` of batch[key], batch['mask']), both on the device."""
     images = batch[key].to(device)
     masks = torch.as_tensor(batch["mask"]).to(device)
-    return _anomaly_maps(model, images, map, sigma, truncate, calibration, min_std, morph, temporal, what), masks
+    return _anomaly_maps(model, images, map, sigma, truncate, calibration, min_std, morph, temporal, what, rank_filter=rank_filter), masks
 
 
 def _clip_key(batch: dict, temporal, map, what: str) -> str:
@@ -526,7 +534,7 @@ def calibrate(model, loader: Iterable[dict], device, map: str = "mse", sigma=Non
 
 
 def pixel_auroc(model, loader: Iterable[dict], device, map: str = "mse", mantissa_bits: int = 11, hist=None, sigma=None,
-                truncate: float = 4.0, calibration=None, min_std: Optional[float] = None, morph=None, temporal=None):
+                truncate: float = 4.0, calibration=None, min_std: Optional[float] = None, morph=None, temporal=None, *, rank_filter=None):
     """Pixel-level AUROC of an image model's anomaly map against the ground-truth masks - the localisation metric of MVTec-style
     datasets; the reference loads `sample['mask']` and only plots it beside the map (evaluate.py:142-171).  Batches are
     {'image', 'mask', ...} as `MVTecDataset` yields them (utils/dataset.py:150-156): mask float `[B,1,H,W]` (ToTensor: a pixel is
@@ -554,9 +562,16 @@ def pixel_auroc(model, loader: Iterable[dict], device, map: str = "mse", mantiss
     video model (map "mse"; or 'image' holding such clips).  Every clip is a fresh stream; every pixel is filtered over the last k
     frames of its clip with `metrics.temporal_maps`, LAST in the chain - sigma, calibration, morph, temporal - and before the
     histogram.  An image batch [B,C,H,W] with it is refused with `VadError`: its frames are not consecutive.  `calibrate` takes
-    none: a calibration is gathered on unfiltered maps."""
+    none: a calibration is gathered on unfiltered maps.
+    `rank_filter` (None = no rank filter, as before; keyword only): a `metrics.rank_filter_steps` spec - one step `("median", 3)` /
+    `("percentile", (3, 5), 90)` / `("rank", 3, 2)` or a list of at most four - applied with `metrics.rank_filter_maps` after the
+    calibration (in z-score units when calibrated) and immediately before `morph`: the chain is sigma, calibration, rank filter,
+    morph, temporal.  A median removes isolated hot pixels before anything ranks, thresholds or labels them, keeps step edges where
+    they are and leaves flat areas at their level.  Like the morphology it only selects values, so it commutes with a threshold.
+    `calibrate` takes none."""
     _check_map_name(map, "pixel_auroc")
     morph = metrics.morph_steps(morph)
+    rank_filter = metrics.rank_filter_steps(rank_filter)
     temporal = metrics.temporal_steps(temporal)
     min_std = _check_calibration(calibration, "pixel_auroc", map, sigma, truncate, min_std)
     if hist is None:
@@ -564,14 +579,15 @@ def pixel_auroc(model, loader: Iterable[dict], device, map: str = "mse", mantiss
     with torch.no_grad():
         for batch in loader:
             key = _clip_key(batch, temporal, map, "pixel_auroc")
-            hist.accumulate(*_masked_maps(model, batch, device, map, sigma, truncate, calibration, min_std, morph, key, temporal, "pixel_auroc"))
+            hist.accumulate(*_masked_maps(model, batch, device, map, sigma, truncate, calibration, min_std, morph, key, temporal, "pixel_auroc",
+                                          rank_filter))
     auroc, tie_bound = hist.auroc()
     return auroc, tie_bound, hist
 
 
 def pixel_aupro(model, loader: Iterable[dict], device, map: str = "mse", fpr_limit: float = 0.3, mantissa_bits: int = 11, hist=None,
                 connectivity: int = 8, sigma=None, truncate: float = 4.0, calibration=None, min_std: Optional[float] = None, morph=None,
-                temporal=None):
+                temporal=None, *, rank_filter=None):
     """Per-region overlap (AUPRO) of an image model's anomaly map against the ground-truth masks: every connected anomalous region
     of the masks weighs the same, and the curve is integrated up to a false-positive rate of `fpr_limit` - the localisation metric
     of the MVTec evaluation, where pixel AUROC is dominated by the large defects.  The loop of `pixel_auroc` (same batches, same
@@ -580,9 +596,10 @@ def pixel_aupro(model, loader: Iterable[dict], device, map: str = "mse", fpr_lim
     on the device; the only host read is the counters, once, at the end.  Returns (aupro, quant_bound, weight_bound, hist)
     (`metrics.aupro_from_counts`); pass `hist` to continue an earlier evaluation or to all-reduce before reading, in which case
     its own mantissa_bits and connectivity apply.  `hist.auroc()` is the pixel AUROC of the same evaluation.  `calibration`,
-    `min_std`, `morph`, `temporal` as in `pixel_auroc`."""
+    `min_std`, `morph`, `temporal`, `rank_filter` as in `pixel_auroc`."""
     _check_map_name(map, "pixel_aupro")
     morph = metrics.morph_steps(morph)
+    rank_filter = metrics.rank_filter_steps(rank_filter)
     temporal = metrics.temporal_steps(temporal)
     min_std = _check_calibration(calibration, "pixel_aupro", map, sigma, truncate, min_std)
     if hist is None:
@@ -590,7 +607,8 @@ def pixel_aupro(model, loader: Iterable[dict], device, map: str = "mse", fpr_lim
     with torch.no_grad():
         for batch in loader:
             key = _clip_key(batch, temporal, map, "pixel_aupro")
-            maps, masks = _masked_maps(model, batch, device, map, sigma, truncate, calibration, min_std, morph, key, temporal, "pixel_aupro")
+            maps, masks = _masked_maps(model, batch, device, map, sigma, truncate, calibration, min_std, morph, key, temporal, "pixel_aupro",
+                                       rank_filter)
             if temporal:                                                      # clips: every frame's regions on their own, [B*T,1,H,W]
                 maps, masks = maps.flatten(0, 1), masks.reshape(maps.shape[0] * maps.shape[1], *masks.shape[-3:])
             hist.accumulate(maps, masks)
@@ -600,7 +618,7 @@ def pixel_aupro(model, loader: Iterable[dict], device, map: str = "mse", fpr_lim
 
 def detection_report(model, loader: Iterable[dict], device, threshold: float, map: str = "mse", sigma=None, truncate: float = 4.0,
                      calibration=None, min_std: Optional[float] = None, morph=(), connectivity: int = 8, min_area: int = 1,
-                     gt_fraction: float = 0.0, pred_fraction: float = 0.0, counts=None, temporal=None):
+                     gt_fraction: float = 0.0, pred_fraction: float = 0.0, counts=None, temporal=None, *, rank_filter=None):
     """What an operating point does against the ground-truth masks: how many of the labelled defects it finds, how many false
     alarms per frame it raises, which pixel IoU it reaches - the questions AUROC and AUPRO, which rank pixels over all thresholds and
     know nothing of `min_area` or of regions as units, do not answer.  The loop of `pixel_aupro`, over the same batches: {'image'
@@ -613,10 +631,12 @@ def detection_report(model, loader: Iterable[dict], device, threshold: float, ma
     `metrics.DetectionCounts`); pass `counts` to continue an earlier evaluation or to all-reduce before reading
     (`counts.all_reduce()`, then `counts.report()`) - counters gathered at another operating point are refused with `ValueError`.
     `temporal` as in `pixel_auroc`: video batches only, every clip a fresh stream, after `morph` and before the threshold; it is part
-    of the operating point the counters are gathered at."""
+    of the operating point the counters are gathered at.  `rank_filter` as in `pixel_auroc` (after the calibration, before `morph`),
+    and part of the operating point likewise."""
     what = "detection_report"
     _check_map_name(map, what)
     morph = metrics.morph_steps(None if morph == () else morph)          # () = no morphology, like None elsewhere
+    rank_filter = metrics.rank_filter_steps(rank_filter)
     temporal = metrics.temporal_steps(temporal)
     min_std = _check_calibration(calibration, what, map, sigma, truncate, min_std)
     params = metrics._match_params(what, threshold, connectivity, min_area, gt_fraction, pred_fraction)
@@ -624,6 +644,8 @@ def detection_report(model, loader: Iterable[dict], device, threshold: float, ma
                 min_std=None if calibration is None else float(min_std))
     if temporal:
         meta["temporal"] = tuple(temporal)
+    if rank_filter:
+        meta["rank_filter"] = tuple(rank_filter)
     if counts is None:
         counts = metrics.DetectionCounts(device)
     elif not isinstance(counts, metrics.DetectionCounts):
@@ -635,13 +657,13 @@ def detection_report(model, loader: Iterable[dict], device, threshold: float, ma
             if video and map != "mse":
                 _refuse_clips_on(map, what, "reported")
             maps, masks = _masked_maps(model, batch, device, map, sigma, truncate, calibration, min_std, morph, "frames" if video else "image",
-                                       temporal, what)
+                                       temporal, what, rank_filter)
             counts.update(metrics.match_regions(maps, masks, threshold, connectivity, min_area, gt_fraction, pred_fraction, max_regions=1), meta)
     return counts.report(), counts
 
 
 def frame_auroc(model, loader: Iterable[dict], device, hist=None, mantissa_bits: int = 11, reduce=None, sigma=None, truncate: float = 4.0,
-                calibration=None, min_std: Optional[float] = None, morph=None, temporal=None):
+                calibration=None, min_std: Optional[float] = None, morph=None, temporal=None, *, rank_filter=None):
     """Frame-level AUROC of a video model (evaluate_video.py:171-176) without gathering the scores: the clip loop of
     `score_clips(per_frame=True)` - batches {'frames' [B,T,C,H,W], 'frame_labels' [B,T], ...} -, each batch's frame scores and
     labels going into a histogram on the device.  Returns (auroc, tie_bound, hist); ranks of a sharded evaluation call
@@ -650,9 +672,11 @@ def frame_auroc(model, loader: Iterable[dict], device, hist=None, mantissa_bits:
     a `frame_scores` spec - "max", ("topk", fraction), ("quantile", q), ("rank", k) -; the frame scores are then those of
     `frame_scores(model, frames, reduce, "mse", sigma, truncate, calibration, min_std, morph)`, reduced from the error maps on the
     device, and go into the same histogram (which bins scores >= 0: a calibrated score below 0 is counted in `hist.rejected()`).
-    `temporal` as in `frame_scores` (it filters maps, so it needs a `reduce`: `VadError` without one)."""
+    `temporal` and `rank_filter` as in `frame_scores` (they filter maps, so they need a `reduce`: `VadError` without one)."""
     if metrics.temporal_steps(temporal) and reduce is None:
         raise hip.VadError("frame_auroc: temporal= filters the error maps before they are reduced; pass a reduce (\"max\", (\"topk\", f), ...)")
+    if metrics.rank_filter_steps(rank_filter) and reduce is None:
+        raise hip.VadError("frame_auroc: rank_filter= filters the error maps before they are reduced; pass a reduce (\"max\", (\"topk\", f), ...)")
     if reduce is not None:
         metrics.reduce_spec(reduce, "frame_auroc")
         metrics.morph_steps(morph)
@@ -666,14 +690,15 @@ def frame_auroc(model, loader: Iterable[dict], device, hist=None, mantissa_bits:
             if reduce is None:
                 scores = model.score_seq_and_frames(frames)["frame"]
             else:
-                scores, _ = frame_scores(model, frames, reduce, "mse", sigma, truncate, calibration, min_std, morph, temporal)
+                scores, _ = frame_scores(model, frames, reduce, "mse", sigma, truncate, calibration, min_std, morph, temporal,
+                                         rank_filter=rank_filter)
             hist.accumulate(scores, labels)
     auroc, tie_bound = hist.auroc()
     return auroc, tie_bound, hist
 
 
 def localize(model, images, threshold: float, map: str = "mse", sigma=None, truncate: float = 4.0, connectivity: int = 8,
-             min_area: int = 1, max_regions: int = 64, calibration=None, min_std: Optional[float] = None, morph=None):
+             min_area: int = 1, max_regions: int = 64, calibration=None, min_std: Optional[float] = None, morph=None, *, rank_filter=None):
     """Detections of one batch: the model's anomaly maps and the connected regions of `map >= threshold` in them - where the
     reference paints the map (evaluate.py:142-171, main.py:231-250) and compares one scalar with a constant (main.py:282-283).
     `images`: `[B,C,H,W]` frames for the image model, `[B,T,C,H,W]` clips for the video model (map "mse" only; every frame of a
@@ -685,20 +710,24 @@ def localize(model, images, threshold: float, map: str = "mse", sigma=None, trun
     the normal frames), the regions are those of `z >= threshold`, and the maps returned are the z-score maps.
     `morph` as in `pixel_auroc` (one `metrics.morph_maps` launch per step, last in the chain): the regions are those of the morphed
     maps - `("open", 2)` drops single-pixel speckle before it is labelled, where `min_area` drops it after and cannot cut a
-    one-pixel bridge between two defects - and the maps returned are the morphed maps."""
+    one-pixel bridge between two defects - and the maps returned are the morphed maps.
+    `rank_filter` as in `pixel_auroc` (one `metrics.rank_filter_maps` launch per step, after the calibration and immediately before
+    `morph`): `("median", 3)` removes isolated hot pixels like an opening, but leaves the corners and thin parts of a real defect and
+    the level of flat areas alone; the maps returned are the filtered maps."""
     _check_map_name(map, "localize")
     morph = metrics.morph_steps(morph)
+    rank_filter = metrics.rank_filter_steps(rank_filter)
     if images.dim() == 5 and map != "mse":
         _refuse_clips_on(map, "localize", "localised")
     min_std = _check_calibration(calibration, "localize", map, sigma, truncate, min_std)
     with torch.no_grad():
-        maps = _anomaly_maps(model, images, map, sigma, truncate, calibration, min_std, morph)
+        maps = _anomaly_maps(model, images, map, sigma, truncate, calibration, min_std, morph, rank_filter=rank_filter)
         return metrics.detect_regions(maps, threshold, connectivity, min_area, max_regions), maps
 
 
 def localize_events(model, images, threshold: float, map: str = "mse", sigma=None, truncate: float = 4.0, calibration=None,
                     min_std: Optional[float] = None, connectivity: int = 8, temporal: int = 9, min_duration: int = 1, min_volume: int = 1,
-                    max_events: int = 64, morph=None, temporal_filter=None, tracks: bool = False):
+                    max_events: int = 64, morph=None, temporal_filter=None, tracks: bool = False, *, rank_filter=None):
     """`localize` with the event table: the model's anomaly maps and the events of `map >= threshold` in them - regions linked
     across consecutive frames (`metrics.detect_events`), so that a line alarms on what persists (`min_duration`) and not on one
     noisy map.  `images`: `[B,T,C,H,W]` clips for the video model (map "mse" only), every clip its own volume; `[N,C,H,W]` frames
@@ -712,17 +741,20 @@ def localize_events(model, images, threshold: float, map: str = "mse", sigma=Non
     `("min", 2)` in front of the labeller removes what differs from frame to frame.
     `tracks=True`: the labels are requested from `detect_events` and ONE `metrics.event_tracks` call follows; `events.tracks` is then
     a `metrics.EventTracks` - a box, a peak and a centroid per kept event and frame - and `events.labels` the label volume.  The
-    default leaves launches and outputs as they are (`events.tracks` is None)."""
+    default leaves launches and outputs as they are (`events.tracks` is None).
+    `rank_filter` as in `localize`: every frame filtered on its own, after the calibration and immediately before `morph`."""
     _check_map_name(map, "localize_events")
     if not isinstance(tracks, bool):
         raise hip.VadError(f"localize_events: tracks must be a bool, got {tracks!r}")
     morph = metrics.morph_steps(morph)
+    rank_filter = metrics.rank_filter_steps(rank_filter)
     temporal_filter = metrics.temporal_steps(temporal_filter)
     if images.dim() == 5 and map != "mse":
         _refuse_clips_on(map, "localize_events", "localised")
     min_std = _check_calibration(calibration, "localize_events", map, sigma, truncate, min_std)
     with torch.no_grad():
-        maps = _anomaly_maps(model, images, map, sigma, truncate, calibration, min_std, morph, temporal_filter, "localize_events")
+        maps = _anomaly_maps(model, images, map, sigma, truncate, calibration, min_std, morph, temporal_filter, "localize_events",
+                             rank_filter=rank_filter)
         volumes = maps if maps.dim() == 5 else maps[:, 0]                 # [B,T,1,H,W], or the image batch as one clip [N,H,W]
         events = metrics.detect_events(volumes, threshold, connectivity, temporal, min_duration, min_volume, max_events, return_labels=tracks)
         if tracks:
@@ -731,7 +763,7 @@ def localize_events(model, images, threshold: float, map: str = "mse", sigma=Non
 
 
 def localize_stream(model, frames, tracker, state=None, sigma=None, truncate: float = 4.0, calibration=None, min_std: Optional[float] = None,
-                    morph=None, temporal_filter=None, boxes: bool = False):
+                    morph=None, temporal_filter=None, boxes: bool = False, *, rank_filter=None):
     """One step of a live stream with events carried between calls (`metrics.EventTracker`): the newest
     frames are scored, their error maps smoothed and calibrated as in `localize_events`, and handed to `tracker.update`.
     Video model: `frames` `[B,T,C,H,W]` (or the uint8 layouts `score_stateful` takes) are the next T frames of B streams; ONE
@@ -746,8 +778,11 @@ def localize_stream(model, frames, tracker, state=None, sigma=None, truncate: fl
     see what `localize_events(temporal=)` sees on the whole stream, however its frames are split over calls.  Both models: the image
     model's `[B,1,H,W]` is one new frame of B cameras.  The maps returned are the filtered maps.  Reset it with the tracker.
     `boxes` is handed to `tracker.update`: with True, `update.boxes` holds the cross-section of every open event in the newest frame
-    (`metrics.TrackBoxes`), and `update.boxes_alarming()` which of them alarm now."""
+    (`metrics.TrackBoxes`), and `update.boxes_alarming()` which of them alarm now.
+    `rank_filter` as in `localize` (after the calibration, immediately before `morph`): every frame is filtered on its own, so the
+    result does not depend on how the frames are split over calls."""
     morph = metrics.morph_steps(morph)
+    rank_filter = metrics.rank_filter_steps(rank_filter)
     if temporal_filter is not None and not isinstance(temporal_filter, metrics.TemporalFilter):
         raise hip.VadError(f"localize_stream: temporal_filter must be a metrics.TemporalFilter, got {type(temporal_filter).__name__}")
     if not isinstance(tracker, metrics.EventTracker):
@@ -766,6 +801,8 @@ def localize_stream(model, frames, tracker, state=None, sigma=None, truncate: fl
             maps = metrics.smooth_maps(maps, sigma, truncate)
         if calibration is not None:
             maps = calibration.normalize(maps, min_std, out=maps)
+        if rank_filter:
+            maps = metrics.apply_rank_filter(maps, rank_filter)
         if morph:
             maps = metrics.apply_morph(maps, morph)
         if temporal_filter is not None:                                   # [B,T,1,H,W] as it stands; [B,1,H,W] = B streams x 1 frame
