@@ -1130,6 +1130,71 @@ int vad_detect_events(const float* maps, long long b, int t, int h, int w, float
                       uint32_t* frame_counts /* [b, t, 3] */, void* ws, size_t ws_bytes, void* stream);
 int vad_events_plan(int* label_round, int* volume_round, int* scan_round, int* reduce_round, int* threads);
 
+/* ------------------------------------------------------------------ Events against ground-truth masks (csrc/map_event_match.hip)
+ * What a debounced alarm is accepted on: how many of the labelled anomalies it still finds, how many false-alarm events it raises,
+ * how many frames after a defect appears it fires.  The kept events of vad_detect_events joined with the connected tracks of the
+ * clip's mask volume - vad_match_regions in three dimensions; maps, masks and both labellings stay on the device.  Everything is an
+ * integer, per clip.
+ *
+ * vad_match_events: maps = b clips of t frames of h x w fp32 with the limits of vad_detect_events; masks = b x t x h x w elements
+ * in mask_format - VAD_LBL_U8_ELEM (anomalous iff >= 128) or VAD_LBL_F32_ELEM (iff > 0.5; 4-byte aligned).  The predictions are the
+ * events of vad_detect_events for the same threshold, connectivity and temporal (foreground is v >= threshold; a NaN voxel never is
+ * and is counted); those that pass min_duration and min_volume are KEPT, and P is the set of their voxels: a dropped event
+ * contributes nothing, its voxels count as background everywhere below.  G is the set of the masks' anomalous voxels; its connected
+ * components under the same (connectivity, temporal) structure are the ground-truth TRACKS, and all of them count.  Clips never
+ * link.
+ *     a track g        hit(g) = |g & P|;      DETECTED iff hit >= 1     and (double)hit     >= gt_fraction   * (double)volume
+ *     a kept event p   overlap(p) = |p & G|;  MATCHED  iff overlap >= 1 and (double)overlap >= pred_fraction * (double)volume
+ * - one IEEE double multiply and one compare, no fused multiply-add, no division, as in vad_match_regions.  Overlap is shared
+ * voxels: adjacency in space or in time is none.  A kept event that is not matched is a false alarm.  The DELAY of a detected track
+ * is the first frame of a shared voxel minus the track's first frame.
+ * gt_records, pred_records uint32 [b, max_events, VAD_EVMATCH_WORDS], 16-byte aligned; one track or event is
+ *     word 0       root: the smallest volume index t * h * w + y * w + x
+ *     word 1       volume in voxels
+ *     words 2-3    t0, t1: first and last frame, inclusive
+ *     word 4       hit (gt_records) or overlap (pred_records)
+ *     words 5-6    first and last frame of a shared voxel; both 0xffffffff when word 4 is 0
+ *     word 7       flags: bit 0 = detected (gt_records) or matched (pred_records)
+ * both in ascending order of their roots - scipy.ndimage.label's numbering of a 3-D array; the first min(count, max_events) are
+ * written (max_events in 1 .. 65536), every other record is all-zero.  pred_records words 0-3 are vad_detect_events' words 0-3 for
+ * the same arguments.
+ * counts uint64 [b, VAD_EVMATCH_COUNTS], 8-byte aligned, per clip:
+ *     words 0-1    tracks; detected tracks
+ *     words 2-4    kept events; matched events; false-alarm events (word 2 - word 3)
+ *     word 5       events dropped by a filter
+ *     words 6-9    voxels of P & G, of P \ G, of G \ P, of neither
+ *     word 10      NaN voxels of the maps (they fall into words 8 or 9 by their mask)
+ *     word 11      |G|
+ *     word 12      the sum of the delays of the detected tracks
+ *     word 13      detected tracks with delay 0
+ *     words 14-17  frames with voxels of G and of P; of P only (false-alarm frames); of G only (missed frames); of neither
+ *     words 18-21  the clip's class, one-hot: tracks and kept events; kept events only; tracks only; neither
+ * The track and event counters are the full numbers, which may exceed max_events: truncation is visible.  Every word sums over
+ * clips, batches and ranks.
+ * frame_counts uint32 [b, t, 4], 4-byte aligned: voxels of P & G, of P \ G, of G \ P and NaN voxels of the frame; word 0 + word 1
+ * is vad_detect_events' frame_counts word 1.
+ * Integer atomics, min and max only: all four outputs are the same words for any batching of clips, launch order or tiling.  Every
+ * walk of the union-find is bounded as in vad_detect_events; one that runs out of its budget sets bit 0 of the flag word.
+ * ws: caller-provided, 16-byte aligned, vad_event_match_workspace_bytes(b, t, h, w) bytes (0 for arguments out of range; no device
+ * is needed): 16 bytes for the flag word - the first uint32; the second uint32 is what the in-frame labelling of the masks
+ * reported, folded into the first -, 4 bytes per chunk of 1024 voxels of every clip for the events and again for the tracks (each
+ * padded to 16), then 48 bytes per voxel: 4 each for labels, sizes and last frames of the events, the same three of the tracks,
+ * then hit, first and last shared frame at the tracks' roots and overlap, first and last shared frame at the events' roots.
+ * vad_event_match_plan reports the pixels one grid round of each pass covers (the labeller inside a frame; rebase, link, flatten
+ * and init over a clip's volume; the count / slot scan; the join) and the threads of a work-group.
+ * VAD_ERR_ARG for what vad_detect_events refuses, an unknown mask_format, misaligned float masks and a fraction that is NaN or
+ * outside [0, 1]; VAD_ERR_WS for a short workspace.  b == 0 clears the flag word only.  Every launch is asynchronous on `stream`;
+ * nothing is allocated, the host never waits, the call can be captured into a graph. */
+#define VAD_EVMATCH_WORDS 8
+#define VAD_EVMATCH_COUNTS 22
+size_t vad_event_match_workspace_bytes(long long b, int t, int h, int w);
+int vad_event_match_plan(int* label_round, int* volume_round, int* scan_round, int* join_round, int* threads);
+int vad_match_events(const float* maps, const void* masks, int mask_format, long long b, int t, int h, int w, float threshold,
+                     int connectivity, int temporal, unsigned min_duration, unsigned min_volume, double gt_fraction,
+                     double pred_fraction, int max_events, uint32_t* gt_records /* [b, max_events, 8] */,
+                     uint32_t* pred_records /* [b, max_events, 8] */, uint64_t* counts /* [b, 22] */,
+                     uint32_t* frame_counts /* [b, t, 4] */, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ Anomaly events across the calls of a live stream (csrc/map_track.hip)
  * The events of vad_detect_events, continued frame by frame: a stream is the sequence of its maps [h, w] since the last init, an
  * event a connected component of {v >= threshold} in the stream's volume so far - same predicate, same three structures

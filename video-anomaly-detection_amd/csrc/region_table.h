@@ -1,5 +1,5 @@
 // What the region consumers build behind the labeller of region_label.h (csrc/map_regions.hip, csrc/map_match.hip,
-// csrc/map_events.hip, csrc/map_track.hip): one copy of the wave-level election and combination, of the accumulator of a record's
+// csrc/map_events.hip, csrc/map_event_match.hip, csrc/map_track.hip): one copy of the wave-level election and combination, of the accumulator of a record's
 // box, peak and coordinate sums, of the raster-order rank of roots over chunks, of the 3 x 3 ring, and of the host-side chunk
 // arithmetic.  Not part of the C ABI; everything here is inlined into the kernels that use it.
 //

@@ -1,4 +1,4 @@
-// Argument checks of the anomaly-map entry points (score_hist, region_overlap, map_regions, map_match, map_events, map_track,
+// Argument checks of the anomaly-map entry points (score_hist, region_overlap, map_regions, map_match, map_events, map_event_match, map_track,
 // map_smooth, map_morph, map_stats): one copy of every check that three or more entry points word the same way; a check that one
 // or two make stays written out where it is made.  Host code only, all of it runs before an entry point's first HIP call.  `who`
 // is the entry point's name in the message, `name` the argument's.  A helper returns VAD_OK or what vad_fail returned (a ?: b:
@@ -43,7 +43,7 @@ static inline int vad_req_map_hw(const char* who, int h, int w) {
 }
 static inline int vad_req_map_dims(const char* who, long long n, int h, int w) { return vad_req_map_n(who, n) ?: vad_req_map_hw(who, h, w) ?: vad_req_map_total(who, n, h, w); }
 
-// ---- dims of the labelling family (label_regions, pro_accumulate, detect_regions, match_regions, detect_events): n >= 0 frames
+// ---- dims of the labelling family (label_regions, pro_accumulate, detect_regions, match_regions, detect_events, match_events): n >= 0 frames
 // (`name`: n or b) of h x w < 2^31 - 1 pixels, n * h * w <= 2^38 (a work-group's run of a 256-group launch stays below 2^32);
 // *total = n * h * w.  One helper per check: the entry points check other arguments between them.
 static inline bool vad_label_hw_ok(int h, int w) { return h >= 1 && w >= 1 && (long long)h * w < 2147483647ll; }

@@ -16,7 +16,7 @@ PKG_DIR = Path(__file__).resolve().parent
 REPO_DIR = PKG_DIR.parent
 CSRC = PKG_DIR / "csrc"
 LIB_PATH = Path(os.environ.get("VAD_LIB", PKG_DIR / "libvad_hip.so"))
-SOURCES = ["conv_mfma.hip", "conv_wino.hip", "dec4_fused.hip", "tail.hip", "wide_io.hip", "state_io.hip", "resize_u8.hip", "frame_gather.hip", "score_hist.hip", "region_overlap.hip", "map_regions.hip", "map_match.hip", "map_events.hip", "map_track.hip", "map_event_tracks.hip", "map_smooth.hip", "map_topk.hip", "map_morph.hip", "map_rankfilt.hip", "map_temporal.hip", "map_stats.hip", "ssim.hip", "train_ops.hip", "wgrad.hip", "train_step.hip", "train_step_img.hip", "vad_api.hip", "pack.cpp"]
+SOURCES = ["conv_mfma.hip", "conv_wino.hip", "dec4_fused.hip", "tail.hip", "wide_io.hip", "state_io.hip", "resize_u8.hip", "frame_gather.hip", "score_hist.hip", "region_overlap.hip", "map_regions.hip", "map_match.hip", "map_events.hip", "map_event_match.hip", "map_track.hip", "map_event_tracks.hip", "map_smooth.hip", "map_topk.hip", "map_morph.hip", "map_rankfilt.hip", "map_temporal.hip", "map_stats.hip", "ssim.hip", "train_ops.hip", "wgrad.hip", "train_step.hip", "train_step_img.hip", "vad_api.hip", "pack.cpp"]
 
 VAD_OK = 0
 ABI_VERSION = 3
@@ -56,6 +56,8 @@ MATCH_WORDS = 4           # VAD_MATCH_WORDS: uint32 words of one record of vad_m
 MATCH_COUNTS = 16         # VAD_MATCH_COUNTS: uint64 counters per frame of vad_match_regions
 EVENT_WORDS = 16          # VAD_EVENT_WORDS: uint32 words of one record of vad_detect_events
 MAX_EVENTS = 65536        # largest max_events of vad_detect_events
+EVMATCH_WORDS = 8         # VAD_EVMATCH_WORDS: uint32 words of one record of vad_match_events
+EVMATCH_COUNTS = 22       # VAD_EVMATCH_COUNTS: uint64 counters per clip of vad_match_events
 TRACK_WORDS = 20          # VAD_TRACK_WORDS: uint32 words of one record of vad_track_events
 TRACK_HEADER_WORDS = 16   # the header of one stream's tracker state: frames, open, lost in total, flags, magic, h, w, max_open, zeros
 TRACK_MAX_OPEN = 65536    # largest max_open / max_closed of vad_track_events
@@ -97,8 +99,10 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     # map_stats.hip: the float64 sums of the per-pixel statistics and the fp32 z-score likewise (tests/map_stats_ref.py)
     # map_match.hip: the fraction tests are one double multiply and one compare (tests/match_ref.py)
     # map_temporal.hip: the exponential average is a subtraction, a product and a sum, each rounded (tests/map_temporal_ref.py)
+    # map_event_match.hip: the fraction tests of map_match.hip (tests/event_match_ref.py)
     extra = {"pack.cpp": ["-ffp-contract=off"], "map_smooth.hip": ["-ffp-contract=off"], "map_stats.hip": ["-ffp-contract=off"],
-             "map_match.hip": ["-ffp-contract=off"], "map_temporal.hip": ["-ffp-contract=off"]}
+             "map_match.hip": ["-ffp-contract=off"], "map_temporal.hip": ["-ffp-contract=off"],
+             "map_event_match.hip": ["-ffp-contract=off"]}
 
     def compile_one(src: Path) -> Path:
         obj = objdir / (src.name + ".o")
@@ -344,6 +348,11 @@ SIGNATURES = {
     "vad_events_workspace_bytes": (_sz, [_ll, _i, _i, _i, _i]),
     "vad_detect_events": (_i, [_vp, _ll, _i, _i, _i, _f, _i, _i, C.c_uint, C.c_uint, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vad_events_plan": (_i, [C.POINTER(_i)] * 5),
+    # events against ground-truth masks: tracks found, false-alarm events, delay (csrc/map_event_match.hip)
+    "vad_event_match_workspace_bytes": (_sz, [_ll, _i, _i, _i]),
+    "vad_event_match_plan": (_i, [C.POINTER(_i)] * 5),
+    "vad_match_events": (_i, [_vp, _vp, _i, _ll, _i, _i, _i, _f, _i, _i, C.c_uint, C.c_uint, C.c_double, C.c_double, _i, _vp, _vp, _vp, _vp,
+                              _vp, _sz, _vp]),
     # anomaly events across the calls of a live stream (csrc/map_track.hip)
     "vad_track_state_bytes": (_sz, [_ll, _i, _i, _i]),
     "vad_track_workspace_bytes": (_sz, [_ll, _i, _i, _i, _i]),

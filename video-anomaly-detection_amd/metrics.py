@@ -1930,6 +1930,240 @@ def detect_events(maps: torch.Tensor, threshold: float, connectivity: int = 8, t
     return result(records, counts, frame_counts, labels)
 
 
+# ====================================================================== events against ground-truth masks
+# `match_regions` in three dimensions: the per-frame report cannot see `min_duration`, `min_volume` or the
+# links in time at all.  The kept events of `detect_events` are joined with the connected tracks of the clip's mask volume: how many
+# labelled anomalies the debounced alarm still finds, how many false-alarm events it raises, how many frames after a defect appears
+# it fires.  The host route copies every map and mask volume and runs a 3-D scipy.ndimage.label of both, sum_labels and minimum.
+EVMATCH_WORDS = hip.EVMATCH_WORDS
+EVMATCH_COUNTS = hip.EVMATCH_COUNTS
+EVENT_COUNT_NAMES = ("gt_tracks", "gt_detected", "pred_events", "pred_matched", "false_alarm_events", "pred_dropped", "voxel_tp", "voxel_fp",
+                     "voxel_fn", "voxel_tn", "nan_voxels", "gt_voxels", "delay_sum", "immediate_tracks", "frames_gt_pred", "frames_pred_only",
+                     "frames_gt_only", "frames_neither", "clips_gt_pred", "clips_pred_only", "clips_gt_only", "clips_neither")
+_NO_FRAME = -1                 # words 5-6 of a record without a shared voxel: 0xffffffff as int32
+
+
+class EventMatches:
+    """What `match_events` returns, as device tensors with the leading shape of the clips (`[B]`, or `()` for one volume):
+
+      gt_records    int32 [..., E, 8]: the mask volume's tracks - root, volume, t0, t1, hit = voxels shared with kept events, first and
+                    last frame of a shared voxel (-1 without one), flags (bit 0: detected) - in ascending order of their first voxel,
+                    E = max_events, all-zero records behind them
+      pred_records  int32 [..., E, 8]: the kept events - root, volume, t0, t1, overlap = voxels shared with the masks, first and last
+                    frame of a shared voxel, flags (bit 0: matched; a kept event that is not matched is a false alarm)
+      counts        int64 [..., 22]: the words of `vad_match_events` (include/vad_hip.h), named by `EVENT_COUNT_NAMES`; the track and
+                    event counters are the full numbers, so a truncated table is visible
+      frame_counts  int32 [..., T, 4]: voxels of P & G, P \\ G, G \\ P and NaN voxels of the frame
+
+    Views of the records (no copies): `gt_volume`, `gt_hit`, `pred_volume`, `pred_overlap` int32 [..., E]."""
+
+    def __init__(self, gt_records: torch.Tensor, pred_records: torch.Tensor, counts: torch.Tensor, frame_counts: torch.Tensor,
+                 volume_shape: Tuple[int, int, int], params: dict):
+        self.gt_records, self.pred_records, self.counts, self.frame_counts = gt_records, pred_records, counts, frame_counts
+        self.volume_shape, self.params = volume_shape, dict(params)
+        self.max_events = int(gt_records.shape[-2])
+
+    gt_volume = property(lambda self: self.gt_records[..., 1])
+    gt_hit = property(lambda self: self.gt_records[..., 4])
+    pred_volume = property(lambda self: self.pred_records[..., 1])
+    pred_overlap = property(lambda self: self.pred_records[..., 4])
+
+    def detected(self) -> torch.Tensor:
+        """bool [..., E]: the track of the record is detected (False for the all-zero records)."""
+        return (self.gt_records[..., 7] & 1) != 0
+
+    def matched(self) -> torch.Tensor:
+        """bool [..., E]: the kept event of the record is matched; a record in use that is not is a false alarm."""
+        return (self.pred_records[..., 7] & 1) != 0
+
+    def delays(self) -> torch.Tensor:
+        """int32 [..., E]: first shared frame - t0 of the detected tracks, -1 for every other record."""
+        return torch.where(self.detected(), self.gt_records[..., 5] - self.gt_records[..., 2], torch.full_like(self.gt_records[..., 5], -1))
+
+    def alarms(self) -> torch.Tensor:
+        """bool [..., T]: the frame holds a voxel of a kept event - `Events.alarms()` of the same operating point."""
+        return (self.frame_counts[..., 0] + self.frame_counts[..., 1]) > 0
+
+    def truncated(self) -> torch.Tensor:
+        """bool [...]: the clip has more tracks or more kept events than a table has records."""
+        return (self.counts[..., 0] > self.max_events) | (self.counts[..., 2] > self.max_events)
+
+    def to_list(self) -> list:
+        """A host copy of the tables - 32 bytes per record, never a map -: one dict per clip {'gt': [{'root', 'volume', 't0', 't1',
+        'hit', 'first_hit', 'last_hit', 'detected', 'delay'}], 'pred': [{'root', 'volume', 't0', 't1', 'overlap', 'first_overlap',
+        'last_overlap', 'matched'}], 'counts': {name: int}} in table order; a frame that does not exist is None."""
+        gt = self.gt_records.reshape(-1, self.max_events, EVMATCH_WORDS).cpu().numpy()
+        pred = self.pred_records.reshape(-1, self.max_events, EVMATCH_WORDS).cpu().numpy()
+        counts = self.counts.reshape(-1, EVMATCH_COUNTS).cpu().numpy()
+
+        def frame(v):
+            return None if int(v) == _NO_FRAME else int(v)
+
+        out = []
+        for c in range(counts.shape[0]):
+            out.append({"gt": [{"root": int(r[0]), "volume": int(r[1]), "t0": int(r[2]), "t1": int(r[3]), "hit": int(r[4]), "first_hit": frame(r[5]),
+                                "last_hit": frame(r[6]), "detected": bool(r[7] & 1), "delay": int(r[5]) - int(r[2]) if r[7] & 1 else None}
+                               for r in gt[c, :min(int(counts[c, 0]), self.max_events)]],
+                        "pred": [{"root": int(r[0]), "volume": int(r[1]), "t0": int(r[2]), "t1": int(r[3]), "overlap": int(r[4]),
+                                  "first_overlap": frame(r[5]), "last_overlap": frame(r[6]), "matched": bool(r[7] & 1)}
+                                 for r in pred[c, :min(int(counts[c, 2]), self.max_events)]],
+                        "counts": {name: int(v) for name, v in zip(EVENT_COUNT_NAMES, counts[c])}})
+        return out
+
+
+def _event_match_params(what: str, threshold, connectivity, temporal, min_duration, min_volume, gt_fraction, pred_fraction) -> dict:
+    """The checked operating point of `match_events` / `EventCounts`: what two sets of counters must share to be added."""
+    connectivity, temporal = _check_structure(connectivity, temporal, what)
+    return {"threshold": _check_threshold(threshold, what), "connectivity": connectivity, "temporal": temporal,
+            "min_duration": _check_int(min_duration, "min_duration", what, 1, 2 ** 32 - 1),
+            "min_volume": _check_int(min_volume, "min_volume", what, 1, 2 ** 32 - 1),
+            "gt_fraction": _check_fraction(gt_fraction, "gt_fraction", what), "pred_fraction": _check_fraction(pred_fraction, "pred_fraction", what)}
+
+
+def match_events(maps: torch.Tensor, masks: torch.Tensor, threshold: float, connectivity: int = 8, temporal: int = 9, min_duration: int = 1,
+                 min_volume: int = 1, gt_fraction: float = 0.0, pred_fraction: float = 0.0, max_events: int = 64) -> EventMatches:
+    """The events of `maps >= threshold` held against the ground-truth `masks`, on the GPU (`vad_match_events`,
+    csrc/map_event_match.hip).  `maps`: float32 GPU tensor `[B,T,H,W]`, `[B,T,1,H,W]` or one volume `[T,H,W]` as in `detect_events`;
+    `masks`: a GPU tensor with as many elements and the same `B` (`T` for one volume), `H`, `W`, in the formats of `match_regions`
+    (float: anomalous iff > 0.5; uint8: iff >= 128; bool and other integers: iff non-zero).  The predictions are the events of
+    `detect_events` with the same `threshold`, `connectivity`, `temporal`, `min_duration` and `min_volume`; a dropped event counts as
+    background.  The connected components of the mask volume under the same structure are the ground-truth tracks; all of them
+    count.  A track is DETECTED iff it shares at least one voxel, and at least `gt_fraction` of its volume, with the kept events; a
+    kept event is MATCHED iff it shares at least one voxel, and at least `pred_fraction` of its volume, with the masks - otherwise
+    it is a false alarm.  The delay of a detected track is the first frame of a shared voxel minus its first frame.  Touching, in
+    space or in time, is no overlap; clips never link.  Returns an `EventMatches`; like `detect_events` it reads the kernels' flag
+    word (one 4-byte copy, which waits for the call) and raises VadError if it is set.  No CPU fallback."""
+    what = "match_events"
+    params = _event_match_params(what, threshold, connectivity, temporal, min_duration, min_volume, gt_fraction, pred_fraction)
+    if not isinstance(maps, torch.Tensor) or not isinstance(masks, torch.Tensor):
+        raise hip.VadError(f"{what}: maps and masks must be torch tensors")
+    if maps.dtype != torch.float32:
+        raise hip.VadError(f"{what}: maps must be float32, got {maps.dtype}")
+    if masks.is_complex():
+        raise hip.VadError(f"{what}: masks must be float, uint8, bool or integer, got {masks.dtype}")
+    max_events = _check_int(max_events, "max_events", what, 1, MAX_EVENTS)
+    if maps.dim() == 3:
+        lead = ()
+    elif maps.dim() == 4 or (maps.dim() == 5 and maps.shape[2] == 1):
+        lead = (int(maps.shape[0]),)
+    else:
+        raise hip.VadError(f"{what}: maps must be [T,H,W], [B,T,H,W] or [B,T,1,H,W], got {tuple(maps.shape)}")
+    if masks.dim() not in (3, 4, 5) or masks.numel() != maps.numel() or masks.shape[-2:] != maps.shape[-2:] or masks.shape[0] != maps.shape[0]:
+        raise hip.VadError(f"{what}: masks {tuple(masks.shape)} do not match maps {tuple(maps.shape)}")
+    if not maps.is_cuda or not masks.is_cuda:
+        raise hip.VadError(f"{what}: maps ({maps.device}) and masks ({masks.device}) must be on the GPU (events are matched on the "
+                           "device; there is no CPU fallback)")
+    if maps.device != masks.device:
+        raise hip.VadError(f"{what}: maps ({maps.device}) and masks ({masks.device}) must be on the same device")
+    t, h, w = int(maps.shape[-4] if maps.dim() == 5 else maps.shape[-3]), int(maps.shape[-2]), int(maps.shape[-1])
+    if t < 1 or h < 1 or w < 1:
+        raise hip.VadError(f"{what}: clips of {t} x {h} x {w} are out of range (T, H, W >= 1)")
+    clips = maps.reshape(-1, t, h, w).contiguous()
+    b = int(clips.shape[0])
+    m, fmt, _, _, _ = _mask_planes(masks.reshape(-1, h, w), what)
+    dev = clips.device
+
+    def result(gt_records, pred_records, counts, frame_counts):
+        return EventMatches(gt_records.view(*lead, max_events, EVMATCH_WORDS), pred_records.view(*lead, max_events, EVMATCH_WORDS),
+                            counts.view(*lead, EVMATCH_COUNTS), frame_counts.view(*lead, t, 4), (t, h, w), params)
+
+    if b == 0:                                                            # nothing to match, nothing to launch
+        return result(torch.zeros((0, max_events, EVMATCH_WORDS), dtype=torch.int32, device=dev),
+                      torch.zeros((0, max_events, EVMATCH_WORDS), dtype=torch.int32, device=dev),
+                      torch.zeros((0, EVMATCH_COUNTS), dtype=torch.int64, device=dev), torch.zeros((0, t, 4), dtype=torch.int32, device=dev))
+    with torch.cuda.device(dev):
+        l = hip.lib()
+        ws = _workspace(l.vad_event_match_workspace_bytes(b, t, h, w), dev, what,
+                        f"{b} clips of {t} x {h} x {w} are out of range (t * h * w < 2^31 - 1, b * t * h * w <= 2^38)")
+        gt_records = torch.empty((b, max_events, EVMATCH_WORDS), dtype=torch.int32, device=dev)
+        pred_records = torch.empty((b, max_events, EVMATCH_WORDS), dtype=torch.int32, device=dev)
+        counts = torch.empty((b, EVMATCH_COUNTS), dtype=torch.int64, device=dev)
+        frame_counts = torch.empty((b, t, 4), dtype=torch.int32, device=dev)
+        hip.check(l.vad_match_events(clips.data_ptr(), m.data_ptr(), fmt, b, t, h, w, params["threshold"], params["connectivity"],
+                                     params["temporal"], params["min_duration"], params["min_volume"], params["gt_fraction"],
+                                     params["pred_fraction"], max_events, gt_records.data_ptr(), pred_records.data_ptr(), counts.data_ptr(),
+                                     frame_counts.data_ptr(), ws.data_ptr(), ws.numel(), hip.current_stream()), "vad_match_events")
+    _launched(ws, what)
+    return result(gt_records, pred_records, counts, frame_counts)
+
+
+def event_report_from_counts(counts) -> dict:
+    """The operating-point report of a debounced alarm from the 22 sums of `vad_match_events`' counters (`EVENT_COUNT_NAMES`), on the
+    host - usable on a machine without a GPU.  Event level: track_recall = detected / tracks, event_precision = matched / kept
+    events, event_f1 their harmonic mean, false-alarm events per frame and per clip.  Voxel level: precision, recall, IoU, Dice.
+    Delay: mean_delay = the sum of the delays / detected tracks, in frames; immediate = the share of the detected tracks found in
+    their first frame.  Frame level (a frame is positive with a mask voxel, alarmed with a voxel of a kept event - `alarms()`):
+    precision, recall, F1.  Clip level (positive with a track, alarmed with a kept event) likewise.  A ratio whose denominator is 0
+    is nan."""
+    c = [int(v) for v in np.asarray(counts).reshape(-1)]
+    if len(c) != EVMATCH_COUNTS or min(c) < 0:
+        raise hip.VadError(f"event_report_from_counts: counts must be {EVMATCH_COUNTS} non-negative integers, got {counts!r}")
+    gt, det, pred, matched, fa, _, tp, fp, fn, _, _, _, delay_sum, immediate, f_both, f_pred, f_gt, f_none, c_both, c_pred, c_gt, c_none = c
+    frames, clips = f_both + f_pred + f_gt + f_none, c_both + c_pred + c_gt + c_none
+    recall, precision = _ratio(det, gt), _ratio(matched, pred)
+    out = {name: v for name, v in zip(EVENT_COUNT_NAMES, c)}
+    out.update({"frames": frames, "clips": clips, "track_recall": recall, "event_precision": precision,
+                "event_f1": 2.0 * precision * recall / (precision + recall) if precision + recall > 0 else float("nan"),
+                "false_alarm_events_per_frame": _ratio(fa, frames), "false_alarm_events_per_clip": _ratio(fa, clips),
+                "voxel_precision": _ratio(tp, tp + fp), "voxel_recall": _ratio(tp, tp + fn), "voxel_iou": _ratio(tp, tp + fp + fn),
+                "voxel_dice": _ratio(2 * tp, 2 * tp + fp + fn),
+                "mean_delay": _ratio(delay_sum, det), "immediate": _ratio(immediate, det),
+                "frame_precision": _ratio(f_both, f_both + f_pred), "frame_recall": _ratio(f_both, f_both + f_gt),
+                "frame_f1": _ratio(2 * f_both, 2 * f_both + f_pred + f_gt),
+                "clip_precision": _ratio(c_both, c_both + c_pred), "clip_recall": _ratio(c_both, c_both + c_gt),
+                "clip_f1": _ratio(2 * c_both, 2 * c_both + c_pred + c_gt)})
+    return out
+
+
+class EventCounts:
+    """The 22 counters of `match_events` summed over clips: an int64 `[22]` device tensor (`EVENT_COUNT_NAMES`) and the operating
+    point they were gathered at - `params` = {threshold, connectivity, temporal, min_duration, min_volume, gt_fraction,
+    pred_fraction} plus whatever `meta` the caller adds (`scoring.event_report`: map, sigma, truncate, morph, calibrated, the
+    filters).  Counters gathered at another operating point are refused with `ValueError`, as in `DetectionCounts`.  Integer sums:
+    the result does not depend on batching or sharding, and ranks combine with ONE all-reduce."""
+
+    def __init__(self, device="cuda", params: Optional[dict] = None):
+        self.counts = torch.zeros(EVMATCH_COUNTS, dtype=torch.int64, device=device)
+        self.params = dict(params) if params else None
+
+    def _adopt(self, params, what: str) -> None:
+        if params is None:
+            return
+        if self.params is None:
+            self.params = dict(params)
+        elif self.params != dict(params):
+            raise ValueError(f"{what}: these counters were gathered with {self.params}, the others with {dict(params)}")
+
+    def update(self, matches: EventMatches, meta: Optional[dict] = None) -> "EventCounts":
+        """Add the clips of one `match_events` result (one reduction on the device; nothing is read by the host)."""
+        if not isinstance(matches, EventMatches):
+            raise hip.VadError(f"EventCounts.update: matches must be a metrics.EventMatches, got {type(matches).__name__}")
+        if matches.counts.device != self.counts.device:
+            raise hip.VadError(f"EventCounts.update: the matches are on {matches.counts.device}, the counters on {self.counts.device}")
+        self._adopt({**matches.params, **(meta or {})}, "EventCounts.update")
+        self.counts += matches.counts.reshape(-1, EVMATCH_COUNTS).sum(dim=0)
+        return self
+
+    def merge(self, other: "EventCounts") -> "EventCounts":
+        """self += other (two halves of a dataset, or the states of several ranks after a gather)."""
+        if not isinstance(other, EventCounts):
+            raise hip.VadError(f"EventCounts.merge: other must be an EventCounts, got {type(other).__name__}")
+        self._adopt(other.params, "EventCounts.merge")
+        self.counts += other.counts.to(self.counts.device)
+        return self
+
+    def all_reduce(self, group=None, force_collective: bool = False) -> int:
+        """Sum the counters over the ranks of `group` (`allreduce_counters_`: one all_reduce).  Like `DetectionCounts.all_reduce` it
+        carries the 22 words only: ranks compare their `params` themselves where they may differ.  Returns the world size."""
+        return allreduce_counters_(self.counts, group, force_collective)
+
+    def report(self) -> dict:
+        """`event_report_from_counts` of the sums (one 176-byte copy to the host) with the operating point under 'params'."""
+        out = event_report_from_counts(self.counts.cpu().numpy())
+        out["params"] = None if self.params is None else dict(self.params)
+        return out
+
+
 # ====================================================================== per-frame tracks of anomaly events
 # An event record holds the union box over the event's whole life; for anything that moves that is a smear over its path (DESIGN.md
 # section 4.24).  A cross-section is the set of one event's pixels in one frame, as a record in the layout of `Regions`: a box that

@@ -623,7 +623,7 @@ def detection_report(model, loader: Iterable[dict], device, threshold: float, ma
     alarms per frame it raises, which pixel IoU it reaches - the questions AUROC and AUPRO, which rank pixels over all thresholds and
     know nothing of `min_area` or of regions as units, do not answer.  The loop of `pixel_aupro`, over the same batches: {'image'
     [B,C,H,W], 'mask' [B,1,H,W]} for the image model, {'frames' [B,T,C,H,W], 'mask' [B,T,1,H,W]} for the video model (map "mse" only;
-    every frame is matched on its own).  The maps come from the chain `localize` thresholds (`map`, `sigma`, `truncate`,
+    every frame is matched on its own; `event_report` matches the events of a clip).  The maps come from the chain `localize` thresholds (`map`, `sigma`, `truncate`,
     `calibration`, `min_std`, `morph` as there), so the report is of exactly the detections `localize(threshold, connectivity,
     min_area)` returns.  Each batch is ONE scoring call, the optional smoothing / calibration / morphology calls and ONE
     `metrics.match_regions`, whose 16 counters per frame are summed on the device; no map or mask is copied to the host.
@@ -760,6 +760,55 @@ def localize_events(model, images, threshold: float, map: str = "mse", sigma=Non
         if tracks:
             events.tracks = metrics.event_tracks(volumes, events)
         return events, maps
+
+
+def event_report(model, loader: Iterable[dict], device, threshold: float, map: str = "mse", sigma=None, truncate: float = 4.0,
+                 calibration=None, min_std: Optional[float] = None, morph=(), connectivity: int = 8, temporal: int = 9, min_duration: int = 1,
+                 min_volume: int = 1, gt_fraction: float = 0.0, pred_fraction: float = 0.0, counts=None, temporal_filter=None, *,
+                 rank_filter=None):
+    """What a debounced alarm does against the ground-truth masks: how many of the labelled anomalies the kept events still find,
+    how many false-alarm events they raise, how many frames after a defect appears the alarm fires, and the frame-level precision and
+    recall of `events.alarms()` - what `detection_report`, which matches every frame on its own, cannot see of `min_duration`,
+    `min_volume` and the links in time.  The chain and the conventions of `localize_events` (`map`, `sigma`, `truncate`,
+    `calibration`, `min_std`, `morph`, `rank_filter`, `temporal_filter`, `connectivity`, `temporal`, `min_duration`, `min_volume` as
+    there), so the report is of exactly the events `localize_events` returns.  Video batches are {'frames' [B,T,C,H,W], 'mask'
+    [B,T,1,H,W]} for the video model (map "mse" only), every clip its own volume; image batches {'image' [N,C,H,W], 'mask'
+    [N,1,H,W]} are read as one volume of N consecutive frames (no `temporal_filter`, as in `localize_events`).  Each batch is ONE
+    scoring call, the optional filter calls and ONE `metrics.match_events`, whose 22 counters per clip are summed on the device; no
+    map or mask is copied to the host.  `gt_fraction`, `pred_fraction` as in `metrics.match_events`.  Returns (report dict of
+    `metrics.event_report_from_counts`, the `metrics.EventCounts`); pass `counts` to continue an earlier evaluation or to all-reduce
+    before reading (`counts.all_reduce()`, then `counts.report()`) - counters gathered at another operating point are refused with
+    `ValueError`."""
+    what = "event_report"
+    _check_map_name(map, what)
+    morph = metrics.morph_steps(None if morph == () else morph)          # () = no morphology, like None elsewhere
+    rank_filter = metrics.rank_filter_steps(rank_filter)
+    temporal_filter = metrics.temporal_steps(temporal_filter)
+    min_std = _check_calibration(calibration, what, map, sigma, truncate, min_std)
+    params = metrics._event_match_params(what, threshold, connectivity, temporal, min_duration, min_volume, gt_fraction, pred_fraction)
+    meta = dict(_map_meta(map, sigma, truncate), morph=tuple(morph), calibrated=calibration is not None,
+                min_std=None if calibration is None else float(min_std))
+    if temporal_filter:
+        meta["temporal_filter"] = tuple(temporal_filter)
+    if rank_filter:
+        meta["rank_filter"] = tuple(rank_filter)
+    if counts is None:
+        counts = metrics.EventCounts(device)
+    elif not isinstance(counts, metrics.EventCounts):
+        raise hip.VadError(f"{what}: counts must be a metrics.EventCounts, got {type(counts).__name__}")
+    counts._adopt({**params, **meta}, what)
+    with torch.no_grad():
+        for batch in loader:
+            video = "frames" in batch
+            if video and map != "mse":
+                _refuse_clips_on(map, what, "reported")
+            maps, masks = _masked_maps(model, batch, device, map, sigma, truncate, calibration, min_std, morph, "frames" if video else "image",
+                                       temporal_filter, what, rank_filter)
+            if not video:                                                 # the image batch as one clip [N,H,W]
+                maps, masks = maps[:, 0], masks.reshape(maps.shape[0], *maps.shape[-2:])
+            counts.update(metrics.match_events(maps, masks, threshold, connectivity, temporal, min_duration, min_volume, gt_fraction,
+                                               pred_fraction, max_events=1), meta)
+    return counts.report(), counts
 
 
 def localize_stream(model, frames, tracker, state=None, sigma=None, truncate: float = 4.0, calibration=None, min_std: Optional[float] = None,
